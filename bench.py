@@ -6,12 +6,18 @@ camera frames that are already resident in HBM.  Workload (BASELINE.json
 configs[1], "C2"): 2048-sample x 1000-line u16 frames, N = 2048, D = 1024,
 Bartlett-Hann window, 1-row background, whole chain to dB.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line (metric = A-scans/s, whole job).  For N > 1 every
 rank owns one GPU and its own frame shard; the only collective is the set-up
 broadcast of the constant state (RCCL), so scaling is "weak".
+
+A plain run sets up, ramps the clocks, warms up, times the K steps and prints
+the line.  --full adds what else the line can carry (package power, CPU
+baselines, the parity check against the oracle, per-stage, half-chip,
+division-setting and sustained legs, copy-rate ceilings): untimed extras that
+run after the timed region.
 """
 import argparse
 import glob
@@ -28,6 +34,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_ACHIEVABLE_GBS = 6290.0  # MI355X_MICROARCH.md: 6.29 TB/s measured (float4 copy, 79 %)
+DUMP_BYTES = 60_000_000      # --dump-outputs: at most this many bytes of results
 
 WORKLOADS = {
     # name: (W, H, N, D, A, window, phase)
@@ -223,6 +230,22 @@ class PowerSampler:
         return out
 
 
+def dump_outputs(out, out_dir, name="bscan_db"):
+    """Writes the tensor `out` to out_dir/<name>.npy as float32: whole when it fits in DUMP_BYTES, else a sample of its rows
+    (last dimension), the same for every run of the same shape (seed 0, rows in ascending order), as a (rows, out.shape[-1])
+    array.  Returns the path."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rows = out.reshape(-1, out.shape[-1])
+    keep = DUMP_BYTES // (rows.shape[1] * 4)
+    if rows.shape[0] > keep:
+        sel = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+        out = rows[torch.from_numpy(sel).to(rows.device)]
+    path = os.path.join(out_dir, name + ".npy")
+    np.save(path, out.float().cpu().numpy())
+    return path
+
+
 def process_group_problems(ranks_seen, n_gpus, devices, share_gpu):
     """What makes an N > 1 line unusable as a scaling point: a process group that does not hold N ranks, or two ranks
     on one device (by PCI address) outside the --share-gpu rehearsal.  Returns a list of messages, empty when the group is sound."""
@@ -255,11 +278,17 @@ def self_launch(nproc):
     return subprocess.run(cmd, env=env).returncode
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: the workload's own, else 1000)")
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: package power sampling, the CPU baselines, the parity check "
+                         "against the oracle, the staged, half-chip, division-setting and sustained legs, the copy-rate ceilings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the dB B-scans of the last timed step (rank 0) to DIR/bscan_db.npy, float32: all of them when they fit "
+                         "in %d bytes, else a fixed seeded sample of rows (dump_outputs)" % DUMP_BYTES)
     ap.add_argument("--ramp-seconds", type=float, default=1.0,
                     help="untimed back-to-back steps run before the warmup so that the timed region starts in the SUSTAINED state: "
                          "memory / fabric clocks up (they need ~0.25 s of unbroken load) and the package at its power cap "
@@ -268,10 +297,10 @@ def main():
     ap.add_argument("--frames-per-step", type=int, default=0, help="frames per step per GPU (0 = auto)")
     ap.add_argument("--ring", type=int, default=0, help="resident frames per GPU (0 = auto, >= 1 GiB)")
     ap.add_argument("--distinct", type=int, default=16, help="distinct synthetic frames generated (tiled into the ring)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: seconds of the single-core CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-workers", type=int, default=16,
-                    help="worker threads of the multi-core CPU figure (0 = every schedulable CPU; default 16 = a 1-GPU box's share)")
+                    help="with --full: worker threads of the multi-core CPU figure (0 = every schedulable CPU; default 16 = a 1-GPU box's share)")
     ap.add_argument("--threads-per-block", type=int, default=0)
     ap.add_argument("--blocks", type=int, default=0)
     ap.add_argument("--plan", type=int, default=-1, help="FFT plan id (tuning; -1 = library default, -2 = the any-configuration kernel)")
@@ -286,10 +315,10 @@ def main():
                     help="full H x W background frame (what the reference's 'b' key stores) instead of one spectrum: "
                          "+W*4 algorithmic bytes per A-scan, reported as its own mode (SURVEY 8d)")
     ap.add_argument("--stage-steps", type=int, default=50,
-                    help="untimed two-kernel (resample stage, FFT stage) steps run AFTER the timed region so that the line "
+                    help="with --full: untimed two-kernel (resample stage, FFT stage) steps run AFTER the timed region so that the line "
                          "carries each stage's HBM roofline (0 = skip)")
     ap.add_argument("--half-chip-steps", type=int, default=200,
-                    help="untimed steps on half of the compute units after the timed region: the per-clock rate below the power cap, "
+                    help="with --full: untimed steps on half of the compute units after the timed region: the per-clock rate below the power cap, "
                          "reported as `half_chip` (0 = skip)")
     ap.add_argument("--staged", action="store_true",
                     help="run the path as two kernels (resample stage, FFT stage) and report each stage's HBM roofline; "
@@ -307,13 +336,20 @@ def main():
                     help="time the run with the OPT-OUT fdoct_set_precise_division(h, 0): one f32 reciprocal of the background on the "
                          "fused fast path (outside the tolerance on fringes below ~1 %% of the DC level); reported as its own mode")
     ap.add_argument("--precise-steps", type=int, default=200,
-                    help="untimed steps with the OTHER division setting after the timed region (the one-word opt-out next to the "
+                    help="with --full: untimed steps with the OTHER division setting after the timed region (the one-word opt-out next to the "
                          "default, or the default next to the opt-out), and the weak-fringe parity leg (fringes of 1e-3 of the DC "
                          "level against the oracle) with both settings, reported as `precise_division` (0 = skip)")
     ap.add_argument("--sustained-seconds", type=float, default=1.0,
-                    help="untimed repetition of the SAME full launch after the timed region, long enough for the power sampler "
+                    help="with --full: untimed repetition of the SAME full launch after the timed region, long enough for the power sampler "
                          "(reported as `sustained`; 0 = skip)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps is None:
+        args.steps = WORKLOADS[args.workload].get("steps", 1000)
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Invoked directly with --gpus N: start one rank per GPU as CHILD processes (torch.distributed.run) before anything
@@ -395,8 +431,6 @@ def main():
     frame_bytes = RW * RH * es
     fps = args.frames_per_step or wl.get("fps") or max(A, (1 << 30) // frame_bytes // A * A)     # ~1 GiB of input per step
     ring = args.ring or wl.get("ring") or 2 * fps                                # two steps' worth resident (2 GiB)
-    if "steps" in wl and "--steps" not in sys.argv:
-        args.steps = wl["steps"]
     ring = (ring + fps - 1) // fps * fps
     distinct = max(A, min(args.distinct, ring))
 
@@ -494,7 +528,7 @@ def main():
     # between the last warmup launch and the first timed one
     ev0 = torch.cuda.Event(enable_timing=True)
     ev1 = torch.cuda.Event(enable_timing=True)
-    psamp = PowerSampler(dev.index if dev.index is not None else 0) if rank == 0 else None
+    psamp = PowerSampler(dev.index if dev.index is not None else 0) if rank == 0 and args.full else None
     if psamp is not None:
         psamp.start()
     for i in range(args.warmup):
@@ -520,6 +554,8 @@ def main():
     if psamp is not None:
         psamp.stop()
     wall_elapsed = fdist.max_over_ranks(elapsed, cdev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(d_out, args.dump_outputs)
     k_avg_ms = ev0.elapsed_time(ev1) / args.steps
     # what the timed launches ran on (fdoct_last_kernel): the label of the roofline object
     from fdoct_amd import capi as _capi
@@ -553,7 +589,7 @@ def main():
     # for the hwmon power average.  The SAME full launch repeats here, untimed (never part of `value` / `roofline`), for
     # --sustained-seconds with the sampler running.
     sustained = None
-    if rank == 0 and args.sustained_seconds > 0:
+    if rank == 0 and args.full and args.sustained_seconds > 0:
         sps = PowerSampler(dev.index if dev.index is not None else 0)
         se0, se1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         per_burst = max(1, int(0.02 / max(k_avg_ms * 1e-3, 1e-6)))      # ~20 ms of launches per host synchronisation
@@ -581,7 +617,7 @@ def main():
     # chain as two kernels with the k-linear rows in HBM between them.  In the default (fused) mode these are UNTIMED
     # extra steps after the timed region; `value` and `roofline` above never include them.
     can_stage = (fps <= 2048 and es == 2 and not args.general_kernel and not args.background_2d and not transposed and M == 1 and binv == 1)
-    want_stages = args.staged or (args.stage_steps > 0 and rank == 0)
+    want_stages = args.staged or (args.full and args.stage_steps > 0 and rank == 0)
     if want_stages and not can_stage:
         stages_note = ("staged kernels exist for the plain u16, row-major configuration only" if fps <= 2048 else
                        "no staged steps at this batch size (the k-linear rows of a %d-frame step would take %.0f GB); see the C2 line" % (fps, fps * H * N * 4 / 1e9))
@@ -612,7 +648,7 @@ def main():
     # (one workgroup per CU, 128 of 256), untimed extra steps after the timed region, with the power / clock of those steps.
     # `value` and `roofline` above never include them.
     half_chip = None
-    if rank == 0 and args.half_chip_steps > 0 and not args.blocks and not args.staged and not transposed:
+    if rank == 0 and args.full and args.half_chip_steps > 0 and not args.blocks and not args.staged and not transposed:
         try:
             hb = max(1, num_cu // 2)
             rec.set_launch(args.threads_per_block, hb)
@@ -648,7 +684,7 @@ def main():
     # fringes are 1e-3 of the DC level (a sample arm's return, not the synthetic mirror pair of the timed frames) against the
     # oracle, with the SURVEY tolerance.  `value` and `roofline` never include these steps.
     precise = None
-    if rank == 0 and args.precise_steps > 0 and not args.staged:
+    if rank == 0 and args.full and args.precise_steps > 0 and not args.staged:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import helpers
@@ -729,7 +765,7 @@ def main():
     # parity spot check of the timed configuration (rank 0): first rows of the last batch vs the oracle
     parity = None
     cpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import helpers
@@ -796,7 +832,7 @@ def main():
     # context for the roofline fraction: the device-to-device copy rate this GPU reaches right now, and
     # the FFT arithmetic rate (5 N log2 N per complex transform, half of it for real rows)
     copy_gbs = copy_f4 = copy_f4_note = None
-    if rank == 0:
+    if rank == 0 and args.full:
         src_t = d_ring.view(torch.uint8).reshape(-1)
         dst_t = torch.empty_like(src_t[: min(src_t.numel(), 1 << 30)])
         ce0, ce1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -895,7 +931,7 @@ def main():
             "precise_division": precise,
             "process_group": group,
         }
-        if world > 1:
+        if world > 1 and args.full:
             out["cpu_baseline_note"] = "the CPU baseline is timed at N = 1 only (rank 0 of a one-GPU run)"
         # Second ceilings (every BASELINE workload sits at the package power cap, so HBM bandwidth alone mis-prices
         # the instruction-heavy ones).  (1) package power: what this run drew against the cap, the energy per input A-scan and

@@ -150,6 +150,40 @@ def test_bench_launches_its_own_ranks_as_child_processes(monkeypatch):
     assert e.value.code == 0 and calls == [4]
 
 
+def test_bench_arguments(monkeypatch):
+    """--steps sets the timed steps in every spelling, also on workloads with a step count of their own; a plain run has
+    --full off and writes no outputs."""
+    import importlib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    monkeypatch.syspath_prepend(root)
+    bench = importlib.import_module("bench")
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert bench.parse_args([]).steps == 1000
+    assert bench.parse_args(["--workload", "C5"]).steps == bench.WORKLOADS["C5"]["steps"]
+    assert bench.parse_args(["--workload", "C5", "--steps=7"]).steps == 7
+    assert bench.parse_args(["--workload=LONG", "--steps", "3"]).steps == 3
+    assert bench.parse_args(["--full", "--dump-outputs", "out"]).full and bench.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+def test_bench_dump_outputs_whole_or_a_fixed_sample(monkeypatch, tmp_path):
+    """--dump-outputs writes the result whole when it fits the byte budget, else the same seeded sample of rows every time."""
+    import importlib
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    monkeypatch.syspath_prepend(root)
+    bench = importlib.import_module("bench")
+    out = torch.arange(6 * 50 * 8, dtype=torch.float32).reshape(6, 50, 8)
+    whole = np.load(bench.dump_outputs(out, str(tmp_path / "whole")))
+    assert whole.dtype == np.float32 and np.array_equal(whole, out.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * 8 * 4)
+    a = np.load(bench.dump_outputs(out, str(tmp_path / "a")))
+    b = np.load(bench.dump_outputs(out, str(tmp_path / "b")))
+    assert a.shape == (100, 8) and a.dtype == np.float32 and a.nbytes <= bench.DUMP_BYTES and np.array_equal(a, b)
+    rows = (a[:, 0] / 8).astype(np.int64)
+    assert (np.diff(rows) > 0).all() and np.array_equal(a, out.numpy().reshape(-1, 8)[rows])
+
+
 def test_bench_process_group_check(monkeypatch):
     """bench.py refuses (exit code 3, no JSON line) a process group that is not N ranks on N devices: the rule itself, on the
     CPU (its use under a launcher runs on the GPU box: tests/test_gpu_c5.py::test_bench_refuses_a_world_size_that_is_not_gpus)."""

@@ -83,7 +83,7 @@ def test_bench_direct_launch_of_two_ranks_without_a_launcher():
     share this box's one GPU over gloo (RCCL refuses two ranks on one device); on a multi-GPU node the default backend is
     nccl = RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo", "--steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--backend", "gloo", "--steps", "3",
            "--warmup", "1", "--ramp-seconds", "0", "--frames-per-step", "6", "--no-cpu-baseline", "--stage-steps", "0",
            "--half-chip-steps", "0", "--sustained-seconds", "0.2"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280, env=env)

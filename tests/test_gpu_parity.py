@@ -1632,14 +1632,14 @@ def test_fast_path_options_on_the_2048_point_plan():
 
 
 def test_bench_contract_line(monkeypatch, capsys):
-    """bench.py prints ONE JSON line with the contract's keys (small batch, two timed steps), including the roofline
+    """bench.py --full prints ONE JSON line with the contract's keys (small batch, two timed steps), including the roofline
     and cpu_baseline objects, and its own parity spot check passes."""
     import importlib
     import json
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     monkeypatch.syspath_prepend(root)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", "--warmup", "1", "--ramp-seconds", "0", "--frames-per-step", "6",
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "2", "--warmup", "1", "--ramp-seconds", "0", "--frames-per-step", "6",
                                       "--cpu-seconds", "0.5", "--stage-steps", "3", "--half-chip-steps", "2", "--sustained-seconds", "0.2"])
     bench = importlib.import_module("bench")
     bench.main()
@@ -1659,7 +1659,7 @@ def test_bench_contract_line(monkeypatch, capsys):
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] == 1
     assert "failed" not in d["parity"]
     assert 0.0 <= d["parity"]["flat_1e-3_dB_pass_rate"] <= 1.0
-    # the per-stage roofline (north star: resample and FFT stages) rides in the default line
+    # the per-stage roofline (north star: resample and FFT stages) rides in the --full line
     assert [s["stage"] for s in d["stages"]] == ["resample", "fft_mag_log"]
     for s in d["stages"]:
         assert s["kernel_ms_avg"] > 0 and abs(s["frac"] - s["achieved"] / s["peak"]) < 1e-3
@@ -1684,6 +1684,43 @@ def test_bench_contract_line(monkeypatch, capsys):
         assert rp["bound"] == "package_power" and abs(rp["frac"] - rp["achieved"] / rp["peak"]) < 1e-3 and rp["uj_per_ascan"] > 0
 
 
+def test_bench_plain_line_and_dumped_outputs(monkeypatch, capsys, tmp_path):
+    """A plain bench run (no --full) prints the headline line without the untimed extras, and --dump-outputs writes what its
+    last timed step computed: the dB B-scans of that step's frames, as the host entry point computes them, the same in two runs."""
+    import importlib
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    monkeypatch.syspath_prepend(root)
+    bench = importlib.import_module("bench")
+    W, H, D, fps = 2048, 1000, 1024, 6
+    lines = []
+    for run in ("a", "b"):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--ramp-seconds", "0", "--frames-per-step", str(fps),
+                                          "--dump-outputs", str(tmp_path / run)])
+        bench.main()
+        lines += [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 2
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "A-scans/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - fps * H / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    for k in ("power", "sustained", "cpu_baseline", "parity", "precise_division"):
+        assert d[k] is None, k
+    for k in ("stages", "half_chip", "roofline_power"):
+        assert k not in d, k
+    assert d["roofline"]["copy_f4_gbs"] is None
+    got = np.load(tmp_path / "a" / "bscan_db.npy")
+    assert got.dtype == np.float32 and got.shape == (fps, H, D)
+    np.testing.assert_array_equal(got, np.load(tmp_path / "b" / "bscan_db.npy"))
+    # the ring holds two steps of frames 0..11; the last timed step (index warmup + steps - 1 = 3) ran on the second half
+    frames = synth.make_frames(0, 2 * fps, W, H)[fps:]
+    r = Reconstructor(Config(width=W, height=H, numfftpoints=2048, numdisplaypoints=D))
+    r.set_background(synth.make_background(W))
+    b, db = r.process(frames)
+    r.close()
+    helpers.check_db(got, db, b, "bench --dump-outputs against the host entry point")
+
+
 def test_bench_two_ranks_rehearsal_on_one_gpu():
     """The N > 1 launch contract (torch.distributed.run, one rank per process, set-up broadcast of the state blob, barrier +
     MAX-over-ranks timing) rehearsed with two ranks sharing this GPU over gloo (RCCL refuses two ranks on one device)."""
@@ -1696,7 +1733,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo",
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--backend", "gloo",
            "--steps", "3", "--warmup", "1", "--ramp-seconds", "0", "--frames-per-step", "6", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]

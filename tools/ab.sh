@@ -12,7 +12,7 @@ for round in $(seq 1 "$rounds"); do
     lib="$root/fdoct_amd/libfdoct_hip_$v.so"; [ "$v" = base ] && lib="$root/fdoct_amd/libfdoct_hip.so"
     [ -f "$lib" ] || { echo "missing $lib"; exit 1; }
     # shellcheck disable=SC2046
-    env FDOCT_LIB="$lib" $(echo "$envs" | tr ',' ' ') python3 bench.py --steps ${AB_STEPS:-600} --warmup 20 --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 --precise-steps 0 $AB_ARGS 2>/dev/null | python3 -c "
+    env FDOCT_LIB="$lib" $(echo "$envs" | tr ',' ' ') python3 bench.py --full --steps ${AB_STEPS:-600} --warmup 20 --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 --precise-steps 0 $AB_ARGS 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -9,7 +9,7 @@ for round in $(seq 1 "$rounds"); do
   i=0
   for v in "$@"; do
     i=$((i+1))
-    FDOCT_JIT_DEFINES="$v" FDOCT_JIT_CACHE=/tmp/abjit_$i python3 bench.py ${AB_ARGS:---workload INI} --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 --precise-steps 0 2>/dev/null | python3 -c "
+    FDOCT_JIT_DEFINES="$v" FDOCT_JIT_CACHE=/tmp/abjit_$i python3 bench.py --full ${AB_ARGS:---workload INI} --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 --precise-steps 0 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

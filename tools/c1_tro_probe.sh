@@ -3,7 +3,7 @@
 # transposed store against the row-major chain and the two-pass route, under wave counts, ring sizes and both division settings.
 # usage: gpurun -- 'bash tools/c1_tro_probe.sh [base|words|groups]'   -> gpurun_out/r6_c1_tro_probe.txt
 cd "$(dirname "${BASH_SOURCE[0]}")/.." || exit 1
-run() { label="$1"; shift; python3 bench.py --workload C1 --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 --precise-steps 0 --steps 300 "$@" 2>/dev/null | python3 -c "
+run() { label="$1"; shift; python3 bench.py --full --workload C1 --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 --precise-steps 0 --steps 300 "$@" 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,13 +1,14 @@
 #!/bin/bash
-# One script for a round's GPU calls (it replaces round 5's r5_*.sh one-offs).  usage, always through gpurun:
-#   gpurun --timeout 1200 -- 'bash tools/gpu_round.sh suite'          the whole GPU suite as the driver runs it + the default and
-#                                                                     the driver-sized bench line; writes gpurun_out/truth_table.txt
-#   gpurun --timeout 1200 -- 'bash tools/gpu_round.sh fuzz [set]'     the seeded sweeps of one set (first | other | final | fresh | fresh2 | fresh3 | bandpass), FIVE processes side by side
-#                                                                     (a sweep is bound by the CPU oracle, not by the GPU)
-#   gpurun --timeout 900  -- 'bash tools/gpu_round.sh tests <pytest args>'   a part of the suite
-#   gpurun --timeout 900  -- 'bash tools/gpu_round.sh wl C1 C3 C4 INI'       bench lines of other workloads (both layouts)
+# One script for a round's GPU runs.  Logs, bench lines and the truth table go to $OUT_DIR (default build/gpu_round).  usage:
+#   bash tools/gpu_round.sh suite                 the whole GPU suite + the --full and the driver-sized bench line; writes
+#                                                 $OUT_DIR/<tag>_truth_table.txt
+#   bash tools/gpu_round.sh fuzz [set]            the seeded sweeps of one set (first | other | final | fresh | fresh2 | fresh3 | bandpass),
+#                                                 FIVE processes side by side (a sweep is bound by the CPU oracle, not by the GPU)
+#   bash tools/gpu_round.sh tests <pytest args>   a part of the suite
+#   bash tools/gpu_round.sh wl C1 C3 C4 INI       --full bench lines of other workloads (both layouts)
 cd "$(dirname "${BASH_SOURCE[0]}")/.." || exit 1
-mkdir -p gpurun_out
+out=${OUT_DIR:-build/gpu_round}
+mkdir -p "$out"
 tag=${TAG:-r6}
 what=${1:-suite}; shift
 line() { python3 - "$1" <<'PY'
@@ -20,24 +21,24 @@ PY
 }
 case $what in
   suite)
-    FDOCT_TRUTH_TABLE=gpurun_out/${tag}_truth_table.txt timeout -k 10 1000 python3 -m pytest tests -x -q -m gpu > gpurun_out/${tag}_tests.log 2>&1
-    rc=$?; echo "pytest exit $rc" >> gpurun_out/${tag}_tests.log; tail -8 gpurun_out/${tag}_tests.log
-    head -3 gpurun_out/${tag}_truth_table.txt
+    FDOCT_TRUTH_TABLE=$out/${tag}_truth_table.txt timeout -k 10 1000 python3 -m pytest tests -x -q -m gpu > $out/${tag}_tests.log 2>&1
+    rc=$?; echo "pytest exit $rc" >> $out/${tag}_tests.log; tail -8 $out/${tag}_tests.log
+    head -3 $out/${tag}_truth_table.txt
     [ $rc -eq 0 ] || exit $rc
-    python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err && line gpurun_out/${tag}_bench.json &&
-    python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${tag}_bench_driver.json 2>/dev/null && line gpurun_out/${tag}_bench_driver.json ;;
+    python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err && line $out/${tag}_bench.json &&
+    python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_driver.json 2>/dev/null && line $out/${tag}_bench_driver.json ;;
   tests)
-    FDOCT_TRUTH_TABLE=gpurun_out/${tag}_truth_table_part.txt timeout -k 10 800 python3 -m pytest -x -q -m gpu "$@" > gpurun_out/${tag}_tests_part.log 2>&1
-    rc=$?; tail -15 gpurun_out/${tag}_tests_part.log; exit $rc ;;
+    FDOCT_TRUTH_TABLE=$out/${tag}_truth_table_part.txt timeout -k 10 800 python3 -m pytest -x -q -m gpu "$@" > $out/${tag}_tests_part.log 2>&1
+    rc=$?; tail -15 $out/${tag}_tests_part.log; exit $rc ;;
   wl)
     for w in "$@"; do
       for lay in rowmajor transposed; do
-        python3 bench.py --workload $w --layout $lay --no-cpu-baseline > gpurun_out/${tag}_wl_${w}_${lay}.json 2>/dev/null && line gpurun_out/${tag}_wl_${w}_${lay}.json || echo "$w $lay failed"
+        python3 bench.py --full --workload $w --layout $lay --no-cpu-baseline > $out/${tag}_wl_${w}_${lay}.json 2>/dev/null && line $out/${tag}_wl_${w}_${lay}.json || echo "$w $lay failed"
       done
     done ;;
   fuzz)
     set_=${1:-first}
-    out=gpurun_out/${tag}_fuzz_${set_}_summary.txt
+    sum=$out/${tag}_fuzz_${set_}_summary.txt
     # <seed> <cases> <shares: jit, long rows, forced routes, weak frames, tall frames, device pointers, reuse>
     case $set_ in
       first) runs=("6101 260 0.2 0.1 0.2 0.3 0.2 0.2 0.2" "6102 260 0.2 0.1 0.2 0.3 0.2 0.2 0.2" "5501 350 0.2 0.1 0.2 0.3 0.2 0.2 0.2" "5401 300 0.7 0 0.2 0.3 0.2 0.2 0.2" "5601 300 0.2 0.1 0.2 0.3 0.2 0.2 0.2") ;;
@@ -50,24 +51,24 @@ case $what in
                 runs=("6401 260 0.4 0 1 0.4 0.1 0.2 0.1" "6402 260 0.6 0 1 0.5 0.1 0.2 0.1" "6403 260 0.2 0.1 1 0.3 0.2 0.2 0.2" "6404 260 0.5 0 1 0.5 0 0 0" "6405 260 0.3 0 1 0.2 0.3 0.3 0.3") ;;
       *) echo "unknown set $set_"; exit 2 ;;
     esac
-    : > $out
+    : > $sum
     pids=()
     for r in "${runs[@]}"; do
       seed=${r%% *}
-      ( OMP_NUM_THREADS=1 timeout -k 10 ${LIMIT:-1050} python3 tools/fuzz_parity.py $r > gpurun_out/${tag}_fuzz_$seed.log 2>&1; echo "exit $?" >> gpurun_out/${tag}_fuzz_$seed.log ) &
+      ( OMP_NUM_THREADS=1 timeout -k 10 ${LIMIT:-1050} python3 tools/fuzz_parity.py $r > $out/${tag}_fuzz_$seed.log 2>&1; echo "exit $?" >> $out/${tag}_fuzz_$seed.log ) &
       pids+=($!)
     done
     # progress lines so that the call is not taken for hung
     while :; do
       alive=0; for p in "${pids[@]}"; do kill -0 $p 2>/dev/null && alive=1; done
       [ $alive -eq 0 ] && break
-      sleep 60; wc -l gpurun_out/${tag}_fuzz_*.log | tail -1
+      sleep 60; wc -l $out/${tag}_fuzz_*.log | tail -1
     done
     for r in "${runs[@]}"; do
       seed=${r%% *}
-      echo "== $r" >> $out
-      grep -E "^FAIL|^truth |failures:|^exit" gpurun_out/${tag}_fuzz_$seed.log | tail -14 >> $out
+      echo "== $r" >> $sum
+      grep -E "^FAIL|^truth |failures:|^exit" $out/${tag}_fuzz_$seed.log | tail -14 >> $sum
     done
-    cat $out ;;
+    cat $sum ;;
   *) echo "unknown target $what"; exit 2 ;;
 esac

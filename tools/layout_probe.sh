@@ -12,7 +12,7 @@ for round in 1 2; do
 for v in $vars; do
   lib="$root/fdoct_amd/libfdoct_hip_$v.so"; [ "$v" = base ] && lib="$root/fdoct_amd/libfdoct_hip.so"
   for mb in 0 16 32 64 128 256; do
-    FDOCT_LIB="$lib" FDOCT_TR_CHUNK_MB=$mb python3 bench.py --layout transposed --steps 400 --warmup 20 --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 2>/dev/null | python3 -c "
+    FDOCT_LIB="$lib" FDOCT_TR_CHUNK_MB=$mb python3 bench.py --full --layout transposed --steps 400 --warmup 20 --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

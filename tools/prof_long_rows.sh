@@ -5,7 +5,7 @@
 # gpurun -- 'bash tools/prof_long_rows.sh'  ->  gpurun_out/long_rows.txt
 cd "$GRAFT_REPO_ROOT" || exit 1
 out=gpurun_out/long_rows.txt; : > $out
-B="--no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 --precise-steps 0"
+B="--full --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 --precise-steps 0"
 line() {  # label, env..., workload
   local label=$1; shift; local wl=${!#}; set -- "${@:1:$(($#-1))}"
   echo "== --workload $wl $label" >> $out

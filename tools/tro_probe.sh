@@ -21,7 +21,7 @@ run() {  # label, variant, "ENV=.. ENV2=.." (or -), bench args...
   local label=$1 v=$2 envs=$3; shift 3
   [ "$envs" = - ] && envs=""
   # shellcheck disable=SC2086
-  env FDOCT_LIB="$(lib "$v")" $envs python3 bench.py --steps ${AB_STEPS:-400} --warmup 20 --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 --precise-steps 0 "$@" 2>/dev/null | python3 -c "
+  env FDOCT_LIB="$(lib "$v")" $envs python3 bench.py --full --steps ${AB_STEPS:-400} --warmup 20 --no-cpu-baseline --half-chip-steps 0 --sustained-seconds 0 --stage-steps 0 --precise-steps 0 "$@" 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
