@@ -8,15 +8,56 @@
 
 using namespace fdoct_impl;
 
+using HandlePtr = std::unique_ptr<fdoct_ctx, int (*)(fdoct_handle)>;  // (deleter: fdoct_destroy)
+
+// Waits for everything the handle has enqueued: nothing is left in flight that still points at the caller's buffers or the
+// chunk slots.
+static void drain(fdoct_ctx* h) {
+  if (h->s_in) (void)hipStreamSynchronize(h->s_in);
+  (void)hipStreamSynchronize(h->stream);
+  if (h->s_out) (void)hipStreamSynchronize(h->s_out);
+}
+
+// The one handler of every entry point (include/fdoct.h: nothing throws across the boundary).  Out of host memory is
+// FDOCT_ERR_NOMEM, any other exception FDOCT_ERR_DEVICE, and the text goes where fdoct_last_error finds it.  A handle's device
+// state is rebuilt by its next call (an exception may have cut an upload short) and the handle's streams are drained.
+static int caught(fdoct_ctx* h) noexcept {
+  int code = FDOCT_ERR_DEVICE;
+  const char* what = "unknown exception";
+  try {
+    throw;
+  } catch (const std::bad_alloc&) {
+    code = FDOCT_ERR_NOMEM;
+    what = "out of host memory";
+  } catch (const std::exception& e) {
+    what = e.what();
+  } catch (...) {
+  }
+  std::string& err = h ? h->err : g_create_error;
+  try {
+    err = what;
+  } catch (...) {
+    err.clear();
+  }
+  if (h) {
+    h->dirty = true;
+    drain(h);
+  }
+  return code;
+}
+#define FDOCT_CATCH(h) catch (...) { return caught(h); }
+#define FDOCT_CATCH_RETURN(h, value) catch (...) { (void)caught(h); return value; }
+#define FDOCT_CATCH_VOID(h) catch (...) { (void)caught(h); }
+
 // ------------------------------------------------------------------ C ABI --
 extern "C" {
 
 #define FDOCT_STR_(x) #x
 #define FDOCT_STR(x) FDOCT_STR_(x)
-const char* fdoct_version(void) { return "fdoct-amd " FDOCT_STR(FDOCT_VERSION_MAJOR) "." FDOCT_STR(FDOCT_VERSION_MINOR) " (gfx950)"; }
+const char* fdoct_version(void) try { return "fdoct-amd " FDOCT_STR(FDOCT_VERSION_MAJOR) "." FDOCT_STR(FDOCT_VERSION_MINOR) " (gfx950)"; } FDOCT_CATCH_RETURN(nullptr, "")
 
 int fdoct_build_resample_table(int width, int multiplier, int numfftpoints, double lambdamin, double lambdamax,
-                               int32_t* nearestkindex, double* fractionalk) {
+                               int32_t* nearestkindex, double* fractionalk) try {
   if (width < 2 || multiplier < 1 || numfftpoints < 1 || !nearestkindex || !fractionalk) return FDOCT_ERR_INVALID;
   std::vector<int32_t> idx;
   std::vector<double> frac;
@@ -24,25 +65,25 @@ int fdoct_build_resample_table(int width, int multiplier, int numfftpoints, doub
   std::memcpy(nearestkindex, idx.data(), sizeof(int32_t) * idx.size());
   std::memcpy(fractionalk, frac.data(), sizeof(double) * frac.size());
   return FDOCT_OK;
-}
+} FDOCT_CATCH(nullptr)
 
-int fdoct_build_colormap_jet(unsigned char* bgr256) {
+int fdoct_build_colormap_jet(unsigned char* bgr256) try {
   if (!bgr256) return FDOCT_ERR_INVALID;
   build_opencv_jet(bgr256);
   return FDOCT_OK;
-}
+} FDOCT_CATCH(nullptr)
 
-int fdoct_build_window(int width, double* win) {
+int fdoct_build_window(int width, double* win) try {
   if (width < 2 || !win) return FDOCT_ERR_INVALID;
   std::vector<double> w;
   build_barthann(width, w);
   std::memcpy(win, w.data(), sizeof(double) * w.size());
   return FDOCT_OK;
-}
+} FDOCT_CATCH(nullptr)
 
-const char* fdoct_last_error(fdoct_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+const char* fdoct_last_error(fdoct_handle h) try { return h ? h->err.c_str() : g_create_error.c_str(); } FDOCT_CATCH_RETURN(h, "")
 
-int fdoct_create(const fdoct_config* cfg, fdoct_handle* out) {
+int fdoct_create(const fdoct_config* cfg, fdoct_handle* out) try {
   if (!cfg || !out) return fail(nullptr, FDOCT_ERR_INVALID, "null argument");
   *out = nullptr;
   if (cfg->struct_size != sizeof(fdoct_config)) return fail(nullptr, FDOCT_ERR_INVALID, "fdoct_config.struct_size mismatch");
@@ -58,8 +99,8 @@ int fdoct_create(const fdoct_config* cfg, fdoct_handle* out) {
     return fail(nullptr, FDOCT_ERR_DEVICE, "no HIP device: this library has no CPU fallback");
   if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, FDOCT_ERR_INVALID, "device ordinal out of range");
 
-  fdoct_ctx* h = new (std::nothrow) fdoct_ctx();
-  if (!h) return fail(nullptr, FDOCT_ERR_NOMEM, "out of memory");
+  HandlePtr owned(new fdoct_ctx(), fdoct_destroy);  // a half-built handle is destroyed on every early return
+  fdoct_ctx* h = owned.get();
   h->cfg = *cfg;
   h->W = cfg->width;
   h->H = cfg->height;
@@ -72,28 +113,23 @@ int fdoct_create(const fdoct_config* cfg, fdoct_handle* out) {
     h->A = 1;
   }
   h->device = cfg->device;
-  auto bail = [&](int code, const std::string& m) {
-    g_create_error = m;
-    fdoct_destroy(h);
-    return code;
-  };
   DeviceScope scope(h->device);  // the caller's current device is restored on every return path
-  if (scope.err != hipSuccess) return bail(FDOCT_ERR_DEVICE, "hipSetDevice failed");
+  if (scope.err != hipSuccess) return fail(nullptr, FDOCT_ERR_DEVICE, "hipSetDevice failed");
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) return bail(FDOCT_ERR_DEVICE, "hipGetDeviceProperties failed");
+  if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) return fail(nullptr, FDOCT_ERR_DEVICE, "hipGetDeviceProperties failed");
   h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
-    return bail(FDOCT_ERR_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    return fail(nullptr, FDOCT_ERR_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
   if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess)
-    return bail(FDOCT_ERR_DEVICE, "hipStreamCreate failed");
+    return fail(nullptr, FDOCT_ERR_DEVICE, "hipStreamCreate failed");
   h->stream = h->own_stream;
   for (auto& ev : h->ev)
-    if (hipEventCreate(&ev) != hipSuccess) return bail(FDOCT_ERR_DEVICE, "hipEventCreate failed");
+    if (hipEventCreate(&ev) != hipSuccess) return fail(nullptr, FDOCT_ERR_DEVICE, "hipEventCreate failed");
 
   build_resample_table(h->W, h->M, h->N, cfg->lambdamin, cfg->lambdamax, h->idx, h->frac);
   build_barthann(h->W, h->win);
   int rc = select_plan(h);
-  if (rc) return bail(rc, h->err);
+  if (rc) return fail(nullptr, rc, h->err);
   builtin_jet(h->lut);
   if (const char* e = std::getenv("FDOCT_NO_TRO")) h->tro_enabled = std::atoi(e) == 0;
   if (const char* e = std::getenv("FDOCT_JIT")) h->jit = std::atoi(e) != 0;
@@ -102,67 +138,51 @@ int fdoct_create(const fdoct_config* cfg, fdoct_handle* out) {
     const long long mb = std::atoll(e);
     h->tr_chunk_bytes = mb > 0 ? (size_t)mb << 20 : ~(size_t)0 >> 1;
   }
-  *out = h;
+  *out = owned.release();
   return FDOCT_OK;
-}
+} FDOCT_CATCH(nullptr)
 
-int fdoct_destroy(fdoct_handle h) {
+int fdoct_destroy(fdoct_handle h) try {
   if (!h) return FDOCT_OK;
   DeviceScope scope(h->device);
   if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
   if (h->stream && h->stream != h->own_stream) (void)hipStreamSynchronize(h->stream);  // work we enqueued on the caller's stream
   if (h->s_in) (void)hipStreamSynchronize(h->s_in);
   if (h->s_out) (void)hipStreamSynchronize(h->s_out);
-  void* ptrs[] = {h->d_ib, h->d_ib2d, h->d_ib2d_f, h->d_il, h->d_il2d, h->d_il2d_f, h->d_il_p, h->d_il16, h->d_il16_2d, h->d_yp, h->d_yd, h->d_yp_lo, h->d_yd_lo, h->d_win, h->d_g, h->d_gidx, h->d_tw, h->d_utw,
-                  h->d_phase, h->d_minmax, h->ws_in, h->ws_f32, h->ws_f32_lo, h->ws_mov_lo, h->ws_out0, h->ws_out1, h->ws_tr, h->ws_ylin,
-                  h->d_win_g, h->d_win_lo_g, h->d_g_g, h->d_idx_g, h->d_wave_gidx, h->d_wave_tw, h->d_blu_chirp, h->d_blu_bhat, h->d_twg_blu, h->d_twg_n, h->d_twg_nh, h->d_twg_w, h->d_twg_mw, h->d_twg_wh, h->d_twg_mwh, h->ws_mov, h->ws_front, h->ws_med, h->ws_raw, h->ws_sim,
-                  h->d_lut, h->d_disp_part, h->ws_disp_in, h->ws_disp_in2, h->ws_disp_out, h->d_gen_tickets,
-                  h->gzf.d_tw, h->gzf.d_chirp, h->gzf.d_bhat, h->gzi.d_tw, h->gzi.d_chirp, h->gzi.d_bhat};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)h->ws_big_y, (void*)h->ws_big_a, (void*)h->ws_big_b})
-    if (p) (void)hipFree(p);
-  big_plans_free(h);
-  if (h->d_tro_fault) (void)hipHostFree(h->d_tro_fault);
+  h->copy_pool.reset();  // (its threads stop before anything else goes)
   for (auto& ev : h->ev)
     if (ev) (void)hipEventDestroy(ev);
-  for (int b = 0; b < 2; b++) {
+  for (int b = 0; b < 2; b++)
     for (hipEvent_t e : {h->pe_in[b], h->pe_k[b], h->pe_out[b]})
       if (e) (void)hipEventDestroy(e);
-    for (void* p : {h->pl_in[b], (void*)h->pl_mag[b], (void*)h->pl_db[b]})
-      if (p) (void)hipFree(p);
-    for (void* p : {h->pin_in[b], (void*)h->pin_mag[b], (void*)h->pin_db[b]})
-      if (p) (void)hipHostFree(p);
-  }
-  delete h->copy_pool;
   if (h->s_in) (void)hipStreamDestroy(h->s_in);
   if (h->s_out) (void)hipStreamDestroy(h->s_out);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
+  delete h;  // the buffers go last, with the handle
   return FDOCT_OK;
-}
+} FDOCT_CATCH(nullptr)
 
-int fdoct_set_stream(fdoct_handle h, void* hip_stream) {
+int fdoct_set_stream(fdoct_handle h, void* hip_stream) try {
   if (!h) return FDOCT_ERR_INVALID;
   h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_background(fdoct_handle h, const void* data, fdoct_dtype dtype, int rows, size_t pitch_bytes) {
+int fdoct_set_background(fdoct_handle h, const void* data, fdoct_dtype dtype, int rows, size_t pitch_bytes) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!data) return fail(h, FDOCT_ERR_INVALID, "background data is null");
   return copy_ref_frame(h, h->yb, data, dtype, rows, pitch_bytes);
-}
-int fdoct_set_pi_frame(fdoct_handle h, const void* data, fdoct_dtype dtype, int rows, size_t pitch_bytes) {
+} FDOCT_CATCH(h)
+int fdoct_set_pi_frame(fdoct_handle h, const void* data, fdoct_dtype dtype, int rows, size_t pitch_bytes) try {
   if (!h) return FDOCT_ERR_INVALID;
   return copy_ref_frame(h, h->yp, data, dtype, rows, pitch_bytes);
-}
-int fdoct_set_dark(fdoct_handle h, const void* data, fdoct_dtype dtype, int rows, size_t pitch_bytes) {
+} FDOCT_CATCH(h)
+int fdoct_set_dark(fdoct_handle h, const void* data, fdoct_dtype dtype, int rows, size_t pitch_bytes) try {
   if (!h) return FDOCT_ERR_INVALID;
   return copy_ref_frame(h, h->yd, data, dtype, rows, pitch_bytes);
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_window(fdoct_handle h, const double* win, int n) {
+int fdoct_set_window(fdoct_handle h, const double* win, int n) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!win) {
     build_barthann(h->W, h->win);
@@ -175,9 +195,9 @@ int fdoct_set_window(fdoct_handle h, const double* win, int n) {
   }
   h->dirty = true;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_resample_table(fdoct_handle h, const int32_t* nearestkindex, const double* fractionalk, int n) {
+int fdoct_set_resample_table(fdoct_handle h, const int32_t* nearestkindex, const double* fractionalk, int n) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!nearestkindex || !fractionalk || n != h->N) return fail(h, FDOCT_ERR_INVALID, "table length must equal numfftpoints");
   for (int i = 0; i < n; i++)
@@ -188,9 +208,9 @@ int fdoct_set_resample_table(fdoct_handle h, const int32_t* nearestkindex, const
   h->custom_table = true;
   h->dirty = true;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_lambda_range(fdoct_handle h, double lambdamin, double lambdamax) {
+int fdoct_set_lambda_range(fdoct_handle h, double lambdamin, double lambdamax) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!(lambdamax > lambdamin) || !(lambdamin > 0)) return fail(h, FDOCT_ERR_INVALID, "lambda range");
   h->cfg.lambdamin = lambdamin;
@@ -199,9 +219,9 @@ int fdoct_set_lambda_range(fdoct_handle h, double lambdamin, double lambdamax) {
   h->custom_table = false;
   h->dirty = true;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_dispersion_phase(fdoct_handle h, const float* cos_sin_pairs, int n) {
+int fdoct_set_dispersion_phase(fdoct_handle h, const float* cos_sin_pairs, int n) try {
   if (!h) return FDOCT_ERR_INVALID;
   std::vector<float> old = h->phase;
   if (!cos_sin_pairs) {
@@ -219,22 +239,22 @@ int fdoct_set_dispersion_phase(fdoct_handle h, const float* cos_sin_pairs, int n
     h->err = msg;
   }
   return rc;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_get_resample_table(fdoct_handle h, int32_t* nearestkindex, double* fractionalk, int n) {
+int fdoct_get_resample_table(fdoct_handle h, int32_t* nearestkindex, double* fractionalk, int n) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (n != h->N) return fail(h, FDOCT_ERR_INVALID, "table length must equal numfftpoints");
   if (nearestkindex) std::memcpy(nearestkindex, h->idx.data(), sizeof(int32_t) * n);
   if (fractionalk) std::memcpy(fractionalk, h->frac.data(), sizeof(double) * n);
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_get_window(fdoct_handle h, double* win, int n) {
+int fdoct_get_window(fdoct_handle h, double* win, int n) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!win || n != (int)h->win.size()) return fail(h, FDOCT_ERR_INVALID, "window length must equal width");
   std::memcpy(win, h->win.data(), sizeof(double) * n);
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
 // The sim variant with averages = S > 1 (sim:936-947): of every S frames the reference keeps the LAST one's magnitudes (copyTo,
 // no accumulate, no division).  Gathers those frames -- frame g S + S - 1 for every group g -- into a packed device buffer
@@ -255,7 +275,7 @@ static int sim_last_frames(fdoct_ctx* h, const void** frames, fdoct_memspace* sp
   const int G = *nframes / S;
   DEVICE_SCOPE(h);
   int rc;
-  if ((rc = dev_reserve(h, &h->ws_sim, &h->ws_sim_cap, frame_bytes * (size_t)G))) return rc;
+  if ((rc = h->ws_sim.reserve(h, frame_bytes * (size_t)G))) return rc;
   HIP_TRY(h, hipMemcpy2DAsync(h->ws_sim, frame_bytes, static_cast<const unsigned char*>(*frames) + (size_t)(S - 1) * frame_bytes, (size_t)S * frame_bytes,
                               frame_bytes, (size_t)G, *space == FDOCT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
   *frames = h->ws_sim;
@@ -265,19 +285,19 @@ static int sim_last_frames(fdoct_ctx* h, const void** frames, fdoct_memspace* sp
 }
 
 int fdoct_process_async(fdoct_handle h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes,
-                        float* d_out_bscan, float* d_out_db, fdoct_layout layout) {
+                        float* d_out_bscan, float* d_out_db, fdoct_layout layout) try {
   if (!h) return FDOCT_ERR_INVALID;
   fdoct_memspace space = FDOCT_MEM_DEVICE;
   if (int rc = sim_last_frames(h, &d_frames, &space, dtype, &nframes, pitch_bytes)) return rc;
   h->record_now = h->async_timing;
   return enqueue(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_timing(fdoct_handle h, int on) {
+int fdoct_set_timing(fdoct_handle h, int on) try {
   if (!h) return FDOCT_ERR_INVALID;
   h->async_timing = on != 0;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
 // Did a wave of a transposed-store launch give up waiting (FusedArgs::tr_fault)?  The word lives in pinned host memory, so
 // this is a plain read: after a synchronisation point it is final for the work synchronised on, anywhere else (the next
@@ -293,12 +313,12 @@ static int check_tro_fault(fdoct_ctx* h) {
   return FDOCT_OK;
 }
 
-int fdoct_synchronize(fdoct_handle h) {
+int fdoct_synchronize(fdoct_handle h) try {
   if (!h) return FDOCT_ERR_INVALID;
   DEVICE_SCOPE(h);
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return check_tro_fault(h);
-}
+} FDOCT_CATCH(h)
 
 // Host buffers in, host buffers out, more than one chunk of work: the batch is cut into chunks of whole averaging
 // groups and pipelined over three streams -- chunk c+1 uploads while chunk c computes and chunk c-1 downloads (the
@@ -315,11 +335,7 @@ static int process_pipelined(fdoct_ctx* h, const unsigned char* frames, fdoct_dt
                              int frames_per_chunk, size_t frame_stride) {
   const int rc = process_pipelined_impl(h, frames, dtype, nframes, src_pitch, row_bytes, rows_per_frame, out_bscan, out_db, layout,
                                         frames_per_chunk, frame_stride);
-  if (rc != FDOCT_OK) {  // leave nothing in flight that still points at the caller's buffers or the chunk slots
-    if (h->s_in) (void)hipStreamSynchronize(h->s_in);
-    (void)hipStreamSynchronize(h->stream);
-    if (h->s_out) (void)hipStreamSynchronize(h->s_out);
-  }
+  if (rc != FDOCT_OK) drain(h);
   return rc;
 }
 
@@ -362,8 +378,8 @@ static int copy_thread_count(const fdoct_ctx* h) {  // 0: pageable buffers are n
 static fdoct_impl::HostCopyPool* copy_pool(fdoct_ctx* h) {
   const int n = copy_thread_count(h);
   if (!n) return nullptr;
-  if (!h->copy_pool) h->copy_pool = new (std::nothrow) fdoct_impl::HostCopyPool(n);
-  return h->copy_pool;
+  if (!h->copy_pool) h->copy_pool.reset(new (std::nothrow) fdoct_impl::HostCopyPool(n));
+  return h->copy_pool.get();
 }
 
 static int process_pipelined_impl(fdoct_ctx* h, const unsigned char* frames, fdoct_dtype dtype, int nframes, size_t src_pitch,
@@ -409,9 +425,9 @@ static int process_pipelined_impl(fdoct_ctx* h, const unsigned char* frames, fdo
     const size_t in0 = packed * (size_t)nf0 * (size_t)rows_per_frame, out0 = (size_t)(nf0 / h->A) * out_per_group * 4;
     const std::string err_before = h->err;
     for (int b = 0; b < 2; b++) {
-      if (stage_in && host_reserve(h, &h->pin_in[b], &h->pin_in_cap[b], in0)) stage_in = false;
-      if (stage_mag && host_reserve(h, &h->pin_mag[b], &h->pin_mag_cap[b], out0)) stage_mag = false;
-      if (stage_db && host_reserve(h, &h->pin_db[b], &h->pin_db_cap[b], out0)) stage_db = false;
+      if (stage_in && h->pin_in[b].reserve(h, in0)) stage_in = false;
+      if (stage_mag && h->pin_mag[b].reserve(h, out0)) stage_mag = false;
+      if (stage_db && h->pin_db[b].reserve(h, out0)) stage_db = false;
     }
     h->err = err_before;
   }
@@ -421,9 +437,9 @@ static int process_pipelined_impl(fdoct_ctx* h, const unsigned char* frames, fdo
     const int nf = std::min(frames_per_chunk, nframes - f0);
     const size_t in_rows = (size_t)nf * rows_per_frame;
     const size_t out_elems = (size_t)(nf / h->A) * out_per_group;
-    if ((rc = dev_reserve(h, &h->pl_in[b], &h->pl_in_cap[b], packed * in_rows))) return rc;
-    if (out_bscan && (rc = dev_reserve(h, &h->pl_mag[b], &h->pl_mag_cap[b], out_elems * 4))) return rc;
-    if (out_db && (rc = dev_reserve(h, &h->pl_db[b], &h->pl_db_cap[b], out_elems * 4))) return rc;
+    if ((rc = h->pl_in[b].reserve(h, packed * in_rows))) return rc;
+    if (out_bscan && (rc = h->pl_mag[b].reserve(h, out_elems * 4))) return rc;
+    if (out_db && (rc = h->pl_db[b].reserve(h, out_elems * 4))) return rc;
     const unsigned char* src = frames + (size_t)f0 * frame_stride;
     // a packed batch moves as one 2-D copy of the chunk's rows, a strided one frame by frame
     const int pieces = packed_batch ? 1 : nf;
@@ -470,35 +486,34 @@ static int process_pipelined_impl(fdoct_ctx* h, const unsigned char* frames, fdo
   return FDOCT_OK;
 }
 
-int fdoct_get_host_staging(fdoct_handle h) {
+int fdoct_get_host_staging(fdoct_handle h) try {
   if (!h) return FDOCT_ERR_INVALID;
   return copy_thread_count(h);
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_host_staging(fdoct_handle h, int threads) {
+int fdoct_set_host_staging(fdoct_handle h, int threads) try {
   if (!h) return FDOCT_ERR_INVALID;
   const int want = threads < 0 ? -1 : std::min(threads, 64);
   if (want != h->host_staging) {  // the pool is sized when it starts: a new count means a new pool (no batch is in flight here)
-    delete h->copy_pool;
-    h->copy_pool = nullptr;
+    h->copy_pool.reset();
   }
   h->host_staging = want;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-void* fdoct_host_alloc(size_t bytes) {
+void* fdoct_host_alloc(size_t bytes) try {
   void* p = nullptr;
   if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
   return p;
-}
+} FDOCT_CATCH_RETURN(nullptr, nullptr)
 
-void fdoct_host_free(void* p) {
+void fdoct_host_free(void* p) try {
   if (p) (void)hipHostFree(p);
-}
+} FDOCT_CATCH_VOID(nullptr)
 
 int fdoct_process(fdoct_handle h, const void* frames, fdoct_dtype dtype, fdoct_memspace space, int nframes,
                   size_t pitch_bytes, float* out_bscan, float* out_db, fdoct_memspace out_space,
-                  fdoct_layout layout) {
+                  fdoct_layout layout) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!frames || nframes <= 0) return fail(h, FDOCT_ERR_INVALID, "no frames");
   const size_t es = dtype_size(dtype);
@@ -558,7 +573,7 @@ int fdoct_process(fdoct_handle h, const void* frames, fdoct_dtype dtype, fdoct_m
   if (space == FDOCT_MEM_HOST) {
     // stage into an aligned, packed device buffer (PCIe-inclusive path)
     const size_t packed = (es * row_samples + 15) & ~(size_t)15;
-    if ((rc = dev_reserve(h, &h->ws_in, &h->ws_in_cap, packed * (size_t)in_rows))) return rc;
+    if ((rc = h->ws_in.reserve(h, packed * (size_t)in_rows))) return rc;
     HIP_TRY(h, hipMemcpy2DAsync(h->ws_in, packed, frames, d_pitch, es * row_samples, (size_t)in_rows, hipMemcpyHostToDevice,
                                 h->stream));
     d_frames = h->ws_in;
@@ -568,11 +583,11 @@ int fdoct_process(fdoct_handle h, const void* frames, fdoct_dtype dtype, fdoct_m
   float* d_db = out_db;
   if (out_space == FDOCT_MEM_HOST) {
     if (out_bscan) {
-      if ((rc = dev_reserve(h, &h->ws_out0, &h->ws_out0_cap, out_elems * 4))) return rc;
+      if ((rc = h->ws_out0.reserve(h, out_elems * 4))) return rc;
       d_mag = h->ws_out0;
     }
     if (out_db) {
-      if ((rc = dev_reserve(h, &h->ws_out1, &h->ws_out1_cap, out_elems * 4))) return rc;
+      if ((rc = h->ws_out1.reserve(h, out_elems * 4))) return rc;
       d_db = h->ws_out1;
     }
   }
@@ -584,9 +599,9 @@ int fdoct_process(fdoct_handle h, const void* frames, fdoct_dtype dtype, fdoct_m
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return check_tro_fault(h);
-}
+} FDOCT_CATCH(h)
 
-int fdoct_get_timing(fdoct_handle h, fdoct_timing* t) {
+int fdoct_get_timing(fdoct_handle h, fdoct_timing* t) try {
   if (!h || !t) return FDOCT_ERR_INVALID;
   if (h->timing_pending) {
     DEVICE_SCOPE(h);
@@ -610,18 +625,18 @@ int fdoct_get_timing(fdoct_handle h, fdoct_timing* t) {
   }
   *t = h->timing;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_launch(fdoct_handle h, int threads_per_block, int blocks) {
+int fdoct_set_launch(fdoct_handle h, int threads_per_block, int blocks) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (threads_per_block < 0 || threads_per_block % 64 || threads_per_block > FDOCT_MAX_BLOCK || blocks < 0)
     return fail(h, FDOCT_ERR_INVALID, "threads_per_block must be a multiple of 64 up to the build's block limit");
   h->block_override = threads_per_block;
   h->grid_override = blocks;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_plan(fdoct_handle h, int plan_id, int force_general_kernel) {
+int fdoct_set_plan(fdoct_handle h, int plan_id, int force_general_kernel) try {
   if (!h) return FDOCT_ERR_INVALID;
   FusedPlan q{};
   if (plan_id >= 0 && !fused_plan_get(plan_id, &q)) return fail(h, FDOCT_ERR_INVALID, "unknown plan id");
@@ -630,9 +645,9 @@ int fdoct_set_plan(fdoct_handle h, int plan_id, int force_general_kernel) {
   h->force_general = force_general_kernel != 0;
   h->dirty = true;
   return select_plan(h);
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_frontend(fdoct_handle h, int mediann, int binx, int biny) {
+int fdoct_set_frontend(fdoct_handle h, int mediann, int binx, int biny) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (binx < 1 || biny < 1 || (mediann != 0 && mediann != 3 && mediann != 5 && mediann != 7))
     return fail(h, FDOCT_ERR_INVALID, "mediann must be 0/3/5/7 and the bin factors >= 1");
@@ -640,10 +655,10 @@ int fdoct_set_frontend(fdoct_handle h, int mediann, int binx, int biny) {
   h->fe_binx = binx;
   h->fe_biny = biny;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
 int fdoct_frontend(fdoct_handle h, const void* raw, fdoct_dtype dtype, int nframes, int raw_w, int raw_h, size_t pitch_bytes,
-                   int mediann, int binx, int biny, void* out) {
+                   int mediann, int binx, int biny, void* out) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!raw || !out || nframes <= 0 || raw_w <= 0 || raw_h <= 0) return fail(h, FDOCT_ERR_INVALID, "fdoct_frontend: bad arguments");
   if (dtype != FDOCT_U8 && dtype != FDOCT_U16)
@@ -655,7 +670,7 @@ int fdoct_frontend(fdoct_handle h, const void* raw, fdoct_dtype dtype, int nfram
   DEVICE_SCOPE(h);
   int rc;
   const size_t packed = (es * raw_w + 15) & ~(size_t)15;
-  if ((rc = dev_reserve(h, &h->ws_raw, &h->ws_raw_cap, packed * (size_t)raw_h * nframes))) return rc;
+  if ((rc = h->ws_raw.reserve(h, packed * (size_t)raw_h * nframes))) return rc;
   HIP_TRY(h, hipMemcpy2DAsync(h->ws_raw, packed, raw, pitch_bytes, es * raw_w, (size_t)raw_h * nframes, hipMemcpyHostToDevice,
                               h->stream));
   void* fo = nullptr;
@@ -665,9 +680,9 @@ int fdoct_frontend(fdoct_handle h, const void* raw, fdoct_dtype dtype, int nfram
   HIP_TRY(h, hipMemcpy2DAsync(out, es * ow, fo, fp, es * ow, (size_t)oh * nframes, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_colormap(fdoct_handle h, const unsigned char* bgr256) {
+int fdoct_set_colormap(fdoct_handle h, const unsigned char* bgr256) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (bgr256)
     std::memcpy(h->lut, bgr256, 768);
@@ -675,17 +690,17 @@ int fdoct_set_colormap(fdoct_handle h, const unsigned char* bgr256) {
     builtin_jet(h->lut);
   h->lut_dirty = true;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_get_colormap(fdoct_handle h, unsigned char* bgr256) {
+int fdoct_get_colormap(fdoct_handle h, unsigned char* bgr256) try {
   if (!h || !bgr256) return FDOCT_ERR_INVALID;
   std::memcpy(bgr256, h->lut, 768);
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
 int fdoct_display(fdoct_handle h, const float* bscandb, fdoct_memspace in_mem, int nbscans, int rows, int cols,
                   double bscanthreshold, int clampupper, unsigned char* out_gray, unsigned char* out_bgr,
-                  fdoct_memspace out_mem) {
+                  fdoct_memspace out_mem) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!bscandb || nbscans <= 0 || rows <= 0 || cols <= 0) return fail(h, FDOCT_ERR_INVALID, "fdoct_display: bad arguments");
   if (!out_gray && !out_bgr) return fail(h, FDOCT_ERR_INVALID, "fdoct_display: no output requested");
@@ -696,22 +711,22 @@ int fdoct_display(fdoct_handle h, const float* bscandb, fdoct_memspace in_mem, i
   const size_t total = (size_t)count * nbscans;
   const float* d_in = bscandb;
   if (in_mem == FDOCT_MEM_HOST) {
-    if ((rc = dev_reserve(h, &h->ws_disp_in, &h->ws_disp_in_cap, total * sizeof(float)))) return rc;
+    if ((rc = h->ws_disp_in.reserve(h, total * sizeof(float)))) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->ws_disp_in, bscandb, total * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    d_in = static_cast<const float*>(h->ws_disp_in);
+    d_in = h->ws_disp_in;
   }
   if (h->lut_dirty || !h->d_lut) {
-    if (!h->d_lut && (rc = dev_alloc(h, &h->d_lut, 768))) return rc;
+    if (!h->d_lut && (rc = h->d_lut.assign(h, 768))) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->d_lut, h->lut, 768, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // h->lut may change right after we return
     h->lut_dirty = false;
   }
-  if ((rc = dev_reserve(h, &h->d_disp_part, &h->disp_part_cap, (size_t)nbscans * display_parts(count) * 2 * sizeof(double))))
+  if ((rc = h->d_disp_part.reserve(h, (size_t)nbscans * display_parts(count) * 2 * sizeof(double))))
     return rc;
   unsigned char *d_gray = out_gray, *d_bgr = out_bgr;
   if (out_mem == FDOCT_MEM_HOST) {
     const size_t need = (out_gray ? total : 0) + (out_bgr ? 3 * total : 0);
-    if ((rc = dev_reserve(h, &h->ws_disp_out, &h->ws_disp_out_cap, need))) return rc;
+    if ((rc = h->ws_disp_out.reserve(h, need))) return rc;
     unsigned char* w = static_cast<unsigned char*>(h->ws_disp_out);
     d_bgr = out_bgr ? w : nullptr;  // colour first: its 12-byte groups stay 4-byte aligned
     d_gray = out_gray ? w + (out_bgr ? 3 * total : 0) : nullptr;
@@ -724,10 +739,10 @@ int fdoct_display(fdoct_handle h, const float* bscandb, fdoct_memspace in_mem, i
   }
   if (in_mem == FDOCT_MEM_HOST || out_mem == FDOCT_MEM_HOST) HIP_TRY(h, hipStreamSynchronize(h->stream));
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
 int fdoct_lockin_db(fdoct_handle h, const float* bscan, const float* jscan, fdoct_memspace mem, int nbscans, size_t count,
-                    float* out_db) {
+                    float* out_db) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!bscan || !jscan || !out_db || nbscans <= 0 || count == 0) return fail(h, FDOCT_ERR_INVALID, "fdoct_lockin_db: bad arguments");
   DEVICE_SCOPE(h);
@@ -737,19 +752,19 @@ int fdoct_lockin_db(fdoct_handle h, const float* bscan, const float* jscan, fdoc
     return FDOCT_OK;
   }
   int rc;
-  if ((rc = dev_reserve(h, &h->ws_disp_in, &h->ws_disp_in_cap, total * sizeof(float)))) return rc;
-  if ((rc = dev_reserve(h, &h->ws_disp_in2, &h->ws_disp_in2_cap, count * sizeof(float)))) return rc;
-  if ((rc = dev_reserve(h, &h->ws_disp_out, &h->ws_disp_out_cap, total * sizeof(float)))) return rc;
+  if ((rc = h->ws_disp_in.reserve(h, total * sizeof(float)))) return rc;
+  if ((rc = h->ws_disp_in2.reserve(h, count * sizeof(float)))) return rc;
+  if ((rc = h->ws_disp_out.reserve(h, total * sizeof(float)))) return rc;
   HIP_TRY(h, hipMemcpyAsync(h->ws_disp_in, bscan, total * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(h->ws_disp_in2, jscan, count * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, launch_lockin_db(static_cast<const float*>(h->ws_disp_in), static_cast<const float*>(h->ws_disp_in2), (long long)total,
-                              (long long)count, static_cast<float*>(h->ws_disp_out), h->stream));
+  HIP_TRY(h, launch_lockin_db(h->ws_disp_in, h->ws_disp_in2, (long long)total, (long long)count,
+                              reinterpret_cast<float*>(static_cast<unsigned char*>(h->ws_disp_out)), h->stream));
   HIP_TRY(h, hipMemcpyAsync(out_db, h->ws_disp_out, total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_averages(fdoct_handle h, int averages) {
+int fdoct_set_averages(fdoct_handle h, int averages) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (averages < 1) return fail(h, FDOCT_ERR_INVALID, "averages must be >= 1");
   if (h->cfg.variant == FDOCT_VARIANT_SIM)
@@ -758,21 +773,21 @@ int fdoct_set_averages(fdoct_handle h, int averages) {
     h->A = averages;  // a launch parameter only: no table depends on it
   h->cfg.averages = averages;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_bandpass(fdoct_handle h, int on) {
+int fdoct_set_bandpass(fdoct_handle h, int on) try {
   if (!h) return FDOCT_ERR_INVALID;
   h->bandpass = on != 0;  // takes effect inside the zero-pad stage (increasefftpointsmultiplier > 1), as in the reference
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_staged(fdoct_handle h, int on) {
+int fdoct_set_staged(fdoct_handle h, int on) try {
   if (!h) return FDOCT_ERR_INVALID;
   h->staged = on != 0;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_prepare(fdoct_handle h, fdoct_dtype dtype, fdoct_layout layout) {
+int fdoct_prepare(fdoct_handle h, fdoct_dtype dtype, fdoct_layout layout) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!h->yb.rows) return fail(h, FDOCT_ERR_STATE, "no background set (fdoct_set_background)");
   const size_t es = dtype_size(dtype);
@@ -783,26 +798,26 @@ int fdoct_prepare(fdoct_handle h, fdoct_dtype dtype, fdoct_layout layout) {
   const int rc = choose_route(h, dtype, 0, es * (size_t)h->W * h->fe_binx, 0, 0, layout, h->A, &r);
   if (rc) return rc;
   return r.family;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_precise_division(fdoct_handle h, int on) {
+int fdoct_set_precise_division(fdoct_handle h, int on) try {
   if (!h) return FDOCT_ERR_INVALID;
   h->precise_div = on != 0;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_set_jit(fdoct_handle h, int on) {
+int fdoct_set_jit(fdoct_handle h, int on) try {
   if (!h) return FDOCT_ERR_INVALID;
   h->jit = on != 0;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_last_kernel(fdoct_handle h) { return h ? h->last_kernel : FDOCT_KERNEL_NONE; }
+int fdoct_last_kernel(fdoct_handle h) try { return h ? h->last_kernel : FDOCT_KERNEL_NONE; } FDOCT_CATCH(h)
 
-const char* fdoct_jit_note(fdoct_handle h) { return h ? h->jit_note.c_str() : ""; }
+const char* fdoct_jit_note(fdoct_handle h) try { return h ? h->jit_note.c_str() : ""; } FDOCT_CATCH_RETURN(h, "")
 
 long long fdoct_jit_compile_check(int width, int multiplier, int numfftpoints, int numdisplaypoints, fdoct_dtype dtype, const char* gcn_arch,
-                                  char* why, int why_len) {
+                                  char* why, int why_len) try {
   std::string reason;
   long long n = -1;
   const int kdt = kernel_dtype(dtype);
@@ -818,15 +833,15 @@ long long fdoct_jit_compile_check(int width, int multiplier, int numfftpoints, i
   }
   if (why && why_len > 0) std::snprintf(why, (size_t)why_len, "%s", reason.c_str());
   return n;
-}
+} FDOCT_CATCH_RETURN(nullptr, -1)
 
-int fdoct_device_count(void) {
+int fdoct_device_count(void) try {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess) return 0;
   return ndev > 0 ? ndev : 0;
-}
+} FDOCT_CATCH(nullptr)
 
-int fdoct_shard_frames(int nframes_total, int averages, int part, int nparts, int* first, int* count) {
+int fdoct_shard_frames(int nframes_total, int averages, int part, int nparts, int* first, int* count) try {
   if (nframes_total < 0 || averages < 1 || nparts < 1 || part < 0 || part >= nparts || !first || !count) return FDOCT_ERR_INVALID;
   const int groups = nframes_total / averages, base = groups / nparts, extra = groups % nparts;
   const int g0 = part * base + (part < extra ? part : extra);
@@ -834,9 +849,9 @@ int fdoct_shard_frames(int nframes_total, int averages, int part, int nparts, in
   *first = g0 * averages;
   *count = (g1 - g0) * averages;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(nullptr)
 
-int fdoct_clone_to_device(fdoct_handle h, int device, fdoct_handle* out) {
+int fdoct_clone_to_device(fdoct_handle h, int device, fdoct_handle* out) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!out) return fail(h, FDOCT_ERR_INVALID, "fdoct_clone_to_device: null output");
   *out = nullptr;
@@ -846,6 +861,7 @@ int fdoct_clone_to_device(fdoct_handle h, int device, fdoct_handle* out) {
   fdoct_handle c = nullptr;
   int rc = fdoct_create(&cfg, &c);
   if (rc) return fail(h, rc, std::string("fdoct_clone_to_device: ") + fdoct_last_error(nullptr));
+  HandlePtr owned(c, fdoct_destroy);  // destroyed on every return but the last
   // constant state: the same blob the multi-process set-up broadcasts (host memory; the device tables of the clone are
   // built on ITS device at the first call, like any handle's)
   size_t used = 0;
@@ -854,9 +870,7 @@ int fdoct_clone_to_device(fdoct_handle h, int device, fdoct_handle* out) {
   if (!rc) rc = fdoct_export_state(h, blob.data(), blob.size(), &used);
   if (!rc) rc = fdoct_import_state(c, blob.data(), blob.size());
   if (rc) {
-    const std::string msg = rc == FDOCT_ERR_INVALID ? c->err : h->err;
-    fdoct_destroy(c);
-    return fail(h, rc, "fdoct_clone_to_device: " + msg);
+    return fail(h, rc, "fdoct_clone_to_device: " + (rc == FDOCT_ERR_INVALID ? c->err : h->err));
   }
   // run-time settings
   c->fe_median = h->fe_median;
@@ -876,16 +890,12 @@ int fdoct_clone_to_device(fdoct_handle h, int device, fdoct_handle* out) {
   c->lut_dirty = true;
   c->dirty = true;
   rc = select_plan(c);
-  if (rc) {
-    const std::string msg = c->err;
-    fdoct_destroy(c);
-    return fail(h, rc, "fdoct_clone_to_device: " + msg);
-  }
-  *out = c;
+  if (rc) return fail(h, rc, "fdoct_clone_to_device: " + c->err);
+  *out = owned.release();
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
-int fdoct_get_ylin(fdoct_handle h, long long row0, int nrows, double* out) {
+int fdoct_get_ylin(fdoct_handle h, long long row0, int nrows, double* out) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!out || nrows <= 0 || row0 < 0) return fail(h, FDOCT_ERR_INVALID, "fdoct_get_ylin: bad arguments");
   if (!h->ylin_rows || !h->ws_ylin) return fail(h, FDOCT_ERR_STATE, "fdoct_get_ylin: the last run was not a staged one (fdoct_set_staged)");
@@ -910,7 +920,7 @@ int fdoct_get_ylin(fdoct_handle h, long long row0, int nrows, double* out) {
     }
   }
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
 // ---- state blob (format 2): 12 x int32 header {magic, version, W, H, N, M, yb_rows, yp_rows, yd_rows, nphase floats,
 // window length, flags (bit 0 custom window, bit 1 custom resample table)}, then yb, yp, yd, window, fractionalk as
@@ -925,7 +935,7 @@ static const size_t kStateHeader = 12 * sizeof(int32_t);
 // device buffers on the handle's stream, the other ranks import it.  librccl is looked up at run time (dlopen: a host that
 // never calls this does not need it); the communicator and its lifetime are the caller's.  A one-rank communicator is a plain
 // export / import round trip.
-int fdoct_broadcast_state_rccl(fdoct_handle h, void* nccl_comm, int root) {
+int fdoct_broadcast_state_rccl(fdoct_handle h, void* nccl_comm, int root) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!nccl_comm) return fail(h, FDOCT_ERR_INVALID, "fdoct_broadcast_state_rccl: null communicator");
   // (the entry points used, by their documented C signatures: ncclResult_t is an int with 0 = success, ncclUint8 = 1,
@@ -982,7 +992,7 @@ int fdoct_broadcast_state_rccl(fdoct_handle h, void* nccl_comm, int root) {
     if (!root_rc) {
       try {
         blob.resize(used);
-      } catch (...) {   // (no exception crosses the C ABI: the root takes part in the size broadcast with 0, every rank returns an error)
+      } catch (...) {   // (caught here, not at the boundary: the root still takes part in the size broadcast, with 0, and every rank returns an error)
         blob.clear();
         root_rc = fail(h, FDOCT_ERR_NOMEM, "fdoct_broadcast_state_rccl: no host memory for the state blob on the root");
       }
@@ -991,43 +1001,29 @@ int fdoct_broadcast_state_rccl(fdoct_handle h, void* nccl_comm, int root) {
     nbytes = root_rc ? 0 : used;
   }
   hipStream_t st = h->stream;
-  unsigned long long* d_n = nullptr;
-  unsigned char* d_chunk = nullptr;
-  auto cleanup = [&]() {
-    if (d_n) (void)hipFree(d_n);
-    if (d_chunk) (void)hipFree(d_chunk);
-  };
-  if (hipMalloc(reinterpret_cast<void**>(&d_n), sizeof nbytes) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_chunk), kChunk) != hipSuccess) {
-    cleanup();
+  DevBuf<unsigned long long> d_n;
+  DevBuf<unsigned char> d_chunk;
+  if (d_n.assign(h, 1) || d_chunk.assign(h, kChunk))
     return fail(h, FDOCT_ERR_NOMEM, "fdoct_broadcast_state_rccl: no device memory for the staging buffers (no collective was entered: abort the communicator)");
-  }
-  if (hipMemcpyAsync(d_n, &nbytes, sizeof nbytes, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    cleanup();
+  if (hipMemcpyAsync(d_n, &nbytes, sizeof nbytes, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return fail(h, FDOCT_ERR_DEVICE, "fdoct_broadcast_state_rccl: copy of the blob size failed (no collective was entered: abort the communicator)");
-  }
   // ---- collective 1: the size
-  if ((rc = nccl_try(nccl_broadcast(d_n, d_n, 1, /*ncclUint64*/ 5, root, nccl_comm, st), "ncclBroadcast (size)"))) {
-    cleanup();
-    return rc;
-  }
+  if ((rc = nccl_try(nccl_broadcast(d_n, d_n, 1, /*ncclUint64*/ 5, root, nccl_comm, st), "ncclBroadcast (size)"))) return rc;
   if (hipMemcpyAsync(&nbytes, d_n, sizeof nbytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
       nbytes > (1ull << 34)) {
-    cleanup();
     // (this rank cannot know how many chunk broadcasts follow, so it cannot stay in step with the others: include/fdoct.h
     // documents this exit next to the pre-collective ones)
     return fail(h, FDOCT_ERR_DEVICE, "fdoct_broadcast_state_rccl: the broadcast blob size could not be read back or is implausible (this rank leaves "
                                      "before the chunk broadcasts: abort the communicator)");
   }
-  if (nbytes == 0) {  // the root had nothing to send: every rank returns an error, nobody is left in a later broadcast
-    cleanup();
+  if (nbytes == 0)  // the root had nothing to send: every rank returns an error, nobody is left in a later broadcast
     return root_rc ? root_rc : fail(h, FDOCT_ERR_INVALID, "fdoct_broadcast_state_rccl: the root rank could not export its state");
-  }
   // ---- collectives 2 ...: the blob, chunk by chunk through the staging buffer.  A copy that fails from here on does not
   // take this rank out of the remaining broadcasts (the others would wait in them): the error is returned at the end.
   if (rank != root) {
     try {
       blob.resize(nbytes);
-    } catch (...) {
+    } catch (...) {   // (caught here, not at the boundary: a rank without host memory must still take part in the chunk broadcasts)
       blob.clear();   // (no host memory: keep taking part, report afterwards)
     }
   }
@@ -1036,10 +1032,8 @@ int fdoct_broadcast_state_rccl(fdoct_handle h, void* nccl_comm, int root) {
     const size_t n = (size_t)std::min<unsigned long long>(kChunk, nbytes - off);
     if (rank == root && hipMemcpyAsync(d_chunk, blob.data() + off, n, hipMemcpyHostToDevice, st) != hipSuccess && !late)
       late = fail(h, FDOCT_ERR_DEVICE, "fdoct_broadcast_state_rccl: upload of the blob failed");
-    if ((rc = nccl_try(nccl_broadcast(d_chunk, d_chunk, n, /*ncclUint8*/ 1, root, nccl_comm, st), "ncclBroadcast (blob)"))) {
-      cleanup();
+    if ((rc = nccl_try(nccl_broadcast(d_chunk, d_chunk, n, /*ncclUint8*/ 1, root, nccl_comm, st), "ncclBroadcast (blob)")))
       return rc;   // (the collective itself failed: the communicator is in error for every rank)
-    }
     if (rank != root && !blob.empty()) {
       if ((hipMemcpyAsync(blob.data() + off, d_chunk, n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) && !late)
         late = fail(h, FDOCT_ERR_DEVICE, "fdoct_broadcast_state_rccl: download of the blob failed");
@@ -1047,14 +1041,13 @@ int fdoct_broadcast_state_rccl(fdoct_handle h, void* nccl_comm, int root) {
       late = fail(h, FDOCT_ERR_DEVICE, "fdoct_broadcast_state_rccl: stream error during the blob broadcast");
     }
   }
-  cleanup();
   if (late) return late;
   if (blob.size() != nbytes) return fail(h, FDOCT_ERR_NOMEM, "fdoct_broadcast_state_rccl: no host memory for the blob");
   // (the root imports its own blob too: every rank ends in the state the blob describes, validated the same way)
   return fdoct_import_state(h, blob.data(), blob.size());
-}
+} FDOCT_CATCH(h)
 
-int fdoct_export_state(fdoct_handle h, void* buf, size_t cap, size_t* used) {
+int fdoct_export_state(fdoct_handle h, void* buf, size_t cap, size_t* used) try {
   if (!h || !used) return FDOCT_ERR_INVALID;
   const size_t need = kStateHeader + (h->yb.v.size() + h->yp.v.size() + h->yd.v.size() + h->win.size() + h->frac.size()) * 8 +
                       h->idx.size() * 4 + h->phase.size() * 4;
@@ -1078,10 +1071,10 @@ int fdoct_export_state(fdoct_handle h, void* buf, size_t cap, size_t* used) {
   put(h->idx.data(), h->idx.size() * 4);
   put(h->phase.data(), h->phase.size() * 4);
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
 // Everything is parsed and checked into temporaries first: a blob that fails any check leaves the handle untouched.
-int fdoct_import_state(fdoct_handle h, const void* buf, size_t len) {
+int fdoct_import_state(fdoct_handle h, const void* buf, size_t len) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!buf || len < kStateHeader) return fail(h, FDOCT_ERR_INVALID, "state blob too short");
   const unsigned char* p = static_cast<const unsigned char*>(buf);
@@ -1139,6 +1132,6 @@ int fdoct_import_state(fdoct_handle h, const void* buf, size_t len) {
   h->custom_table = (hdr[11] & 2) != 0;
   h->dirty = true;
   return FDOCT_OK;
-}
+} FDOCT_CATCH(h)
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -41,7 +42,53 @@ struct RefFrame {  // a caller-supplied reference frame (background / pi / dark)
   int rows = 0;  // 0 = unset, 1 = one spectrum for all rows, H = full frame
 };
 
+inline int fail(fdoct_ctx* h, int code, const std::string& msg);
+
+// Memory a handle owns: device memory (hipMalloc) or, Pinned, page-locked host memory (hipHostMalloc with the given flags).
+// Freed when the buffer dies; reads as the T* it holds, so that launch code fills its argument blocks from it directly.
+// Move-only (a BigPlan moves into the handle's map).
+template <typename T, bool Pinned>
+class Buffer {
+ public:
+  Buffer() = default;
+  explicit Buffer(unsigned flags) : flags_(flags) {}
+  Buffer(Buffer&& o) noexcept : p_(o.p_), bytes_(o.bytes_), flags_(o.flags_) { o.p_ = nullptr, o.bytes_ = 0; }
+  ~Buffer() { release(); }
+  operator T*() const { return p_; }
+
+  void release() {
+    if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+    p_ = nullptr;
+    bytes_ = 0;
+  }
+  // at least `bytes`, grown only (the old contents are not kept)
+  int reserve(fdoct_ctx* h, size_t bytes) {
+    if (bytes_ >= bytes && p_) return FDOCT_OK;
+    release();
+    void* q = nullptr;
+    const hipError_t e = Pinned ? hipHostMalloc(&q, bytes, flags_) : hipMalloc(&q, bytes);
+    if (e != hipSuccess) return fail(h, FDOCT_ERR_NOMEM, std::string(Pinned ? "hipHostMalloc: " : "hipMalloc: ") + hipGetErrorString(e));
+    p_ = static_cast<T*>(q);
+    bytes_ = bytes;
+    return FDOCT_OK;
+  }
+  // exactly `count` elements; 0 releases the buffer
+  int assign(fdoct_ctx* h, size_t count) {
+    release();
+    return count ? reserve(h, count * sizeof(T)) : FDOCT_OK;
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t bytes_ = 0;
+  unsigned flags_ = hipHostMallocDefault;
+};
+template <typename T> using DevBuf = Buffer<T, false>;
+template <typename T> using PinnedBuf = Buffer<T, true>;
+
 }  // namespace fdoct_impl
+using fdoct_impl::DevBuf;
+using fdoct_impl::PinnedBuf;
 using fdoct_impl::RefFrame;
 
 struct fdoct_ctx {
@@ -76,20 +123,20 @@ struct fdoct_ctx {
   struct GenericDftPlan {
     int n = 0, blu_m = 0;
     std::vector<int> rad;   // of n, or of blu_m
-    float2 *d_tw = nullptr, *d_chirp = nullptr, *d_bhat = nullptr;
+    DevBuf<float2> d_tw, d_chirp, d_bhat;
   };
-  unsigned* d_gen_tickets = nullptr;   // kGenTickets row counters of generic_kernel launches, used round-robin (one per launch in flight)
+  DevBuf<unsigned> d_gen_tickets;   // kGenTickets row counters of generic_kernel launches, used round-robin (one per launch in flight)
   unsigned gen_ticket_seq = 0;
   bool zp_full = false;
   int zn = 0;               // W + 2 floor((M W - W) / 2)
   GenericDftPlan gzf, gzi;  // the W-point and the zn-point +i transform
   int blu_m = 0;  // > 0: the final transform (length N or N/2) has a prime factor > 5 and runs as Bluestein's chirp-z of this power-of-two length
-  float2 *d_blu_chirp = nullptr, *d_blu_bhat = nullptr, *d_twg_blu = nullptr;
+  DevBuf<float2> d_blu_chirp, d_blu_bhat, d_twg_blu;
 
   // device state
-  float *d_ib = nullptr, *d_ib2d = nullptr, *d_ib2d_f = nullptr, *d_yp = nullptr, *d_yd = nullptr, *d_yp_lo = nullptr, *d_yd_lo = nullptr, *d_win = nullptr, *d_g = nullptr;
-  float *d_il = nullptr, *d_il2d = nullptr, *d_il2d_f = nullptr, *d_il_p = nullptr;  // d_il_p: d_il in the order of the fused kernels' LDS planes  // low words of the reciprocal background, laid out like d_ib / d_ib2d / d_ib2d_f
-  uint32_t *d_il16 = nullptr, *d_il16_2d = nullptr;  // the second word as the fast path reads it: il / ib * 2^38 as half-float pairs (fdoct_kernels.h: FDOCT_PREC16)
+  DevBuf<float> d_ib, d_ib2d, d_ib2d_f, d_yp, d_yd, d_yp_lo, d_yd_lo, d_win, d_g;
+  DevBuf<float> d_il, d_il2d, d_il2d_f, d_il_p;  // d_il_p: d_il in the order of the fused kernels' LDS planes  // low words of the reciprocal background, laid out like d_ib / d_ib2d / d_ib2d_f
+  DevBuf<uint32_t> d_il16, d_il16_2d;  // the second word as the fast path reads it: il / ib * 2^38 as half-float pairs (fdoct_kernels.h: FDOCT_PREC16)
   // fdoct_set_precise_division.  ON by default (round 5): main:1132 divides in double, and one f32 reciprocal leaves a fixed
   // pattern of 6e-8 of the DC level -- 8 x the tolerance on fringes of 1e-3 of it.  Off (or FDOCT_PRECISE_DIVISION=0) is the
   // opt-out for callers who know their fringes exceed ~1 % of the DC level.
@@ -98,20 +145,18 @@ struct fdoct_ctx {
   // is commented out) and what is emitted, undivided, is the last copy -- frame averages - 1 of every group.  The chain then
   // runs with A = 1 on those frames only (sim_last_frames gathers them); sim_group is the group length the caller counts in.
   int sim_group = 1;
-  void* ws_sim = nullptr;
-  size_t ws_sim_cap = 0;
-  uint32_t* d_gidx = nullptr;
-  float2 *d_tw = nullptr, *d_utw = nullptr, *d_phase = nullptr, *d_minmax = nullptr;
+  DevBuf<unsigned char> ws_sim;
+  DevBuf<uint32_t> d_gidx;
+  DevBuf<float2> d_tw, d_utw, d_phase, d_minmax;
   // generic path
-  float *d_win_g = nullptr, *d_win_lo_g = nullptr, *d_g_g = nullptr;
-  int32_t* d_idx_g = nullptr;
+  DevBuf<float> d_win_g, d_win_lo_g, d_g_g;
+  DevBuf<int32_t> d_idx_g;
   // wave-per-row kernels (fdoct_wave.hip)
-  uint32_t* d_wave_gidx = nullptr;
-  float2* d_wave_tw = nullptr;
+  DevBuf<uint32_t> d_wave_gidx;
+  DevBuf<float2> d_wave_tw;
   int wave_tw_count = 0, wave_off[6] = {0, 0, 0, 0, 0, 0};
   bool wave_tables_ok = false;
-  float2 *d_twg_n = nullptr, *d_twg_nh = nullptr, *d_twg_w = nullptr, *d_twg_mw = nullptr, *d_twg_wh = nullptr, *d_twg_mwh = nullptr;
-  size_t minmax_cap = 0;
+  DevBuf<float2> d_twg_n, d_twg_nh, d_twg_w, d_twg_mw, d_twg_wh, d_twg_mwh;
   // long-row path (fdoct_big.hip): rows in HBM, one DFT plan per length
   struct BigGroupPlan {        // one launch: a group of the transform's passes with the data in LDS (fdoct_big.h)
     int P = 1, Q = 1, F = 1, log2ts = 0;
@@ -121,58 +166,48 @@ struct fdoct_ctx {
     std::vector<int> rad;      // Stockham radices of the length itself, or (Bluestein) of mb: the one-launch-per-pass form
     std::vector<BigGroupPlan> groups;  // the same transform as a few launches of several passes each (empty: not available)
     int mb = 0;                // > 0: the length has a prime factor above 5 and runs as Bluestein around two mb-point DFTs
-    float2 *d_tw = nullptr, *d_chirp = nullptr, *d_bhat = nullptr;  // exp(+2 pi i j / (mb ? mb : n)); e^(+i pi m^2/n); DFT(conj chirp)/mb
+    DevBuf<float2> d_tw, d_chirp, d_bhat;  // exp(+2 pi i j / (mb ? mb : n)); e^(+i pi m^2/n); DFT(conj chirp)/mb
   };
   bool use_big = false;
   std::map<int, BigPlan> big_plans;
-  float* ws_big_y = nullptr;
-  float2 *ws_big_a = nullptr, *ws_big_b = nullptr;
-  size_t ws_big_y_cap = 0, ws_big_a_cap = 0, ws_big_b_cap = 0;
+  DevBuf<float> ws_big_y;
+  DevBuf<float2> ws_big_a, ws_big_b;
   // workspaces
-  void* ws_in = nullptr;
-  size_t ws_in_cap = 0;
-  float *ws_f32 = nullptr, *ws_f32_lo = nullptr;   // f64 frames as two f32 planes (launch_f64_split)
-  size_t ws_f32_cap = 0, ws_f32_lo_cap = 0;
-  float* ws_mov_lo = nullptr;                       // ... and the moving average of the low plane
-  size_t ws_mov_lo_cap = 0;
-  float *ws_out0 = nullptr, *ws_out1 = nullptr, *ws_tr = nullptr;
-  size_t ws_out0_cap = 0, ws_out1_cap = 0, ws_tr_cap = 0;
-  float2* ws_ylin = nullptr;
-  size_t ws_ylin_cap = 0;
+  DevBuf<unsigned char> ws_in;
+  DevBuf<float> ws_f32, ws_f32_lo;   // f64 frames as two f32 planes (launch_f64_split)
+  DevBuf<float> ws_mov_lo;           // ... and the moving average of the low plane
+  DevBuf<float> ws_out0, ws_out1, ws_tr;
+  DevBuf<float2> ws_ylin;
   long long ylin_rows = 0;  // A-scans the last staged run left in ws_ylin (0: none)
-  float* ws_mov = nullptr;
-  size_t ws_mov_cap = 0;
-  void *ws_front = nullptr, *ws_med = nullptr, *ws_raw = nullptr;
-  size_t ws_front_cap = 0, ws_med_cap = 0, ws_raw_cap = 0;
+  DevBuf<float> ws_mov;
+  DevBuf<unsigned char> ws_front, ws_med, ws_raw;
   int fe_median = 0, fe_binx = 1, fe_biny = 1;
   // display post-chain
   // host-pointer pipeline (fdoct_process with host buffers): copy-in / kernels / copy-out on three streams
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t pe_in[2] = {nullptr, nullptr}, pe_k[2] = {nullptr, nullptr}, pe_out[2] = {nullptr, nullptr};
-  void* pl_in[2] = {nullptr, nullptr};
-  float *pl_mag[2] = {nullptr, nullptr}, *pl_db[2] = {nullptr, nullptr};
-  size_t pl_in_cap[2] = {0, 0}, pl_mag_cap[2] = {0, 0}, pl_db_cap[2] = {0, 0};
+  DevBuf<unsigned char> pl_in[2];
+  DevBuf<float> pl_mag[2], pl_db[2];
   // the same pipeline fed from / drained to PAGEABLE caller memory (fdoct_hostcopy.h): pinned staging slots the handle owns
   // and the threads that move a chunk between them and the caller's buffers
-  void* pin_in[2] = {nullptr, nullptr};
-  float *pin_mag[2] = {nullptr, nullptr}, *pin_db[2] = {nullptr, nullptr};
-  size_t pin_in_cap[2] = {0, 0}, pin_mag_cap[2] = {0, 0}, pin_db_cap[2] = {0, 0};
-  fdoct_impl::HostCopyPool* copy_pool = nullptr;
+  PinnedBuf<unsigned char> pin_in[2];
+  PinnedBuf<float> pin_mag[2], pin_db[2];
+  std::unique_ptr<fdoct_impl::HostCopyPool> copy_pool;
   int host_staging = -1;  // fdoct_set_host_staging: -1 = the library decides per buffer (pageable: staged), 0 = never, > 0 = that many copy threads
   unsigned char lut[768];
   bool lut_dirty = true;
-  unsigned char* d_lut = nullptr;
-  double* d_disp_part = nullptr;
-  size_t disp_part_cap = 0;
-  void *ws_disp_in = nullptr, *ws_disp_in2 = nullptr, *ws_disp_out = nullptr;
-  size_t ws_disp_in_cap = 0, ws_disp_in2_cap = 0, ws_disp_out_cap = 0;
+  DevBuf<unsigned char> d_lut;
+  DevBuf<double> d_disp_part;
+  DevBuf<float> ws_disp_in, ws_disp_in2;
+  DevBuf<unsigned char> ws_disp_out;
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
   bool async_timing = false, record_now = false;  // event records cost stream time: async calls opt in
   bool rec_first = true, rec_last = true;         // chunked calls: the first chunk records the start events, the last one the end events
-  unsigned* d_tro_fault = nullptr;                // see FusedArgs::tr_fault: one word of pinned, device-visible HOST memory, so that any
-                                                  // entry point can look at it without a copy or a synchronisation of its own
+  // see FusedArgs::tr_fault: one word of pinned, device-visible HOST memory, so that any entry point can look at it without a
+  // copy or a synchronisation of its own (coherent: fdoct_route.cpp, launch_family_fused)
+  PinnedBuf<unsigned> d_tro_fault{hipHostMallocCoherent | hipHostMallocMapped};
   bool tro_used = false;                          // a TRO launch has run on this handle
   bool tro_enabled = true;                        // FDOCT_NO_TRO=1 (tuning / tests): always the two-pass path
   size_t tr_chunk_bytes = (size_t)2 << 30;        // transposed layout, two-pass path: row-major intermediate per chunk (bounds the workspace)
@@ -223,47 +258,9 @@ struct DeviceScope {
   return fail(h, FDOCT_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(device_scope_.err))
 
 template <typename T>
-int dev_alloc(fdoct_ctx* h, T** p, size_t count) {
-  if (*p) {
-    (void)hipFree(*p);
-    *p = nullptr;
-  }
-  if (count == 0) return FDOCT_OK;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-  if (e != hipSuccess) return fail(h, FDOCT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  return FDOCT_OK;
-}
-
-template <typename T>
-int dev_reserve(fdoct_ctx* h, T** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes && *p) return FDOCT_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), bytes);
-  if (e != hipSuccess) return fail(h, FDOCT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  *cap = bytes;
-  return FDOCT_OK;
-}
-
-// pinned host memory, grown on demand (the staging slots of fdoct_process's chunk pipeline)
-template <typename T>
-int host_reserve(fdoct_ctx* h, T** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes && *p) return FDOCT_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  hipError_t e = hipHostMalloc(reinterpret_cast<void**>(p), bytes, hipHostMallocDefault);
-  if (e != hipSuccess) return fail(h, FDOCT_ERR_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-  *cap = bytes;
-  return FDOCT_OK;
-}
-
-template <typename T>
-int upload(fdoct_ctx* h, T** dptr, const std::vector<T>& v) {
-  int rc = dev_alloc(h, dptr, v.size());
-  if (rc) return rc;
-  if (!v.empty()) HIP_TRY(h, hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+int upload(fdoct_ctx* h, DevBuf<T>& d, const std::vector<T>& v) {
+  if (int rc = d.assign(h, v.size())) return rc;
+  if (!v.empty()) HIP_TRY(h, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return FDOCT_OK;
 }
 
@@ -327,7 +324,6 @@ struct Call {
 int kernel_dtype(int dt);
 int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_w, int raw_h, size_t raw_pitch, int mediann,
                  int binx, int biny, void** out, size_t* out_pitch);
-void big_plans_free(fdoct_ctx* h);
 int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
                  uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r);
 int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes,

@@ -30,14 +30,14 @@ int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_
   size_t src_pitch = raw_pitch;
   if (mediann > 0) {
     const size_t mp = ((size_t)raw_w * es + 15) & ~(size_t)15;
-    if ((rc = dev_reserve(h, &h->ws_med, &h->ws_med_cap, mp * (size_t)raw_h * nframes))) return rc;
+    if ((rc = h->ws_med.reserve(h, mp * (size_t)raw_h * nframes))) return rc;
     HIP_TRY(h, launch_median(src, (long long)src_pitch, h->ws_med, (long long)mp, kdt, raw_w, raw_h, mediann, nframes, st));
     src = h->ws_med;
     src_pitch = mp;
   }
   const int ow = raw_w / binx, oh = raw_h / biny;
   const size_t op = ((size_t)ow * es + 15) & ~(size_t)15;
-  if ((rc = dev_reserve(h, &h->ws_front, &h->ws_front_cap, op * (size_t)oh * nframes))) return rc;
+  if ((rc = h->ws_front.reserve(h, op * (size_t)oh * nframes))) return rc;
   HIP_TRY(h, launch_bin(src, (long long)src_pitch, h->ws_front, (long long)op, kdt, ow, oh, binx, biny, nframes, st));
   *out = h->ws_front;
   *out_pitch = op;
@@ -126,8 +126,8 @@ int big_plan_get(fdoct_ctx* h, int n, fdoct_ctx::BigPlan** out) {
     std::vector<float2> chirp, bhat;
     build_bluestein_tables(n, mb, chirp, bhat);
     int rc;
-    if ((rc = upload(h, &p.d_chirp, chirp))) return rc;
-    if ((rc = upload(h, &p.d_bhat, bhat))) return rc;
+    if ((rc = upload(h, p.d_chirp, chirp))) return rc;
+    if ((rc = upload(h, p.d_bhat, bhat))) return rc;
   }
   static const bool per_pass = [] { const char* e = std::getenv("FDOCT_BIG_PER_PASS"); return e && std::atoi(e) != 0; }();  // measurement: round 3's form
   if (!per_pass) big_plan_groups(tn, p.groups);
@@ -137,16 +137,9 @@ int big_plan_get(fdoct_ctx* h, int n, fdoct_ctx::BigPlan** out) {
     tw[j] = make_float2((float)std::cos(a), (float)std::sin(a));
   }
   int rc;
-  if ((rc = upload(h, &p.d_tw, tw))) return rc;
-  *out = &h->big_plans.emplace(n, p).first->second;
+  if ((rc = upload(h, p.d_tw, tw))) return rc;
+  *out = &h->big_plans.emplace(n, std::move(p)).first->second;
   return FDOCT_OK;
-}
-
-void big_plans_free(fdoct_ctx* h) {
-  for (auto& kv : h->big_plans)
-    for (float2* p : {kv.second.d_tw, kv.second.d_chirp, kv.second.d_bhat})
-      if (p) (void)hipFree(p);
-  h->big_plans.clear();
 }
 
 // What stands in front of a transform, fused into the loads of its first launch (or run as a kernel of its own where the
@@ -256,9 +249,9 @@ int run_big(fdoct_ctx* h, const void* kframes, const float* kframes_lo, int kdt,
   if (cg < 1) cg = 1;
   if (cg > G) cg = G;
   const size_t crow = (size_t)cg * A * H;
-  if ((rc = dev_reserve(h, &h->ws_big_y, &h->ws_big_y_cap, crow * W * 4))) return rc;
-  if ((rc = dev_reserve(h, &h->ws_big_a, &h->ws_big_a_cap, crow * lmax * sizeof(float2)))) return rc;
-  if ((rc = dev_reserve(h, &h->ws_big_b, &h->ws_big_b_cap, crow * lmax * sizeof(float2)))) return rc;
+  if ((rc = h->ws_big_y.reserve(h, crow * W * 4))) return rc;
+  if ((rc = h->ws_big_a.reserve(h, crow * lmax * sizeof(float2)))) return rc;
+  if ((rc = h->ws_big_b.reserve(h, crow * lmax * sizeof(float2)))) return rc;
   for (long long g0 = 0; g0 < G; g0 += cg) {
     const long long ng = std::min<long long>(cg, G - g0);
     BigArgs a{};
@@ -929,9 +922,10 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
     grid = h->grid_override > 0 ? h->grid_override : h->num_cu;   // one workgroup per CU (the ring fills its LDS)
     if (grid > tiles) grid = tiles;
     if (!h->d_tro_fault) {
-      // (coherent, mapped host memory; the kernels raise the word with a plain system-scope STORE of 1 -- a read-modify-write
-      // atomic on host memory would need PCIe AtomicOps on the link and is dropped silently where they are missing: ADVICE r4)
-      HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->d_tro_fault), sizeof(unsigned), hipHostMallocCoherent | hipHostMallocMapped));
+      // (coherent, mapped host memory: the buffer's flags, fdoct_ctx.h.  The kernels raise the word with a plain system-scope
+      // STORE of 1 -- a read-modify-write atomic on host memory would need PCIe AtomicOps on the link and is dropped silently
+      // where they are missing: ADVICE r4)
+      if ((rc = h->d_tro_fault.reserve(h, sizeof(unsigned)))) return rc;
       *h->d_tro_fault = 0u;
     }
     h->tro_used = true;
@@ -947,7 +941,7 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
       return fail(h, FDOCT_ERR_UNSUPPORTED, "staged mode is built for the plain u16 acquisition configuration only");
     // one k-linear row per INPUT A-scan between the stages: the resample stage runs over the in_rows input rows as they
     // lie (A = 1), the FFT stage gathers the A rows of an output A-scan
-    if ((rc = dev_reserve(h, &h->ws_ylin, &h->ws_ylin_cap, (size_t)c.in_rows * h->NC * sizeof(float2)))) return rc;
+    if ((rc = h->ws_ylin.reserve(h, (size_t)c.in_rows * h->NC * sizeof(float2)))) return rc;
     a.ylin = h->ws_ylin;
     h->ylin_rows = c.in_rows;
     {
@@ -1013,16 +1007,16 @@ int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nfram
     pitch_now = fp;
   }
   if (r.narrow_f64 && r.movavg) {  // doubles through smoothmovavg (main:987-991): the tap sums in double, then the two planes
-    if ((rc = dev_reserve(h, &h->ws_mov, &h->ws_mov_cap, (size_t)c.in_rows * W * 4))) return rc;
-    if ((rc = dev_reserve(h, &h->ws_mov_lo, &h->ws_mov_lo_cap, (size_t)c.in_rows * W * 4 + 32))) return rc;
+    if ((rc = h->ws_mov.reserve(h, (size_t)c.in_rows * W * 4))) return rc;
+    if ((rc = h->ws_mov_lo.reserve(h, (size_t)c.in_rows * W * 4 + 32))) return rc;
     HIP_TRY(h, launch_movavg_f64(static_cast<const double*>(d_frames), (long long)(pitch_bytes / 8), W, c.in_rows, h->cfg.movavgn, h->ws_mov, h->ws_mov_lo, st));
     c.kframes = h->ws_mov;
     c.kframes_lo = h->ws_mov_lo;
     pitch_now = (size_t)W * 4;
     kdt_now = FDOCT_K_F32;
   } else if (r.narrow_f64) {  // data_y doubles (main:987): split once into two f32 planes on the device, x = hi + lo
-    if ((rc = dev_reserve(h, &h->ws_f32, &h->ws_f32_cap, (size_t)c.in_rows * W * 4))) return rc;
-    if ((rc = dev_reserve(h, &h->ws_f32_lo, &h->ws_f32_lo_cap, (size_t)c.in_rows * W * 4 + 32))) return rc;
+    if ((rc = h->ws_f32.reserve(h, (size_t)c.in_rows * W * 4))) return rc;
+    if ((rc = h->ws_f32_lo.reserve(h, (size_t)c.in_rows * W * 4 + 32))) return rc;
     HIP_TRY(h, launch_f64_split(static_cast<const double*>(d_frames), (long long)(pitch_bytes / 8), h->ws_f32, h->ws_f32_lo, W, c.in_rows, st));
     c.kframes = h->ws_f32;
     c.kframes_lo = h->ws_f32_lo;
@@ -1030,15 +1024,15 @@ int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nfram
     kdt_now = FDOCT_K_F32;
   }
   if (r.movavg && r.mov_lo && !r.narrow_f64) {  // ... of float frames: sums in double, two planes
-    if ((rc = dev_reserve(h, &h->ws_mov, &h->ws_mov_cap, (size_t)c.in_rows * W * 4))) return rc;
-    if ((rc = dev_reserve(h, &h->ws_mov_lo, &h->ws_mov_lo_cap, (size_t)c.in_rows * W * 4 + 32))) return rc;
+    if ((rc = h->ws_mov.reserve(h, (size_t)c.in_rows * W * 4))) return rc;
+    if ((rc = h->ws_mov_lo.reserve(h, (size_t)c.in_rows * W * 4 + 32))) return rc;
     HIP_TRY(h, launch_movavg_f32_wide(static_cast<const float*>(c.kframes), (long long)(pitch_now / 4), W, c.in_rows, h->cfg.movavgn, h->ws_mov, h->ws_mov_lo, st));
     c.kframes = h->ws_mov;
     c.kframes_lo = h->ws_mov_lo;
     pitch_now = (size_t)W * 4;
     kdt_now = FDOCT_K_F32;
   } else if (r.movavg && !r.narrow_f64) {  // smoothmovavg (main:990-991) runs before everything else, on the raw samples
-    if ((rc = dev_reserve(h, &h->ws_mov, &h->ws_mov_cap, (size_t)c.in_rows * W * 4))) return rc;
+    if ((rc = h->ws_mov.reserve(h, (size_t)c.in_rows * W * 4))) return rc;
     HIP_TRY(h, launch_movavg(c.kframes, kdt_now, (long long)pitch_now, W, c.in_rows, h->cfg.movavgn, h->ws_mov, st));
     c.kframes = h->ws_mov;
     pitch_now = (size_t)W * 4;
@@ -1048,7 +1042,7 @@ int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nfram
   if (r.need_minmax) {
     // [nframes] results followed by the fast kernel's per-workgroup partials
     const size_t mm_elems = (size_t)nframes + (size_t)minmax_partial_count(nframes);
-    if ((rc = dev_reserve(h, &h->d_minmax, &h->minmax_cap, mm_elems * sizeof(float2)))) return rc;
+    if ((rc = h->d_minmax.reserve(h, mm_elems * sizeof(float2)))) return rc;
     HIP_TRY(h, launch_minmax(c.kframes, r.kdt, (long long)r.kpitch, W, H, nframes, h->d_yd, h->yd.rows > 1, h->d_minmax,
                              h->d_minmax + nframes, st));
   }
@@ -1057,7 +1051,7 @@ int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nfram
   c.k_db = d_out_db;
   if (r.transpose_pass) {
     const size_t bytes = (size_t)c.out_rows * D * 4;
-    if ((rc = dev_reserve(h, &h->ws_tr, &h->ws_tr_cap, bytes * 2))) return rc;
+    if ((rc = h->ws_tr.reserve(h, bytes * 2))) return rc;
     if (d_out_bscan) c.k_mag = h->ws_tr;
     if (d_out_db) c.k_db = h->ws_tr + (size_t)c.out_rows * D;
   }

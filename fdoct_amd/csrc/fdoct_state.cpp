@@ -399,22 +399,22 @@ int rebuild_device_state(fdoct_ctx* h) {
         h16_2d.resize((size_t)H * WC / 2);
         for (int r = 0; r < H; r++) half_pattern_row(ybs.data() + (size_t)r * W, WC, p.T, h16_2d.data() + (size_t)r * WC / 2);
       }
-      if ((rc = upload(h, &h->d_il16, h16))) return rc;
-      if ((rc = upload(h, &h->d_il16_2d, h16_2d))) return rc;
+      if ((rc = upload(h, h->d_il16, h16))) return rc;
+      if ((rc = upload(h, h->d_il16_2d, h16_2d))) return rc;
     }
     if (h->yb.rows == 1) {
-      if ((rc = upload(h, &h->d_ib, ib))) return rc;
-      if ((rc = upload(h, &h->d_il, il))) return rc;
+      if ((rc = upload(h, h->d_ib, ib))) return rc;
+      if ((rc = upload(h, h->d_il, il))) return rc;
       {  // the same plane in the slot order of the kernels' LDS planes (sample 8 (ln + T c) + e -> c 8T + (e & 1) 4T + 4 ln + (e >> 1))
         std::vector<float> ilp((size_t)WC, 0.f);
         for (int i = 0; i < W; i++) {
           const int e = i & 7, ln = (i >> 3) & (p.T - 1), c = i / (8 * p.T);
           ilp[(size_t)c * 8 * p.T + (e & 1) * 4 * p.T + 4 * ln + (e >> 1)] = il[i];
         }
-        if ((rc = upload(h, &h->d_il_p, ilp))) return rc;
+        if ((rc = upload(h, h->d_il_p, ilp))) return rc;
       }
-      if ((rc = dev_alloc(h, &h->d_ib2d_f, 0))) return rc;
-      if ((rc = dev_alloc(h, &h->d_il2d_f, 0))) return rc;
+      h->d_ib2d_f.release();
+      h->d_il2d_f.release();
     } else {
       // the fused kernels read a 2-D background with every 8-sample group stored evens first, then odds (the
       // order their sample pairs are held in), rows padded to the plan's chunk width; the generic kernel keeps
@@ -425,15 +425,15 @@ int rebuild_device_state(fdoct_ctx* h) {
           for (int i = 0; i < W; i++) perm[(size_t)r * WC + (i & ~7) + ((i & 1) * 4 + ((i & 7) >> 1))] = src[(size_t)r * W + i];
       };
       permute(ib);
-      if ((rc = upload(h, &h->d_ib2d_f, perm))) return rc;
+      if ((rc = upload(h, h->d_ib2d_f, perm))) return rc;
       permute(il);
-      if ((rc = upload(h, &h->d_il2d_f, perm))) return rc;
-      if ((rc = dev_alloc(h, &h->d_ib, 0))) return rc;
-      if ((rc = dev_alloc(h, &h->d_il, 0))) return rc;
+      if ((rc = upload(h, h->d_il2d_f, perm))) return rc;
+      h->d_ib.release();
+      h->d_il.release();
     }
   }
   // (second words: what the float planes leave of the double ones -- read where the row is formed in double, BscanDark's band-pass)
-  auto up_ref = [&](const RefFrame& f, double scale, float** d, float** d_lo) -> int {
+  auto up_ref = [&](const RefFrame& f, double scale, DevBuf<float>& d, DevBuf<float>& d_lo) -> int {
     std::vector<float> t(f.v.size()), tl(f.v.size());
     for (size_t i = 0; i < t.size(); i++) {
       t[i] = (float)(f.v[i] * scale);
@@ -442,8 +442,8 @@ int rebuild_device_state(fdoct_ctx* h) {
     if (int e = upload(h, d_lo, tl)) return e;
     return upload(h, d, t);
   };
-  if ((rc = up_ref(h->yp, plane_scales(h).yp, &h->d_yp, &h->d_yp_lo))) return rc;
-  if ((rc = up_ref(h->yd, plane_scales(h).yd, &h->d_yd, &h->d_yd_lo))) return rc;
+  if ((rc = up_ref(h->yp, plane_scales(h).yp, h->d_yp, h->d_yp_lo))) return rc;
+  if ((rc = up_ref(h->yd, plane_scales(h).yd, h->d_yd, h->d_yd_lo))) return rc;
   {
     // Window (main:1142) and slope step (main:1153-1173) folded into two per-sample planes: with t = x - mean and
     // y = t * w, s_i = y_i + g_i (y_i - y_(i-1)) = a_i t_i + b_i t_(i-1), a_i = (1 + g_i) w_i, b_i = -g_i w_(i-1).
@@ -460,8 +460,8 @@ int rebuild_device_state(fdoct_ctx* h) {
     }
     pa[0] = (float)((1.0 - gg(0)) * half * h->win[0]);
     pb[0] = (float)(gg(0) * half * h->win[1]);
-    if ((rc = upload(h, &h->d_win, pa))) return rc;
-    if ((rc = upload(h, &h->d_g, pb))) return rc;
+    if ((rc = upload(h, h->d_win, pa))) return rc;
+    if ((rc = upload(h, h->d_g, pb))) return rc;
   }
   {
     // gather sources: data_ylin[q] = s[nearestkindex[q]] for q = 1..N-2, else 0 (main:1164)
@@ -471,7 +471,7 @@ int rebuild_device_state(fdoct_ctx* h) {
       return (uint32_t)staging_offset_bytes(h->idx[q], WC, h->split);
     };
     for (int n = 0; n < h->NC; n++) gi[n] = h->cplx ? off(n) : (off(2 * n) | (off(2 * n + 1) << 16));
-    if ((rc = upload(h, &h->d_gidx, gi))) return rc;
+    if ((rc = upload(h, h->d_gidx, gi))) return rc;
   }
   {
     std::vector<float2> tw(h->tw_count, make_float2(0.f, 0.f));
@@ -503,18 +503,18 @@ int rebuild_device_state(fdoct_ctx* h) {
           const double a = 2.0 * kPi * (double)r * (double)k / (double)h->NC;
           tw[o++] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
-    if ((rc = upload(h, &h->d_tw, tw))) return rc;
+    if ((rc = upload(h, h->d_tw, tw))) return rc;
     std::vector<float2> utw(p.T);
     for (int l = 0; l < p.T; l++) {
       const double a = 2.0 * kPi * (double)l / (double)N;
       utw[l] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
-    if ((rc = upload(h, &h->d_utw, utw))) return rc;
+    if ((rc = upload(h, h->d_utw, utw))) return rc;
   }
   {
     std::vector<float2> ph(h->phase.size() / 2);
     for (size_t i = 0; i < ph.size(); i++) ph[i] = make_float2(h->phase[2 * i], h->phase[2 * i + 1]);
-    if ((rc = upload(h, &h->d_phase, ph))) return rc;
+    if ((rc = upload(h, h->d_phase, ph))) return rc;
   }
   (void)H;
   h->dirty = false;
@@ -603,19 +603,19 @@ int rebuild_generic_state(fdoct_ctx* h) {
     std::vector<float> ib, il;
     reciprocal_words(scaled_copy(h->yb.v, plane_scales(h).yb), ib, il);
     if (h->yb.rows == 1) {
-      if ((rc = upload(h, &h->d_ib, ib))) return rc;
-      if ((rc = upload(h, &h->d_il, il))) return rc;
-      if ((rc = dev_alloc(h, &h->d_ib2d, 0))) return rc;
-      if ((rc = dev_alloc(h, &h->d_il2d, 0))) return rc;
+      if ((rc = upload(h, h->d_ib, ib))) return rc;
+      if ((rc = upload(h, h->d_il, il))) return rc;
+      h->d_ib2d.release();
+      h->d_il2d.release();
     } else {
-      if ((rc = upload(h, &h->d_ib2d, ib))) return rc;
-      if ((rc = upload(h, &h->d_il2d, il))) return rc;
-      if ((rc = dev_alloc(h, &h->d_ib, 0))) return rc;
-      if ((rc = dev_alloc(h, &h->d_il, 0))) return rc;
+      if ((rc = upload(h, h->d_ib2d, ib))) return rc;
+      if ((rc = upload(h, h->d_il2d, il))) return rc;
+      h->d_ib.release();
+      h->d_il.release();
     }
   }
   // (second words: what the float planes leave of the double ones -- read where the row is formed in double, BscanDark's band-pass)
-  auto up_ref = [&](const RefFrame& f, double scale, float** d, float** d_lo) -> int {
+  auto up_ref = [&](const RefFrame& f, double scale, DevBuf<float>& d, DevBuf<float>& d_lo) -> int {
     std::vector<float> t(f.v.size()), tl(f.v.size());
     for (size_t i = 0; i < t.size(); i++) {
       t[i] = (float)(f.v[i] * scale);
@@ -624,20 +624,20 @@ int rebuild_generic_state(fdoct_ctx* h) {
     if (int e = upload(h, d_lo, tl)) return e;
     return upload(h, d, t);
   };
-  if ((rc = up_ref(h->yp, plane_scales(h).yp, &h->d_yp, &h->d_yp_lo))) return rc;
-  if ((rc = up_ref(h->yd, plane_scales(h).yd, &h->d_yd, &h->d_yd_lo))) return rc;
+  if ((rc = up_ref(h->yp, plane_scales(h).yp, h->d_yp, h->d_yp_lo))) return rc;
+  if ((rc = up_ref(h->yd, plane_scales(h).yd, h->d_yd, h->d_yd_lo))) return rc;
   std::vector<float> w(W), g(MW);
   for (int i = 0; i < W; i++) w[i] = (float)h->win[i];
   for (int i = 0; i < MW; i++) g[i] = (i < N) ? (float)h->frac[i] : 0.f;  // fractionalk[nearestkindex[q]], 0 past its end
-  if ((rc = upload(h, &h->d_win_g, w))) return rc;
+  if ((rc = upload(h, h->d_win_g, w))) return rc;
   {
     std::vector<float> wl(W);
     for (int i = 0; i < W; i++) wl[i] = (float)(h->win[i] - (double)w[i]);
-    if ((rc = upload(h, &h->d_win_lo_g, wl))) return rc;
+    if ((rc = upload(h, h->d_win_lo_g, wl))) return rc;
   }
-  if ((rc = upload(h, &h->d_g_g, g))) return rc;
-  if ((rc = upload(h, &h->d_idx_g, h->idx))) return rc;
-  auto up_tw = [&](int n, float2** d) -> int {
+  if ((rc = upload(h, h->d_g_g, g))) return rc;
+  if ((rc = upload(h, h->d_idx_g, h->idx))) return rc;
+  auto up_tw = [&](int n, DevBuf<float2>& d) -> int {
     std::vector<float2> t(n);
     for (int j = 0; j < n; j++) {
       const double a = 2.0 * kPi * (double)j / (double)n;
@@ -645,39 +645,39 @@ int rebuild_generic_state(fdoct_ctx* h) {
     }
     return upload(h, d, t);
   };
-  if ((rc = up_tw(N, &h->d_twg_n))) return rc;
-  if ((N % 2) == 0 && (rc = up_tw(N / 2, &h->d_twg_nh))) return rc;
+  if ((rc = up_tw(N, h->d_twg_n))) return rc;
+  if ((N % 2) == 0 && (rc = up_tw(N / 2, h->d_twg_nh))) return rc;
   if (h->blu_m) {
     const int n = generic_real_half(h) ? N / 2 : N, Mb = h->blu_m;
     std::vector<float2> chirp, bhat;
     build_bluestein_tables(n, Mb, chirp, bhat);
-    if ((rc = upload(h, &h->d_blu_chirp, chirp))) return rc;
-    if ((rc = upload(h, &h->d_blu_bhat, bhat))) return rc;
-    if ((rc = up_tw(Mb, &h->d_twg_blu))) return rc;
+    if ((rc = upload(h, h->d_blu_chirp, chirp))) return rc;
+    if ((rc = upload(h, h->d_blu_bhat, bhat))) return rc;
+    if ((rc = up_tw(Mb, h->d_twg_blu))) return rc;
   }
   if (h->M > 1 && h->zp_full) {  // the full-length zero-pad stage's two plans
     for (fdoct_ctx::GenericDftPlan* p : {&h->gzf, &h->gzi}) {
-      if ((rc = up_tw(p->blu_m ? p->blu_m : p->n, &p->d_tw))) return rc;
+      if ((rc = up_tw(p->blu_m ? p->blu_m : p->n, p->d_tw))) return rc;
       if (p->blu_m) {
         std::vector<float2> chirp, bhat;
         build_bluestein_tables(p->n, p->blu_m, chirp, bhat);
-        if ((rc = upload(h, &p->d_chirp, chirp))) return rc;
-        if ((rc = upload(h, &p->d_bhat, bhat))) return rc;
+        if ((rc = upload(h, p->d_chirp, chirp))) return rc;
+        if ((rc = upload(h, p->d_bhat, bhat))) return rc;
       }
     }
   }
   if (h->M > 1) {
-    if ((rc = up_tw(W, &h->d_twg_w))) return rc;     // untangle factors of the half-length transforms
-    if ((rc = up_tw(MW, &h->d_twg_mw))) return rc;
-    if ((rc = up_tw(W / 2, &h->d_twg_wh))) return rc;
-    if ((rc = up_tw(MW / 2, &h->d_twg_mwh))) return rc;
+    if ((rc = up_tw(W, h->d_twg_w))) return rc;     // untangle factors of the half-length transforms
+    if ((rc = up_tw(MW, h->d_twg_mw))) return rc;
+    if ((rc = up_tw(W / 2, h->d_twg_wh))) return rc;
+    if ((rc = up_tw(MW / 2, h->d_twg_mwh))) return rc;
   }
   {
     std::vector<float2> ph(h->phase.size() / 2);
     for (size_t i = 0; i < ph.size(); i++) ph[i] = make_float2(h->phase[2 * i], h->phase[2 * i + 1]);
-    if ((rc = upload(h, &h->d_phase, ph))) return rc;
+    if ((rc = upload(h, h->d_phase, ph))) return rc;
   }
-  if (!h->d_gen_tickets && (rc = dev_alloc(h, &h->d_gen_tickets, 64))) return rc;   // generic_kernel's row counters (launch_family_generic)
+  if (!h->d_gen_tickets && (rc = h->d_gen_tickets.assign(h, 64))) return rc;   // generic_kernel's row counters (launch_family_generic)
   h->dirty = false;
   h->generic_tables_ok = true;
   return FDOCT_OK;
@@ -721,8 +721,8 @@ int rebuild_wave_state(fdoct_ctx* h) {
     for (int k = 0; k < (D > N / 2 ? N / 2 + 1 : D); k++) tw.push_back(unit((double)k, (double)N));
   h->wave_tw_count = (int)tw.size();
   int rc;
-  if ((rc = upload(h, &h->d_wave_gidx, gi))) return rc;
-  if ((rc = upload(h, &h->d_wave_tw, tw))) return rc;
+  if ((rc = upload(h, h->d_wave_gidx, gi))) return rc;
+  if ((rc = upload(h, h->d_wave_tw, tw))) return rc;
   h->wave_tables_ok = true;
   return FDOCT_OK;
 }

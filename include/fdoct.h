@@ -9,8 +9,9 @@
  * BscanFFT.cpp, "sim" = BscanFFTsim.cpp, "dark" = BscanDark.cpp.
  *
  * Conventions (mirroring the reference host code, main:729-925,1991-1993):
- *   - every call returns int, 0 = success, negative = error; nothing throws or
- *     exits across this boundary; fdoct_last_error() gives the text;
+ *   - every call returns int, 0 = success, negative = error; every entry point
+ *     catches at this boundary, so nothing throws or exits across it (out of
+ *     host memory is FDOCT_ERR_NOMEM); fdoct_last_error() gives the text;
  *   - the caller owns every buffer it passes; setters COPY; the library never
  *     keeps a caller pointer after the call returns;
  *   - a handle is used from one thread at a time (the reference loop is single

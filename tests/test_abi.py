@@ -94,6 +94,66 @@ int main(void) {
     assert int(mid) == int(oidx[512]) and ver.split()[1].startswith(hv)
 
 
+def test_out_of_host_memory_in_an_entry_point_is_an_error_code(tmp_path):
+    """Nothing throws across the C ABI (include/fdoct.h): tests/native/alloc_fail_check.cpp replaces the global operator new
+    so that the k-th allocation fails, and for every k each host-only table builder returns FDOCT_ERR_NOMEM instead of
+    taking the process down -- and disarmed computes what it computed before.  Built the way a C++ host links the library."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++")
+    if not cxx:
+        pytest.skip("no g++")
+    exe = tmp_path / "alloc_fail_check"
+    libdir = os.path.dirname(fdoct_amd.library_path())
+    cmd = [cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+           os.path.join(ROOT, "tests", "native", "alloc_fail_check.cpp"), "-o", str(exe),
+           "-L", libdir, "-lfdoct_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = out.stdout.strip().splitlines()
+    assert lines[-1] == "ok" and len(lines) == 4, out.stdout
+
+
+def test_every_entry_point_catches_at_the_boundary():
+    """Each extern "C" definition in fdoct_capi.cpp is a function-try-block that ends in the boundary's catch macro
+    (FDOCT_CATCH and its variants), and those definitions are exactly the exported ABI."""
+    src = open(os.path.join(ROOT, "fdoct_amd", "csrc", "fdoct_capi.cpp")).read()
+    body = src[src.index('extern "C" {'):src.rindex('}  // extern "C"')]
+
+    def close_of(i):  # index of the brace that closes the one at i (string / character literals and // comments skipped)
+        depth = 0
+        while True:
+            if body.startswith("//", i):
+                i = body.index("\n", i)
+                continue
+            c = body[i]
+            if c in "\"'":
+                j = i + 1
+                while body[j] != c:
+                    j += 2 if body[j] == "\\" else 1
+                i = j + 1
+                continue
+            depth += {"{": 1, "}": -1}.get(c, 0)
+            if depth == 0:
+                return i
+            i += 1
+
+    defined = []
+    for m in re.finditer(r"^(?!static\b)[A-Za-z_][\w \*]*?\b(fdoct_\w+)\(", body, re.M):
+        head_end = min(k for k in (body.find("{", m.end()), body.find(";", m.end())) if k >= 0)
+        if body[head_end] == ";":
+            continue  # a declaration
+        name = m.group(1)
+        defined.append(name)
+        assert re.search(r"\)\s*try\s*$", body[m.start():head_end]), name + " is not a function-try-block"
+        tail = body[close_of(head_end) + 1:]
+        assert re.match(r"\s*FDOCT_CATCH\w*\(", tail), name + " does not end in FDOCT_CATCH"
+    assert len(defined) == len(set(defined)) == 50
+    assert set(defined) == set(capi.ABI_SYMBOLS)
+
+
 def test_run_time_compile_of_the_wave_kernel_needs_no_gpu():
     """fdoct_jit_compile_check: the device source that travels inside the library compiles for gfx950 through hipRTC for a
     geometry outside the built-in list (1280 samples, zero-pad x2, numfftpoints 2560), and a geometry the template cannot take
