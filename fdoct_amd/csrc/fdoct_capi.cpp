@@ -40,7 +40,7 @@ static int caught(fdoct_ctx* h) noexcept {
     err.clear();
   }
   if (h) {
-    h->dirty = true;
+    invalidate(h);
     drain(h);
   }
   return code;
@@ -128,8 +128,7 @@ int fdoct_create(const fdoct_config* cfg, fdoct_handle* out) try {
 
   build_resample_table(h->W, h->M, h->N, cfg->lambdamin, cfg->lambdamax, h->idx, h->frac);
   build_barthann(h->W, h->win);
-  int rc = select_plan(h);
-  if (rc) return fail(nullptr, rc, h->err);
+  if (int rc = adopt_plan(h, plan_inputs(h))) return fail(nullptr, rc, h->err);
   builtin_jet(h->lut);
   if (const char* e = std::getenv("FDOCT_NO_TRO")) h->tro_enabled = std::atoi(e) == 0;
   if (const char* e = std::getenv("FDOCT_JIT")) h->jit = std::atoi(e) != 0;
@@ -193,7 +192,7 @@ int fdoct_set_window(fdoct_handle h, const double* win, int n) try {
     h->win.assign(win, win + n);
     h->custom_win = true;
   }
-  h->dirty = true;
+  invalidate(h);
   return FDOCT_OK;
 } FDOCT_CATCH(h)
 
@@ -206,7 +205,7 @@ int fdoct_set_resample_table(fdoct_handle h, const int32_t* nearestkindex, const
   h->idx.assign(nearestkindex, nearestkindex + n);
   h->frac.assign(fractionalk, fractionalk + n);
   h->custom_table = true;
-  h->dirty = true;
+  invalidate(h);
   return FDOCT_OK;
 } FDOCT_CATCH(h)
 
@@ -217,28 +216,22 @@ int fdoct_set_lambda_range(fdoct_handle h, double lambdamin, double lambdamax) t
   h->cfg.lambdamax = lambdamax;
   build_resample_table(h->W, h->M, h->N, lambdamin, lambdamax, h->idx, h->frac);
   h->custom_table = false;
-  h->dirty = true;
+  invalidate(h);
   return FDOCT_OK;
 } FDOCT_CATCH(h)
 
 int fdoct_set_dispersion_phase(fdoct_handle h, const float* cos_sin_pairs, int n) try {
   if (!h) return FDOCT_ERR_INVALID;
-  std::vector<float> old = h->phase;
-  if (!cos_sin_pairs) {
-    h->phase.clear();
-  } else {
+  std::vector<float> phase;
+  if (cos_sin_pairs) {
     if (n != h->N) return fail(h, FDOCT_ERR_INVALID, "phase length must equal numfftpoints");
-    h->phase.assign(cos_sin_pairs, cos_sin_pairs + 2 * (size_t)n);
+    phase.assign(cos_sin_pairs, cos_sin_pairs + 2 * (size_t)n);
   }
-  h->dirty = true;
-  int rc = select_plan(h);
-  if (rc) {  // no kernel for the complex path at this size: keep the previous state usable
-    const std::string msg = h->err;
-    h->phase.swap(old);
-    (void)select_plan(h);
-    h->err = msg;
-  }
-  return rc;
+  PlanInputs in = plan_inputs(h);
+  in.phase = !phase.empty();
+  if (int rc = adopt_plan(h, in)) return rc;  // no kernel for the complex path at this size: the previous state stays
+  h->phase.swap(phase);
+  return FDOCT_OK;
 } FDOCT_CATCH(h)
 
 int fdoct_get_resample_table(fdoct_handle h, int32_t* nearestkindex, double* fractionalk, int n) try {
@@ -641,10 +634,13 @@ int fdoct_set_plan(fdoct_handle h, int plan_id, int force_general_kernel) try {
   FusedPlan q{};
   if (plan_id >= 0 && !fused_plan_get(plan_id, &q)) return fail(h, FDOCT_ERR_INVALID, "unknown plan id");
   if (plan_id < -3) return fail(h, FDOCT_ERR_INVALID, "plan id: -1 automatic, -2 the workgroup-per-row kernel, -3 the long-row path");
-  h->plan_override = plan_id;
-  h->force_general = force_general_kernel != 0;
-  h->dirty = true;
-  return select_plan(h);
+  PlanInputs in = plan_inputs(h);
+  in.plan_override = plan_id;
+  in.force_general = force_general_kernel != 0;
+  if (int rc = adopt_plan(h, in)) return rc;
+  h->plan_override = in.plan_override;
+  h->force_general = in.force_general;
+  return FDOCT_OK;
 } FDOCT_CATCH(h)
 
 int fdoct_set_frontend(fdoct_handle h, int mediann, int binx, int biny) try {
@@ -888,9 +884,7 @@ int fdoct_clone_to_device(fdoct_handle h, int device, fdoct_handle* out) try {
   c->grid_override = h->grid_override;
   std::memcpy(c->lut, h->lut, sizeof c->lut);
   c->lut_dirty = true;
-  c->dirty = true;
-  rc = select_plan(c);
-  if (rc) return fail(h, rc, "fdoct_clone_to_device: " + c->err);
+  if ((rc = adopt_plan(c, plan_inputs(c)))) return fail(h, rc, "fdoct_clone_to_device: " + c->err);
   *out = owned.release();
   return FDOCT_OK;
 } FDOCT_CATCH(h)
@@ -901,14 +895,14 @@ int fdoct_get_ylin(fdoct_handle h, long long row0, int nrows, double* out) try {
   if (!h->ylin_rows || !h->ws_ylin) return fail(h, FDOCT_ERR_STATE, "fdoct_get_ylin: the last run was not a staged one (fdoct_set_staged)");
   if (row0 + nrows > h->ylin_rows) return fail(h, FDOCT_ERR_INVALID, "fdoct_get_ylin: rows past the end of the last batch");
   DEVICE_SCOPE(h);
-  const int NC = h->NC, N = h->N;
+  const int NC = h->plan.NC, N = h->N;
   std::vector<float2> z((size_t)nrows * NC);
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   HIP_TRY(h, hipMemcpy(z.data(), h->ws_ylin + (size_t)row0 * NC, z.size() * sizeof(float2), hipMemcpyDeviceToHost));
   for (int r = 0; r < nrows; r++) {
     const float2* zr = z.data() + (size_t)r * NC;
     double* o = out + (size_t)r * N;
-    if (h->cplx) {
+    if (h->plan.cplx) {
       // complex path: the stage stores data_ylin[q] * (cos, sin)[q]; the phasors have unit modulus
       for (int q = 0; q < N; q++) o[q] = (double)zr[q].x * h->phase[2 * q] + (double)zr[q].y * h->phase[2 * q + 1];
     } else {
@@ -1111,17 +1105,12 @@ int fdoct_import_state(fdoct_handle h, const void* buf, size_t len) try {
   for (int32_t v : idx)
     if (v < 0 || v >= h->W * h->M)  // the kernels index LDS with these
       return fail(h, FDOCT_ERR_INVALID, "corrupt state blob: nearestkindex entry outside the row");
-  // the complex path must have a kernel at this size before anything is committed (as fdoct_set_dispersion_phase checks)
-  std::vector<float> old_phase = h->phase;
+  // the complex path must have a kernel at this size before anything is committed (as fdoct_set_dispersion_phase checks); the
+  // new plan leaves every device table to be rebuilt
+  PlanInputs in = plan_inputs(h);
+  in.phase = !phase.empty();
+  if (int rc = adopt_plan(h, in)) return rc;
   h->phase.swap(phase);
-  int rc = select_plan(h);
-  if (rc) {
-    const std::string msg = h->err;
-    h->phase.swap(old_phase);
-    (void)select_plan(h);
-    h->err = msg;
-    return rc;
-  }
   h->yb = std::move(yb);
   h->yp = std::move(yp);
   h->yd = std::move(yd);
@@ -1130,7 +1119,6 @@ int fdoct_import_state(fdoct_handle h, const void* buf, size_t len) try {
   h->idx.swap(idx);
   h->custom_win = (hdr[11] & 1) != 0;
   h->custom_table = (hdr[11] & 2) != 0;
-  h->dirty = true;
   return FDOCT_OK;
 } FDOCT_CATCH(h)
 

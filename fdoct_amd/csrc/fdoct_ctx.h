@@ -1,6 +1,6 @@
 // fdoct_ctx.h -- what the three translation units of the C-ABI layer share: the handle (fdoct_ctx), the error / device-scope /
 // device-memory helpers, and the declarations of
-//   fdoct_state.cpp   plan selection and everything a handle uploads to its device (tables, planes, twiddles)
+//   fdoct_state.cpp   the handle's plan (fdoct_plan.h) and everything a handle uploads to its device (tables, planes, twiddles)
 //   fdoct_route.cpp   the dispatch: choose_route, the passes in front of the chain, one launcher per kernel family, enqueue
 //   fdoct_capi.cpp    the extern "C" entry points of include/fdoct.h
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
@@ -106,31 +106,17 @@ struct fdoct_ctx {
   RefFrame yb, yp, yd;
   std::vector<float> phase;  // N (cos,sin) pairs or empty
   bool custom_win = false, custom_table = false, force_general = false, staged = false, bandpass = false;
-  bool dirty = true;
-
-  // derived plan
-  bool cplx = false;
-  int NC = 0;
-  FusedPlan plan{};
-  int split = 0, scratch_bytes = 0, tw_count = 0;
   int block_override = 0, grid_override = 0, plan_override = -1;  // plan_override == -2: force the generic path
-  bool use_generic = false;   // no specialised kernel for this configuration: fdoct_generic.hip runs it
-  bool generic_radix16 = false;  // ... its pass plans hold radix-16 butterflies (the 1024-thread kernels)
-  bool generic_inplace = false;  // ... with ONE DFT buffer in LDS (rows whose two ping-pong buffers do not fit: generic_kernel<1024, 1, true>)
-  bool generic_tables_ok = false;
-  std::vector<int> rad_n, rad_nh, rad_wh, rad_mwh, rad_blu;
-  // the zero-pad stage at full length inside generic_kernel (round 6: odd widths, half lengths with a prime factor above 5)
-  struct GenericDftPlan {
-    int n = 0, blu_m = 0;
-    std::vector<int> rad;   // of n, or of blu_m
-    DevBuf<float2> d_tw, d_chirp, d_bhat;
-  };
+
+  Plan plan;               // made for plan_inputs(this); replaced only by a plan made in full (adopt_plan)
+  unsigned tables_ok = 0;  // TABLES_* whose device tables match the host state (invalidate clears them all)
+
   DevBuf<unsigned> d_gen_tickets;   // kGenTickets row counters of generic_kernel launches, used round-robin (one per launch in flight)
   unsigned gen_ticket_seq = 0;
-  bool zp_full = false;
-  int zn = 0;               // W + 2 floor((M W - W) / 2)
-  GenericDftPlan gzf, gzi;  // the W-point and the zn-point +i transform
-  int blu_m = 0;  // > 0: the final transform (length N or N/2) has a prime factor > 5 and runs as Bluestein's chirp-z of this power-of-two length
+  struct GenericDftTables {
+    DevBuf<float2> tw, chirp, bhat;
+  };
+  GenericDftTables d_gzf, d_gzi;  // of plan.gen.gzf / gzi: the zero-pad stage at full length inside generic_kernel
   DevBuf<float2> d_blu_chirp, d_blu_bhat, d_twg_blu;
 
   // device state
@@ -155,7 +141,6 @@ struct fdoct_ctx {
   DevBuf<uint32_t> d_wave_gidx;
   DevBuf<float2> d_wave_tw;
   int wave_tw_count = 0, wave_off[6] = {0, 0, 0, 0, 0, 0};
-  bool wave_tables_ok = false;
   DevBuf<float2> d_twg_n, d_twg_nh, d_twg_w, d_twg_mw, d_twg_wh, d_twg_mwh;
   // long-row path (fdoct_big.hip): rows in HBM, one DFT plan per length
   struct BigGroupPlan {        // one launch: a group of the transform's passes with the data in LDS (fdoct_big.h)
@@ -269,24 +254,23 @@ int upload(fdoct_ctx* h, DevBuf<T>& d, const std::vector<T>& v) {
 inline void builtin_jet(unsigned char* bgr) { build_opencv_jet(bgr); }
 
 // ---- fdoct_state.cpp ------------------------------------------------------------------------------------------------------
+// Each family's device tables, built by its ensure_*_tables when they do not match the host state.
+enum : unsigned { TABLES_FUSED = 1, TABLES_GENERIC = 2, TABLES_WAVE = 4 };
+inline void invalidate(fdoct_ctx* h) { h->tables_ok = 0; }
 size_t dtype_size(int dt);
 int copy_ref_frame(fdoct_ctx* h, RefFrame& dst, const void* data, fdoct_dtype dtype, int rows, size_t pitch);
-bool factor_radices(int n, std::vector<int>& rad, int log2max = 0);
-bool generic_real_half(const fdoct_ctx* h);
-int generic_buffer_len(const fdoct_ctx* h);
-size_t generic_lds_bytes(const fdoct_ctx* h, int buffers = 0);
-int select_generic(fdoct_ctx* h);
-int select_plan(fdoct_ctx* h);
+PlanInputs plan_inputs(const fdoct_ctx* h);
+int adopt_plan(fdoct_ctx* h, const PlanInputs& in);
 size_t const_lds_bytes(const fdoct_ctx* h, bool planes, bool il_plane, bool il_half, bool tw3 = true, bool gi = true);
 size_t tro_const_lds_bytes(const fdoct_ctx* h, int sample_bytes, bool normalize);  // (of the launch: fused_tro_pf2 depends on both)
 void reciprocal_words(const std::vector<double>& yb, std::vector<float>& ib, std::vector<float>& il);
 struct PlaneScales { double yb, yp, yd; };
 PlaneScales plane_scales(const fdoct_ctx* h);
 std::vector<double> scaled_copy(const std::vector<double>& v, double s);
-int rebuild_device_state(fdoct_ctx* h);
 void build_bluestein_tables(int n, int Mb, std::vector<float2>& chirp, std::vector<float2>& bhat);
-int rebuild_generic_state(fdoct_ctx* h);
-int rebuild_wave_state(fdoct_ctx* h);
+int ensure_fused_tables(fdoct_ctx* h);
+int ensure_generic_tables(fdoct_ctx* h);  // (fails where the plan's generic path does: GenericPlan::rc)
+int ensure_wave_tables(fdoct_ctx* h);
 
 // ---- fdoct_route.cpp ------------------------------------------------------------------------------------------------------
 // ---- dispatch ----------------------------------------------------------------------------------------------------------

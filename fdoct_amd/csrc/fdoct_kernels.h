@@ -5,6 +5,8 @@
 
 #include <mutex>
 
+#include "fdoct_plan.h"
+
 #ifndef FDOCT_MAX_BLOCK
 #define FDOCT_MAX_BLOCK 768
 #endif
@@ -237,10 +239,6 @@ struct FusedArgs {
 };
 
 // Arguments of the any-configuration kernel (fdoct_generic.hip).  All pointers are device pointers.
-constexpr int GENERIC_MAX_PASSES = 16;
-#ifndef GENERIC_MAX_RADIX
-#define GENERIC_MAX_RADIX 8  // largest power-of-two butterfly of the generic kernel (8 or 16)
-#endif
 // One in-LDS +i DFT of any length for generic_kernel's full-length zero-pad stage: Stockham radices of the length itself
 // (blu_m == 0; tw = exp(+2 pi i j / n)) or, for a length with a prime factor above 5, Bluestein around two blu_m-point
 // transforms (radices and tw of blu_m; chirp[n], bhat[blu_m] as fdoct_state.cpp::build_bluestein_tables makes them).
@@ -329,12 +327,6 @@ hipError_t launch_display(const float* db, long long count, int nbscans, double 
 hipError_t launch_lockin_db(const float* bscan, const float* jscan, long long count, long long jcount, float* out,
                             hipStream_t st);
 
-struct FusedPlan {
-  int id, nc, T, R1, R2, R3, WCH, kind;
-};
-
-int fused_plan_count();
-bool fused_plan_get(int id, FusedPlan* p);
 // lean = the unpredicated fast-path kernel (see fused_kernel); the caller guarantees its conditions.
 hipError_t launch_fused(const FusedPlan& p, const FusedArgs& a, int dtype, bool cplx, bool lean, int grid,
                         int block, size_t lds, hipStream_t st);

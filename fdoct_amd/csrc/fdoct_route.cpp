@@ -332,8 +332,8 @@ int run_big(fdoct_ctx* h, const void* kframes, const float* kframes_lo, int kdt,
 // aligned outputs.
 bool fused_transposed_store_applies(const fdoct_ctx* h, fdoct_dtype dtype, const void* d_frames, size_t pitch_bytes,
                                     const float* d_out_bscan, const float* d_out_db, int nframes) {
-  if (!h->tro_enabled || h->use_generic || h->staged || h->force_general || h->cplx) return false;
-  const FusedPlan& p = h->plan;
+  if (!h->tro_enabled || !h->plan.fused || h->staged || h->force_general || h->plan.cplx) return false;
+  const FusedPlan& p = *h->plan.fused;
   if (!fused_tro_compiled(p.kind, p.T, p.WCH)) return false;
   if (dtype != FDOCT_U8 && dtype != FDOCT_U16) return false;
   if (h->fe_median > 0 || h->fe_binx > 1 || h->fe_biny > 1 || h->cfg.movavgn > 0) return false;
@@ -344,7 +344,7 @@ bool fused_transposed_store_applies(const fdoct_ctx* h, fdoct_dtype dtype, const
   const size_t es = dtype == FDOCT_U8 ? 1 : 2, valign = dtype == FDOCT_U8 ? 8 : 16;
   const size_t pitch = pitch_bytes ? pitch_bytes : es * (size_t)h->W;
   if (((uintptr_t)d_frames % valign) || (pitch % valign)) return false;
-  if ((h->H % 4) || (h->D % fused_tro_step_bins(64 / p.T)) || h->D > h->NC) return false;
+  if ((h->H % 4) || (h->D % fused_tro_step_bins(64 / p.T)) || h->D > h->plan.NC) return false;
   // (both words: a full-frame background brings its second word along with the prefetched row -- no LDS plane; a 1-row one needs
   // the plane next to the ring, which then holds one computing wave less)
   if (h->precise_div && h->yb.rows > 1 && !fused_il_half(true, p.WCH)) return false;
@@ -352,10 +352,10 @@ bool fused_transposed_store_applies(const fdoct_ctx* h, fdoct_dtype dtype, const
   if (rpw == 4) {
     // four rows per wave: no ring -- groups of four waves own tiles and write them out from their own row buffers (fused_kernel,
     // TRO_INPLACE): at least one group must fit, and a launch override must leave whole groups
-    if ((size_t)160 * 1024 - 64 < tro_const_lds_bytes(h, (int)es, normalize) + (size_t)fused_tro_group_waves() * h->scratch_bytes * rpw) return false;
-    if (fused_max_block(h->NC, p.T, true, p.kind) / 64 < fused_tro_group_waves()) return false;
+    if ((size_t)160 * 1024 - 64 < tro_const_lds_bytes(h, (int)es, normalize) + (size_t)fused_tro_group_waves() * h->plan.scratch_bytes * rpw) return false;
+    if (fused_max_block(h->plan.NC, p.T, true, p.kind) / 64 < fused_tro_group_waves()) return false;
     if (h->block_override && h->block_override / 64 < fused_tro_group_waves()) return false;
-  } else if (fused_tro_ring_pick((size_t)160 * 1024 - 64 - tro_const_lds_bytes(h, (int)es, normalize) - (size_t)h->scratch_bytes * rpw, h->D, rpw) == 0) {
+  } else if (fused_tro_ring_pick((size_t)160 * 1024 - 64 - tro_const_lds_bytes(h, (int)es, normalize) - (size_t)h->plan.scratch_bytes * rpw, h->D, rpw) == 0) {
     return false;  // (no ring next to one computing wave)
   }
   if (((uintptr_t)d_out_bscan % 16) || ((uintptr_t)d_out_db % 16)) return false;
@@ -370,7 +370,7 @@ bool fused_transposed_store_applies(const fdoct_ctx* h, fdoct_dtype dtype, const
 int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
                  uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r) {
   int rc;
-  if (h->dirty && (rc = rebuild_device_state(h))) return rc;
+  if ((rc = h->plan.fused ? ensure_fused_tables(h) : ensure_generic_tables(h))) return rc;
   if (h->D > h->N) return fail(h, FDOCT_ERR_INVALID, "numdisplaypoints > numfftpoints");
   const int W = h->W, H = h->H, D = h->D, A = h->A;
   const long long out_rows = (long long)(nframes / A) * H;
@@ -388,25 +388,15 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
                        (h->bandpass && h->M > 1 ? FDOCT_WAVE_OPT_BANDPASS : 0) | (h->cfg.rowwisenormalize ? FDOCT_WAVE_OPT_ROWNORM : 0) |
                        (r->need_minmax ? FDOCT_WAVE_OPT_FRAMENORM : 0) | (!h->phase.empty() ? FDOCT_WAVE_OPT_CPLX : 0) |
                        (h->phase.empty() && D > h->N / 2 ? FDOCT_WAVE_OPT_DEEP : 0);
-  auto wave_tables = [&]() -> int {  // (the wave tables read the resample table's device copies)
-    if (!h->generic_tables_ok) {
-      const bool keep = h->use_generic;
-      int rc2 = select_generic(h);
-      h->use_generic = keep;
-      if (rc2) return rc2;
-      if ((rc2 = rebuild_generic_state(h))) return rc2;
-    }
-    return h->wave_tables_ok ? FDOCT_OK : rebuild_wave_state(h);
-  };
   // 2 x 2 binning with nothing else in front of the chain, on a configuration the wave-per-row kernel takes: the kernel compiled
   // for the handle does the binning in its own loads (FDOCT_WAVE_OPT_BIN2) and the pass over the raw frames is skipped.
   // (Measured on the shipped shapes, tools/bench_generic.py with and without FDOCT_JIT=0: + 4.5 % on 160-sample 8-bit rows, + 5 % on
   // 640-sample 16-bit rows, - 1 % on 640-sample 8-bit rows -- twenty 2-byte loads per lane cost what the pass saves: those keep the pass.)
   if (h->fe_median == 0 && h->fe_binx == 2 && h->fe_biny == 2 && (dtype == FDOCT_U16 || (dtype == FDOCT_U8 && W <= 320)) && h->cfg.movavgn == 0 &&
-      h->jit && h->use_generic && !h->use_big && h->plan_override > -2 && h->phase.empty() && D <= h->N / 2 && !r->need_minmax &&
+      h->jit && !h->plan.fused && !h->plan.gen.use_big && h->plan_override > -2 && h->phase.empty() && D <= h->N / 2 && !r->need_minmax &&
       (frames_addr % 4 == 0) && (pitch_bytes % 4 == 0) && pitch_bytes >= es * 2 * (size_t)W && out_rows < 0x7fffffffLL &&
       wave_jit_shape_ok(W, h->M, h->N, D)) {
-    if ((rc = wave_tables())) return rc;
+    if ((rc = ensure_wave_tables(h))) return rc;
     const size_t shared = wave_shared_lds_bytes(h->wave_tw_count, W, h->M, h->N, h->yb.rows > 1);
     std::string why;
     hipFunction_t fn = nullptr;
@@ -451,14 +441,8 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
   // the specialised kernels read 16-byte vectors; anything else goes through the generic kernel
   const size_t valign = (kdt == FDOCT_K_U8) ? 8 : 16;
   const bool misaligned = (kaddr % valign) || (kpitch % valign);
-  const bool run_generic = h->use_generic || misaligned;
-  if (run_generic && !h->generic_tables_ok) {
-    const bool keep = h->use_generic;
-    rc = select_generic(h);
-    h->use_generic = keep;
-    if (rc) return rc;
-    if ((rc = rebuild_generic_state(h))) return rc;
-  }
+  const bool run_generic = !h->plan.fused || misaligned;
+  if (run_generic && (rc = ensure_generic_tables(h))) return rc;
   if (run_generic && h->staged) return fail(h, FDOCT_ERR_UNSUPPORTED, "staged mode needs a specialised kernel for this configuration");
 
   const bool transposed = layout == FDOCT_LAYOUT_TRANSPOSED_DxH;
@@ -469,7 +453,7 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
 
   // the acquisition configurations the reference ships: one wave per A-scan (fdoct_wave.hip) instead of one workgroup
   // (frames handed over as doubles carry a low word per sample: the fused any-option, workgroup-per-row and long-row kernels take it)
-  const bool wave_scope = run_generic && !h->use_big && h->plan_override > -2 && kdt >= 0 && !r->narrow_f64 && !r->mov_lo &&
+  const bool wave_scope = run_generic && !h->plan.gen.use_big && h->plan_override > -2 && kdt >= 0 && !r->narrow_f64 && !r->mov_lo &&
                           (kaddr % 4 == 0) && (kpitch % 4 == 0) && out_rows < 0x7fffffffLL;
   if (r->bin2_in_kernel && !wave_scope) return fail(h, FDOCT_ERR_DEVICE, "internal: binning left to a kernel that does not run");
   bool run_wave = r->bin2_in_kernel;
@@ -490,7 +474,7 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
     run_wave = wave_builtin || r->jit_fn;
   }
   if (run_wave) {
-    if ((rc = wave_tables())) return rc;
+    if ((rc = ensure_wave_tables(h))) return rc;
     const size_t shared = wave_shared_lds_bytes(h->wave_tw_count, W, h->M, h->N, h->yb.rows > 1, r->wave_opt);
     if (shared + wave_private_lds_bytes(W, h->M, h->N, r->wave_opt) > 160 * 1024 - 64) {  // not even one wave's buffer next to the tables
       if (r->bin2_in_kernel) return fail(h, FDOCT_ERR_DEVICE, "internal: binning left to a kernel that did not launch");
@@ -501,9 +485,9 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
   if (run_wave)
     r->family = r->jit_fn ? FDOCT_KERNEL_WAVE_JIT : FDOCT_KERNEL_WAVE;
   else if (run_generic) {
-    r->family = h->use_big ? FDOCT_KERNEL_LONG_ROWS : FDOCT_KERNEL_GENERIC;
+    r->family = h->plan.gen.use_big ? FDOCT_KERNEL_LONG_ROWS : FDOCT_KERNEL_GENERIC;
     // the cliff an integrator should see: rows in HBM run an order of magnitude below their LDS-resident neighbours
-    if (h->use_big)
+    if (h->plan.gen.use_big)
       h->jit_note = "this geometry runs on the long-row path (rows in HBM, fdoct_big.hip: one launch per group of DFT passes): its transforms do not fit "
                     "the 160 KB of LDS of a compute unit; expect 1e6 ... 1e7 A-scans/s where LDS-resident rows reach 1e8";
   }
@@ -621,6 +605,8 @@ int launch_family_long_rows(fdoct_ctx* h, const Route& r, const Call& c) {
 
 int launch_family_generic(fdoct_ctx* h, const Route& r, const Call& c) {
   const int W = h->W, H = h->H, D = h->D, A = h->A;
+  const PlanInputs in = plan_inputs(h);
+  const GenericPlan& gp = h->plan.gen;
   GenericArgs ga{};
   ga.frames = c.kframes;
   ga.frames_lo = c.kframes_lo;
@@ -628,8 +614,8 @@ int launch_family_generic(fdoct_ctx* h, const Route& r, const Call& c) {
   ga.total_out_rows = c.out_rows;
   ga.dtype = r.kdt;
   ga.W = W; ga.H = H; ga.N = h->N; ga.D = D; ga.M = h->M; ga.A = A;
-  ga.L = generic_buffer_len(h);
-  ga.real_half = generic_real_half(h) ? 1 : 0;
+  ga.L = generic_buffer_len(in, gp);
+  ga.real_half = generic_real_half(in) ? 1 : 0;
   ga.ybuf_len = (W + 3) & ~3;
   ga.ib = h->yb.rows == 1 ? h->d_ib : h->d_ib2d;
   ga.il = h->yb.rows == 1 ? h->d_il : h->d_il2d;
@@ -653,38 +639,38 @@ int launch_family_generic(fdoct_ctx* h, const Route& r, const Call& c) {
       ns *= (unsigned)rad[i];
     }
   };
-  put_plan(h->rad_n, ga.rad_n, ga.mag_n);
-  if (ga.real_half) put_plan(h->rad_nh, ga.rad_nh, ga.mag_nh);
-  ga.npass_nh = (int)h->rad_nh.size();
-  put_plan(h->rad_wh, ga.rad_wh, ga.mag_wh);
-  put_plan(h->rad_mwh, ga.rad_mwh, ga.mag_mwh);
-  ga.npass_n = (int)h->rad_n.size(); ga.npass_wh = (int)h->rad_wh.size(); ga.npass_mwh = (int)h->rad_mwh.size();
-  ga.blu_m = h->blu_m;
-  if (h->blu_m) {
-    put_plan(h->rad_blu, ga.rad_blu, ga.mag_blu);
-    ga.npass_blu = (int)h->rad_blu.size();
+  put_plan(gp.rad_n, ga.rad_n, ga.mag_n);
+  if (ga.real_half) put_plan(gp.rad_nh, ga.rad_nh, ga.mag_nh);
+  ga.npass_nh = (int)gp.rad_nh.size();
+  put_plan(gp.rad_wh, ga.rad_wh, ga.mag_wh);
+  put_plan(gp.rad_mwh, ga.rad_mwh, ga.mag_mwh);
+  ga.npass_n = (int)gp.rad_n.size(); ga.npass_wh = (int)gp.rad_wh.size(); ga.npass_mwh = (int)gp.rad_mwh.size();
+  ga.blu_m = gp.blu_m;
+  if (gp.blu_m) {
+    put_plan(gp.rad_blu, ga.rad_blu, ga.mag_blu);
+    ga.npass_blu = (int)gp.rad_blu.size();
     ga.blu_chirp = h->d_blu_chirp;
     ga.blu_bhat = h->d_blu_bhat;
     ga.tw_blu = h->d_twg_blu;
   }
-  ga.zp_full = (h->M > 1 && h->zp_full) ? 1 : 0;
-  ga.zn = h->zn;
+  ga.zp_full = (h->M > 1 && gp.zp_full) ? 1 : 0;
+  ga.zn = gp.zn;
   if (ga.zp_full) {
-    auto put_dft = [&](const fdoct_ctx::GenericDftPlan& p, GenericDft& d) {
+    auto put_dft = [&](const GenericDftPlan& p, const fdoct_ctx::GenericDftTables& t, GenericDft& d) {
       d.n = p.n;
       d.blu_m = p.blu_m;
       d.npass = (int)p.rad.size();
       put_plan(p.rad, d.rad, d.mag);
-      d.tw = p.d_tw;
-      d.chirp = p.d_chirp;
-      d.bhat = p.d_bhat;
+      d.tw = t.tw;
+      d.chirp = t.chirp;
+      d.bhat = t.bhat;
     };
-    put_dft(h->gzf, ga.zf);
-    put_dft(h->gzi, ga.zi);
+    put_dft(gp.gzf, h->d_gzf, ga.zf);
+    put_dft(gp.gzi, h->d_gzi, ga.zi);
   }
   ga.bandpass = h->bandpass ? 1 : 0;
-  ga.inplace = h->generic_inplace ? 1 : 0;
-  ga.radix16 = h->generic_radix16 ? 1 : 0;
+  ga.inplace = gp.inplace ? 1 : 0;
+  ga.radix16 = gp.radix16 ? 1 : 0;
   ga.rowwisenormalize = h->cfg.rowwisenormalize;
   ga.dcmask = h->cfg.dc_mask;
   ga.inv_A = (float)(1.0 / (double)A);
@@ -697,13 +683,13 @@ int launch_family_generic(fdoct_ctx* h, const Route& r, const Call& c) {
     // synchronisation; 64 launches of one handle are never in flight together)
     constexpr unsigned kGenTickets = 64;
     static const bool no_tickets = [] { const char* e = std::getenv("FDOCT_GENERIC_TICKETS"); return e && std::atoi(e) == 0; }();  // measurement: the static stride
-    if (h->d_gen_tickets && !no_tickets) {   // (allocated with the kernel's tables: rebuild_generic_state)
+    if (h->d_gen_tickets && !no_tickets) {   // (allocated with the kernel's tables: ensure_generic_tables)
       unsigned* t = h->d_gen_tickets + (h->gen_ticket_seq++ % kGenTickets);
       HIP_TRY(h, hipMemsetAsync(t, 0, sizeof(unsigned), c.st));
       ga.row_ticket = t;
     }
   }
-  const size_t glds = generic_lds_bytes(h);
+  const size_t glds = generic_lds_bytes(in, gp);
   int per_cu = (int)((160 * 1024 - 1024) / glds);
   if (per_cu > 6) per_cu = 6;  // generic_kernel is compiled for 6 waves per SIMD = 6 workgroups of 4 waves per CU
   if (per_cu < 1) per_cu = 1;
@@ -804,9 +790,9 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
   a.H = H;
   a.D = D;
   a.A = A;
-  a.split = h->split;
-  a.scratch_bytes = h->scratch_bytes;
-  a.tw_count = h->tw_count;
+  a.split = h->plan.split;
+  a.scratch_bytes = h->plan.scratch_bytes;
+  a.tw_count = h->plan.tw_count;
   a.ib = h->d_ib;
   a.ib2d = h->d_ib2d_f;
   a.il = h->d_il;
@@ -837,7 +823,9 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
   dev_build_hooks(a, st);
 #endif
 
-  const FusedPlan& p = h->plan;
+  const FusedPlan& p = *h->plan.fused;
+  const bool cplx = h->plan.cplx;
+  const int NC = h->plan.NC, scratch_bytes = h->plan.scratch_bytes;
   // the unpredicated fast-path kernel applies to the plain acquisition configuration
   // (a full-frame background keeps the fast path on the row-swap plan: its resident registers prefetch the frame row)
   const bool fast_opts = fused_resident_consts(p.kind, true, A > 1, p.WCH, 0) && c.out_rows < 0x7fffffffLL && !h->staged;
@@ -861,11 +849,11 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
   if (a.prec == 1 && fused_il_global(lean, A > 1 && !h->staged, p.WCH, p.T)) a.prec = 3;
   const size_t lds_const = const_lds_bytes(h, a.lds_planes != 0, a.prec == 1, fused_il_half(lean, p.WCH));
   const size_t lds_max = 160 * 1024 - 64;  // the kernel's static row-ticket counter lives in LDS too
-  const int max_block = fused_max_block(h->NC, p.T, lean, p.kind);
+  const int max_block = fused_max_block(NC, p.T, lean, p.kind);
   int max_waves = max_block / 64;
   // (a full-frame background with both words: every wave has a slot for the prefetched pattern row of its next A-scan)
   const size_t dma_per_wave = fused_il16_dma_bytes(lean && h->yb.rows > 1, a.prec == 2 && fused_il_half(lean, p.WCH), r.tro, 8 * p.T * p.WCH);
-  const size_t per_wave = (size_t)h->scratch_bytes * rpw + dma_per_wave;
+  const size_t per_wave = (size_t)scratch_bytes * rpw + dma_per_wave;
   int waves = (int)((lds_max - lds_const) / per_wave);
   if (waves > max_waves) waves = max_waves;
   if (h->block_override) {
@@ -901,12 +889,12 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
     if (rpw == 4) {
       // whole groups of four waves, as many as registers and LDS allow; no ring (the rows wait in the waves' own buffers)
       constexpr int GW = fused_tro_group_waves();
-      while (cw >= GW && tro_const + (size_t)cw * h->scratch_bytes * rpw > lds_max) cw--;
+      while (cw >= GW && tro_const + (size_t)cw * scratch_bytes * rpw > lds_max) cw--;
       cw = cw / GW * GW;
       if (cw < GW) return fail(h, FDOCT_ERR_DEVICE, "internal: no group of waves fits the LDS (transposed store, four rows per wave)");
     } else {
       for (; cw >= 1; cw--) {
-        slots = fused_tro_ring_pick(lds_max - tro_const - (size_t)cw * h->scratch_bytes * rpw, D, rpw);
+        slots = fused_tro_ring_pick(lds_max - tro_const - (size_t)cw * scratch_bytes * rpw, D, rpw);
         if (slots) break;
       }
       if (cw < 1 || !slots) return fail(h, FDOCT_ERR_DEVICE, "internal: no LDS left for the transposed store's ring");
@@ -915,7 +903,7 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
     const size_t ring = (size_t)slots * (size_t)(D + 4) * 4;
     a.tr_ring = slots;
     block_launch = (cw + ww) * 64;
-    lds_launch = tro_const + (size_t)cw * h->scratch_bytes * rpw + ring;
+    lds_launch = tro_const + (size_t)cw * scratch_bytes * rpw + ring;
     const unsigned tile_rows = (unsigned)fused_tro_tile_rows(rpw);
     const unsigned tpf = (unsigned)((H + tile_rows - 1) / tile_rows);
     const long long tiles = (long long)c.G * tpf;
@@ -941,7 +929,7 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
       return fail(h, FDOCT_ERR_UNSUPPORTED, "staged mode is built for the plain u16 acquisition configuration only");
     // one k-linear row per INPUT A-scan between the stages: the resample stage runs over the in_rows input rows as they
     // lie (A = 1), the FFT stage gathers the A rows of an output A-scan
-    if ((rc = h->ws_ylin.reserve(h, (size_t)c.in_rows * h->NC * sizeof(float2)))) return rc;
+    if ((rc = h->ws_ylin.reserve(h, (size_t)c.in_rows * NC * sizeof(float2)))) return rc;
     a.ylin = h->ws_ylin;
     h->ylin_rows = c.in_rows;
     {
@@ -953,14 +941,14 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
       long long need1 = (c.in_rows + (long long)waves * rpw - 1) / ((long long)waves * rpw);
       long long grid1 = h->grid_override > 0 ? h->grid_override : (long long)h->num_cu * bpc;
       if (grid1 > need1) grid1 = need1;
-      HIP_TRY(h, launch_fused(p, a1, r.kdt, h->cplx, lean, (int)grid1, waves * 64, lds, st));
+      HIP_TRY(h, launch_fused(p, a1, r.kdt, cplx, lean, (int)grid1, waves * 64, lds, st));
     }
     if (h->record_now) HIP_TRY(h, hipEventRecord(h->ev[4], st));
     a.stage = 2;
-    HIP_TRY(h, launch_fused(p, a, r.kdt, h->cplx, lean, (int)grid, waves * 64, lds, st));
+    HIP_TRY(h, launch_fused(p, a, r.kdt, cplx, lean, (int)grid, waves * 64, lds, st));
   } else {
     h->ylin_rows = 0;
-    HIP_TRY(h, launch_fused(p, a, r.kdt, h->cplx, lean, (int)grid, block_launch, lds_launch, st));
+    HIP_TRY(h, launch_fused(p, a, r.kdt, cplx, lean, (int)grid, block_launch, lds_launch, st));
   }
   return finish_launch(h, r, c, h->staged);
 }
@@ -1083,12 +1071,8 @@ int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, 
   long long cg = per_group ? (long long)(h->tr_chunk_bytes / per_group) : G;
   if (cg < 1) cg = 1;
   if (G <= cg) return enqueue_one(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
-  if (h->yb.rows) {  // (without a background enqueue_one reports the error)
-    int rc;
-    if (h->dirty && (rc = rebuild_device_state(h))) return rc;
-    if (fused_transposed_store_applies(h, dtype, d_frames, pitch_bytes, d_out_bscan, d_out_db, nframes))  // no intermediate at all
-      return enqueue_one(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
-  }
+  if (fused_transposed_store_applies(h, dtype, d_frames, pitch_bytes, d_out_bscan, d_out_db, nframes))  // no intermediate at all
+    return enqueue_one(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
   const size_t es = dtype_size(dtype);
   if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
   const size_t pitch = pitch_bytes ? pitch_bytes : es * (size_t)h->W * h->fe_binx;

@@ -1,7 +1,7 @@
-// fdoct_state.cpp -- plan selection and the device state of a handle: which kernel family a configuration takes
-// (select_plan / select_generic), and everything the kernels read that is built on the host in double and uploaded once per
-// change of the handle's state (reciprocal words of the background and their half-float pattern, window and slope planes,
-// gather tables, twiddles, Bluestein chirps).  Part of the C-ABI layer (fdoct_ctx.h); no CPU compute path.
+// fdoct_state.cpp -- the plan and the device state of a handle: the plan it adopts (fdoct_plan.h makes it), and everything the
+// kernels read that is built on the host in double and uploaded once per change of the handle's state (reciprocal words of the
+// background and their half-float pattern, window and slope planes, gather tables, twiddles, Bluestein chirps).  Part of the
+// C-ABI layer (fdoct_ctx.h); no CPU compute path.
 #include "fdoct_ctx.h"
 
 namespace fdoct_impl {
@@ -20,7 +20,7 @@ int copy_ref_frame(fdoct_ctx* h, RefFrame& dst, const void* data, fdoct_dtype dt
   if (!data) {
     dst.v.clear();
     dst.rows = 0;
-    h->dirty = true;
+    invalidate(h);
     return FDOCT_OK;
   }
   const size_t es = dtype_size(dtype);
@@ -42,226 +42,22 @@ int copy_ref_frame(fdoct_ctx* h, RefFrame& dst, const void* data, fdoct_dtype dt
     }
   }
   dst.rows = rows;
-  h->dirty = true;
+  invalidate(h);
   return FDOCT_OK;
 }
 
-bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
-
-// n = 2^a 3^b 5^c -> Stockham radices (4s first), false if another prime divides n
-// Radix plan of the generic kernel's Stockham DFT (radices 16/8/4/2/5/3).  The first pass writes butterfly j's
-// outputs R apart (stride R*8 bytes across lanes), so it gets an odd radix -- or a small power of two -- to keep
-// those LDS writes off the same banks; it is also the pass without twiddle multiplies.
-bool factor_radices(int n, std::vector<int>& rad, int log2max) {
-  rad.clear();
-  int a = 0, b = 0, c = 0;
-  while (n % 2 == 0) { a++; n /= 2; }
-  while (n % 3 == 0) { b++; n /= 3; }
-  while (n % 5 == 0) { c++; n /= 5; }
-  if (n != 1) return false;
-  for (int i = 0; i < c; i++) rad.push_back(5);
-  for (int i = 0; i < b; i++) rad.push_back(3);
-  if (rad.empty() && a > 0) {
-    const int first = (a % 2) ? 1 : 2;
-    rad.push_back(1 << first);
-    a -= first;
-  }
-  const int kLog2Max = log2max ? log2max : (GENERIC_MAX_RADIX >= 16 ? 4 : 3);
-  for (; a >= kLog2Max; a -= kLog2Max) rad.push_back(1 << kLog2Max);
-  if (a) rad.push_back(1 << a);
-  return (int)rad.size() <= GENERIC_MAX_PASSES;
+PlanInputs plan_inputs(const fdoct_ctx* h) {
+  return {h->W, h->M, h->N, h->D, !h->phase.empty(), h->plan_override, h->force_general};
 }
 
-// real rows run the N-point DFT as an N/2-point complex one (see generic_kernel)
-bool generic_real_half(const fdoct_ctx* h) { return h->phase.empty() && (h->N % 2) == 0; }
-
-int generic_buffer_len(const fdoct_ctx* h) {
-  const int MW = h->W * h->M;
-  int L = generic_real_half(h) ? h->N / 2 : h->N;
-  if (h->M > 1) L = std::max(L, MW / 2);  // the zero-pad DFTs run at half length (real row, Hermitian spectrum)
-  if (h->blu_m > L) L = h->blu_m;         // Bluestein: the transform runs as two power-of-two DFTs of this length
-  if (h->M > 1 && h->zp_full) {           // the zero-pad stage at full length: both transforms, and the upsampled row as floats
-    L = std::max(L, std::max(h->gzf.blu_m ? h->gzf.blu_m : h->W, h->gzi.blu_m ? h->gzi.blu_m : h->zn));
-    L = std::max(L, (MW + 1) / 2);
-  }
-  return L;
-}
-
-size_t generic_lds_bytes(const fdoct_ctx* h, int buffers) {
-  const int L = generic_buffer_len(h);
-  const int ybuf = (h->W + 3) & ~3;
-  if (!buffers) buffers = h->generic_inplace ? 1 : 2;
-  return (size_t)ybuf * 4 + (size_t)L * 8 * buffers + (size_t)((h->D + 3) & ~3) * 4;  // row, the DFT buffer(s), magnitude sums
-}
-
-// The any-configuration path: checks that fdoct_generic.hip can run this geometry.
-int select_generic(fdoct_ctx* h) {
-  const int MW = h->W * h->M;
-  // cv::dft takes any length (main:1185).  Lengths with prime factors up to 5 run as mixed-radix Stockham passes; any
-  // other length as Bluestein's algorithm: two power-of-two DFTs of length >= 2n - 1 around a chirp multiplication.
-  h->blu_m = 0;
-  const int tlen = generic_real_half(h) ? h->N / 2 : h->N;  // the transform the kernel actually runs
-  std::vector<int> probe;
-  if (!factor_radices(tlen, probe)) {
-    int mb = 1;
-    while (mb < 2 * tlen - 1) mb <<= 1;
-    // (round 6: the smallest length 2^a 3^b 5^c >= 2n - 1 where the host can afford the transformed chirp by the DFT's definition:
-    // 1296 instead of 2048 around a 642-point transform)
-    if (2 * tlen - 1 <= 8192) {
-      for (int c = 2 * tlen - 1; c < mb; c++) {
-        int m = c;
-        for (int f : {2, 3, 5})
-          while (m % f == 0) m /= f;
-        std::vector<int> tmp;
-        if (m == 1 && factor_radices(c, tmp)) {
-          mb = c;
-          break;
-        }
-      }
-    }
-    h->blu_m = mb;
-    factor_radices(mb, h->rad_blu);
-    h->rad_n.clear();
-    h->rad_nh.clear();
-  } else {
-    if (!factor_radices(h->N, h->rad_n)) h->rad_n.clear();  // (only used when the full-length transform runs)
-    if ((h->N % 2) == 0 && !factor_radices(h->N / 2, h->rad_nh)) h->rad_nh.clear();
-  }
-  h->use_big = false;
-  if (h->M > 1) {
-    // an odd width (the reference's fftshift leaves the last column of the spectrum where it is and, under an even multiplier,
-    // pads to M W - 1 bins, main:215-241) and zero-pad lengths with a prime factor above 5: the long-row path, whose DFTs run at
-    // full length and take any length (the LDS kernels halve the transforms of a real row, which needs an even width)
-    h->zp_full = false;
-    if ((h->W % 2) || !factor_radices(h->W / 2, h->rad_wh) || !factor_radices(MW / 2, h->rad_mwh)) {
-      h->rad_wh.clear();
-      h->rad_mwh.clear();
-      // Round 6: such a row stays in LDS when two buffers of its full-length transforms fit -- the W-point and the padded
-      // spectrum's zn-point +i transforms inside generic_kernel (Stockham passes, or Bluestein around a power of two: 321 x 4 ->
-      // 1283 points, a prime, runs around 4096) -- and leaves for HBM only when they do not.
-      h->zn = h->W + 2 * ((MW - h->W) / 2);
-      auto plan = [](int n, fdoct_ctx::GenericDftPlan& p) {
-        p.n = n;
-        p.blu_m = 0;
-        if (!factor_radices(n, p.rad)) {
-          // Bluestein around the smallest length 2^a 3^b 5^c >= 2n - 1 (the convolution only needs that much room; the passes
-          // take radices 2, 3, 4, 5, 8): 2592 for a 1283-point transform where the next power of two is 4096
-          int mb = 2 * n - 1;
-          for (;; mb++) {
-            int m = mb;
-            for (int f : {2, 3, 5})
-              while (m % f == 0) m /= f;
-            if (m == 1 && factor_radices(mb, p.rad)) break;
-            if (mb > 4 * n) return false;
-          }
-          p.blu_m = mb;
-          return mb <= 8192;   // (the host builds the transformed chirp by the DFT's definition: bounded work)
-        }
-        return true;
-      };
-      h->zp_full = plan(h->W, h->gzf) && plan(h->zn, h->gzi);
-      if (h->zp_full && generic_lds_bytes(h, 2) + 1024 > 160 * 1024) h->zp_full = false;
-      static const bool no_full = [] { const char* e = std::getenv("FDOCT_NO_ZP_FULL"); return e && std::atoi(e) != 0; }();  // measurement: round 5's route
-      if (no_full) h->zp_full = false;
-      if (!h->zp_full) h->use_big = true;
-    }
-  } else {
-    h->zp_full = false;
-  }
-  // rows whose two DFT buffers do not fit the 160 KB of LDS (half-length transforms beyond about 9000 points): with ONE buffer and
-  // every step in place (generic_kernel<1024, 1, true>) up to 16384 points -- 4096 samples upsampled x8 -- as long as a thread of
-  // the 1024 holds its share of a pass in 16 registers (radices 5 / 3: 15), the zero-pad spectrum in 8 and the resampled row
-  // in 32, and the length needs no Bluestein; what lies beyond runs with the rows in HBM (fdoct_big.hip)
-  h->generic_inplace = false;
-  // (FDOCT_GENERIC_INPLACE_ABOVE: the two-buffer footprint above which the one-buffer kernel is taken, for measurements)
-  static const size_t inplace_above = [] { const char* e = std::getenv("FDOCT_GENERIC_INPLACE_ABOVE"); return e ? (size_t)std::atol(e) : (size_t)160 * 1024; }();
-  const bool must_inplace = generic_lds_bytes(h, 2) + 1024 > 160 * 1024;
-  if (!h->zp_full && generic_lds_bytes(h, 2) + 1024 > inplace_above) {
-    auto pass_ok = [](const std::vector<int>& rad, int n) {
-      for (int R : rad)
-        if (R > 16 || n / R > 1024 * (16 / R)) return false;
-      return !rad.empty();
-    };
-    const bool real_half = generic_real_half(h);
-    // (the in-place passes take radix-16 butterflies -- one per thread on a 16384-point transform -- and with them a pass less)
-    std::vector<int> r_n = h->rad_n, r_nh = h->rad_nh, r_wh = h->rad_wh, r_mwh = h->rad_mwh;
-    if (!h->blu_m && !h->use_big) {
-      if (!h->rad_n.empty()) factor_radices(h->N, h->rad_n, 4);
-      if (!h->rad_nh.empty()) factor_radices(h->N / 2, h->rad_nh, 4);
-      if (h->M > 1) {
-        factor_radices(h->W / 2, h->rad_wh, 4);
-        factor_radices(MW / 2, h->rad_mwh, 4);
-      }
-    }
-    const bool ok = !h->use_big && !h->blu_m && generic_lds_bytes(h, 1) + 1024 <= 160 * 1024 && h->N <= 32 * 1024 &&
-                    (real_half ? pass_ok(h->rad_nh, h->N / 2) : pass_ok(h->rad_n, h->N)) &&
-                    (h->M == 1 || (h->W / 2 <= 8 * 1024 && pass_ok(h->rad_wh, h->W / 2) && pass_ok(h->rad_mwh, MW / 2)));
-    if (ok) {
-      h->generic_inplace = true;
-    } else {
-      if (must_inplace) h->use_big = true;
-      h->rad_n = r_n; h->rad_nh = r_nh; h->rad_wh = r_wh; h->rad_mwh = r_mwh;
-    }
-  }
-  // rows of which a CU holds one (two buffers beyond half the LDS) run with 1024 threads, 128 registers each: radix-16 passes there too
-  h->generic_radix16 = h->generic_inplace;
-  {
-    static const int r16 = [] { const char* e = std::getenv("FDOCT_GENERIC_RADIX16"); return e ? std::atoi(e) : 1; }();  // measurement
-    if (r16 && !h->generic_inplace && !h->use_big && !h->blu_m && !h->zp_full && generic_lds_bytes(h, 2) > (160 * 1024 - 1024) / 2) {
-      if (!h->rad_n.empty()) factor_radices(h->N, h->rad_n, 4);
-      if (!h->rad_nh.empty()) factor_radices(h->N / 2, h->rad_nh, 4);
-      if (h->M > 1) {
-        factor_radices(h->W / 2, h->rad_wh, 4);
-        factor_radices(MW / 2, h->rad_mwh, 4);
-      }
-      h->generic_radix16 = true;
-    }
-  }
-  {
-    static const int force = [] { const char* e = std::getenv("FDOCT_FORCE_LONG_ROWS"); return e ? std::atoi(e) : 0; }();  // measurement
-    if (force || h->plan_override == -3) h->use_big = true, h->generic_inplace = false, h->zp_full = false;   // (-3: fdoct_set_plan's "rows in HBM")
-  }
-  if (h->use_big && (h->N > (1 << 24) || MW > (1 << 24)))
-    return fail(h, FDOCT_ERR_UNSUPPORTED, "rows of more than 2^24 points");
-  h->use_generic = true;
-  return FDOCT_OK;
-}
-
-// Pick the compiled plan for the current (N, W, phase) and derive LDS geometry; configurations without a
-// specialised kernel go to the generic path.
-int select_plan(fdoct_ctx* h) {
-  h->cplx = !h->phase.empty();
-  h->use_generic = false;
-  h->NC = h->cplx ? h->N : h->N / 2;
-  const bool special_ok = is_pow2(h->N) && h->M == 1 && (h->W % 8) == 0 && (h->cplx || h->D <= h->N / 2) &&
-                          h->plan_override > -2;
-  bool found = false;
-  // preference order for equal NC: the override, then the measured-fastest plan ids
-  static const int pref[] = {5, 2, 3, 0, 1, 7, 6, 8, 4};  // per NC: fastest first; equal plans: smallest chunk count that holds W
-  FusedPlan q{};
-  if (special_ok && h->plan_override >= 0 && fused_plan_get(h->plan_override, &q) && q.nc == h->NC && h->W <= 8 * q.T * q.WCH) {
-    h->plan = q;
-    found = true;
-  }
-  for (int i = 0; special_ok && !found && i < (int)(sizeof pref / sizeof pref[0]); i++) {
-    if (fused_plan_get(pref[i], &q) && q.nc == h->NC && h->W <= 8 * q.T * q.WCH) {
-      h->plan = q;
-      found = true;
-    }
-  }
-  if (!found) return select_generic(h);
-  const FusedPlan& p = h->plan;
-  const int WC = 8 * p.T * p.WCH;
-  const int LP = p.R1 == 32 ? 5 : p.R1 == 16 ? 4 : p.R1 == 8 ? 3 : 2;
-  const int stg = 4 * (WC + 4);
-  const int xch = p.kind == 1 ? 8 * (65 * 16 + 2) : p.kind == 2 ? 8 * (129 * 16 + 2) : 8 * (h->NC + (h->NC >> LP) + 2);
-  h->scratch_bytes = ((stg > xch ? stg : xch) + 15) & ~15;
-  const double sigma = (h->cplx ? 1.0 : 2.0) * (double)(h->W * h->M) / (double)h->N;
-  h->split = (sigma >= 1.5 && sigma <= 3.0) ? 1 : 0;
-  int tw = (p.R2 - 1) * p.R1 + (p.R3 > 1 ? (p.R3 - 1) * p.R1 * p.R2 : 0);
-  if (p.kind == 1) tw = 48 + 15 * 64;
-  if (p.kind == 2) tw = 96 + 128;  // step-5 twiddles are formed as powers of W_2048^(l') in the kernel
-  h->tw_count = (tw + 1) & ~1;
+// Makes the plan for `in` the handle's plan.  Nothing changes unless the plan is made in full; a new plan invalidates every
+// device table.
+int adopt_plan(fdoct_ctx* h, const PlanInputs& in) {
+  Plan p;
+  std::string why;
+  if (int rc = make_plan(in, &p, &why)) return fail(h, rc, why);
+  h->plan = std::move(p);
+  invalidate(h);
   return FDOCT_OK;
 }
 
@@ -271,13 +67,14 @@ int select_plan(fdoct_ctx* h) {
 // tw3 / gi: the step-5 twiddle table and the gather table are staged (the transposed-store kernels leave out what they hold in
 // registers: fused_tw3_in_lds / fused_gi_in_lds)
 size_t const_lds_bytes(const fdoct_ctx* h, bool planes, bool il_plane, bool il_half, bool tw3, bool gi) {
-  const int WC = 8 * h->plan.T * h->plan.WCH;
-  const size_t tw_entries = tw3 ? (size_t)h->tw_count : (size_t)(h->plan.R2 - 1) * h->plan.R1;
-  return (planes ? (size_t)3 : 0) * WC * 4 + (il_plane ? (size_t)WC * (il_half ? 2 : 4) : 0) + tw_entries * 8 + (h->cplx ? (size_t)h->NC * 8 : 0) + (gi ? (size_t)h->NC * 4 : 0);
+  const Plan& pl = h->plan;
+  const int WC = 8 * pl.fused->T * pl.fused->WCH;
+  const size_t tw_entries = tw3 ? (size_t)pl.tw_count : (size_t)(pl.fused->R2 - 1) * pl.fused->R1;
+  return (planes ? (size_t)3 : 0) * WC * 4 + (il_plane ? (size_t)WC * (il_half ? 2 : 4) : 0) + tw_entries * 8 + (pl.cplx ? (size_t)pl.NC * 8 : 0) + (gi ? (size_t)pl.NC * 4 : 0);
 }
 // constants of a transposed-store launch (fast path, 1024-point row-swap plan)
 size_t tro_const_lds_bytes(const fdoct_ctx* h, int sample_bytes, bool normalize) {
-  const FusedPlan& p = h->plan;
+  const FusedPlan& p = *h->plan.fused;
   const bool both = h->precise_div, ib2d = h->yb.rows > 1, half = fused_il_half(true, p.WCH);
   // (the row-swap plan's transposed-store kernels hold the constant planes in registers; the 512-point Stockham plan's read them
   // from LDS like its row-major kernels, and its averaging kernels take the low words from global memory: fused_il_global)
@@ -371,26 +168,49 @@ std::vector<double> scaled_copy(const std::vector<double>& v, double s) {
   return t;
 }
 
-// Recompute everything the kernel reads from the host-side state and upload it.
-int rebuild_generic_state(fdoct_ctx* h);
+// What the fused and the generic tables share: 1/background in double as two floats (reciprocal_words, into ib / il; a
+// one-row background is uploaded as d_ib / d_il), the pi and dark frames with their second words, the phase.
+static int upload_shared(fdoct_ctx* h, std::vector<float>& ib, std::vector<float>& il) {
+  int rc;
+  reciprocal_words(scaled_copy(h->yb.v, plane_scales(h).yb), ib, il);
+  if (h->yb.rows == 1) {
+    if ((rc = upload(h, h->d_ib, ib))) return rc;
+    if ((rc = upload(h, h->d_il, il))) return rc;
+  } else {
+    h->d_ib.release();
+    h->d_il.release();
+  }
+  // (second words: what the float planes leave of the double ones -- read where the row is formed in double, BscanDark's band-pass)
+  auto up_ref = [&](const RefFrame& f, double scale, DevBuf<float>& d, DevBuf<float>& d_lo) -> int {
+    std::vector<float> t(f.v.size()), tl(f.v.size());
+    for (size_t i = 0; i < t.size(); i++) {
+      t[i] = (float)(f.v[i] * scale);
+      tl[i] = (float)(f.v[i] * scale - (double)t[i]);
+    }
+    if (int e = upload(h, d_lo, tl)) return e;
+    return upload(h, d, t);
+  };
+  if ((rc = up_ref(h->yp, plane_scales(h).yp, h->d_yp, h->d_yp_lo))) return rc;
+  if ((rc = up_ref(h->yd, plane_scales(h).yd, h->d_yd, h->d_yd_lo))) return rc;
+  std::vector<float2> ph(h->phase.size() / 2);
+  for (size_t i = 0; i < ph.size(); i++) ph[i] = make_float2(h->phase[2 * i], h->phase[2 * i + 1]);
+  return upload(h, h->d_phase, ph);
+}
 
-int rebuild_device_state(fdoct_ctx* h) {
-  int rc = select_plan(h);
-  if (rc) return rc;
-  h->generic_tables_ok = false;
-  h->wave_tables_ok = false;
-  if (h->use_generic) return rebuild_generic_state(h);
+// Tables of the fused kernels.
+int ensure_fused_tables(fdoct_ctx* h) {
+  if (h->tables_ok & TABLES_FUSED) return FDOCT_OK;
   const int W = h->W, H = h->H, N = h->N;
-  const FusedPlan& p = h->plan;
+  const Plan& pl = h->plan;
+  const FusedPlan& p = *pl.fused;
   const int WC = 8 * p.T * p.WCH;
   DEVICE_SCOPE(h);
-
-  // 1/background in double, as two floats (reciprocal_words)
+  int rc;
   {
     std::vector<float> ib, il;
-    const std::vector<double> ybs = h->yb.rows ? scaled_copy(h->yb.v, plane_scales(h).yb) : std::vector<double>();
-    if (h->yb.rows) reciprocal_words(ybs, ib, il);
+    if ((rc = upload_shared(h, ib, il))) return rc;
     {  // the half-float pattern of the second word (rows exactly one chunk width wide: the fast path's condition)
+      const std::vector<double> ybs = scaled_copy(h->yb.v, plane_scales(h).yb);
       std::vector<uint32_t> h16, h16_2d;
       if (W == WC && h->yb.rows == 1) {
         h16.resize((size_t)WC / 2);
@@ -403,16 +223,13 @@ int rebuild_device_state(fdoct_ctx* h) {
       if ((rc = upload(h, h->d_il16_2d, h16_2d))) return rc;
     }
     if (h->yb.rows == 1) {
-      if ((rc = upload(h, h->d_ib, ib))) return rc;
-      if ((rc = upload(h, h->d_il, il))) return rc;
-      {  // the same plane in the slot order of the kernels' LDS planes (sample 8 (ln + T c) + e -> c 8T + (e & 1) 4T + 4 ln + (e >> 1))
-        std::vector<float> ilp((size_t)WC, 0.f);
-        for (int i = 0; i < W; i++) {
-          const int e = i & 7, ln = (i >> 3) & (p.T - 1), c = i / (8 * p.T);
-          ilp[(size_t)c * 8 * p.T + (e & 1) * 4 * p.T + 4 * ln + (e >> 1)] = il[i];
-        }
-        if ((rc = upload(h, h->d_il_p, ilp))) return rc;
+      // the low words again in the slot order of the kernels' LDS planes (sample 8 (ln + T c) + e -> c 8T + (e & 1) 4T + 4 ln + (e >> 1))
+      std::vector<float> ilp((size_t)WC, 0.f);
+      for (int i = 0; i < W; i++) {
+        const int e = i & 7, ln = (i >> 3) & (p.T - 1), c = i / (8 * p.T);
+        ilp[(size_t)c * 8 * p.T + (e & 1) * 4 * p.T + 4 * ln + (e >> 1)] = il[i];
       }
+      if ((rc = upload(h, h->d_il_p, ilp))) return rc;
       h->d_ib2d_f.release();
       h->d_il2d_f.release();
     } else {
@@ -428,22 +245,8 @@ int rebuild_device_state(fdoct_ctx* h) {
       if ((rc = upload(h, h->d_ib2d_f, perm))) return rc;
       permute(il);
       if ((rc = upload(h, h->d_il2d_f, perm))) return rc;
-      h->d_ib.release();
-      h->d_il.release();
     }
   }
-  // (second words: what the float planes leave of the double ones -- read where the row is formed in double, BscanDark's band-pass)
-  auto up_ref = [&](const RefFrame& f, double scale, DevBuf<float>& d, DevBuf<float>& d_lo) -> int {
-    std::vector<float> t(f.v.size()), tl(f.v.size());
-    for (size_t i = 0; i < t.size(); i++) {
-      t[i] = (float)(f.v[i] * scale);
-      tl[i] = (float)(f.v[i] * scale - (double)t[i]);
-    }
-    if (int e = upload(h, d_lo, tl)) return e;
-    return upload(h, d, t);
-  };
-  if ((rc = up_ref(h->yp, plane_scales(h).yp, h->d_yp, h->d_yp_lo))) return rc;
-  if ((rc = up_ref(h->yd, plane_scales(h).yd, h->d_yd, h->d_yd_lo))) return rc;
   {
     // Window (main:1142) and slope step (main:1153-1173) folded into two per-sample planes: with t = x - mean and
     // y = t * w, s_i = y_i + g_i (y_i - y_(i-1)) = a_i t_i + b_i t_(i-1), a_i = (1 + g_i) w_i, b_i = -g_i w_(i-1).
@@ -452,7 +255,7 @@ int rebuild_device_state(fdoct_ctx* h) {
     // it is out of bounds there and defined as 0 here.  Real path: the 1/2 of the real-input untangle is folded into
     // the window (exact: power of two).  Products in double, rounded once.
     std::vector<float> pa(W), pb(W);
-    const double half = h->cplx ? 1.0 : 0.5;
+    const double half = pl.cplx ? 1.0 : 0.5;
     auto gg = [&](int i) { return i < N ? h->frac[i] : 0.0; };
     for (int i = 1; i < W; i++) {
       pa[i] = (float)((1.0 + gg(i)) * half * h->win[i]);
@@ -465,21 +268,21 @@ int rebuild_device_state(fdoct_ctx* h) {
   }
   {
     // gather sources: data_ylin[q] = s[nearestkindex[q]] for q = 1..N-2, else 0 (main:1164)
-    std::vector<uint32_t> gi(h->NC);
+    std::vector<uint32_t> gi(pl.NC);
     auto off = [&](int q) -> uint32_t {
       if (q <= 0 || q >= N - 1) return (uint32_t)(4 * WC);
-      return (uint32_t)staging_offset_bytes(h->idx[q], WC, h->split);
+      return (uint32_t)staging_offset_bytes(h->idx[q], WC, pl.split);
     };
-    for (int n = 0; n < h->NC; n++) gi[n] = h->cplx ? off(n) : (off(2 * n) | (off(2 * n + 1) << 16));
+    for (int n = 0; n < pl.NC; n++) gi[n] = pl.cplx ? off(n) : (off(2 * n) | (off(2 * n + 1) << 16));
     if ((rc = upload(h, h->d_gidx, gi))) return rc;
   }
   {
-    std::vector<float2> tw(h->tw_count, make_float2(0.f, 0.f));
+    std::vector<float2> tw(pl.tw_count, make_float2(0.f, 0.f));
     size_t o = 0;
     if (p.kind == 1 || p.kind == 2) {
       // row-swap plans: tw2[(3c + i-1)*4 + j] = W_(4Q)^(i*(4c+j)), c < Q/4; tw3[(b-1)*L + l] = W_NC^(b*l), l < L = NC/16
       // (Q = first radix: 16 for fft1024_rowswap, 32 for fft2048_rowswap)
-      const int Q = p.R1, L = h->NC / 16;
+      const int Q = p.R1, L = pl.NC / 16;
       for (int c = 0; c < Q / 4; c++)
         for (int i = 1; i < 4; i++)
           for (int j = 0; j < 4; j++) {
@@ -488,7 +291,7 @@ int rebuild_device_state(fdoct_ctx* h) {
           }
       for (int b = 1; b < (p.kind == 1 ? 16 : 2); b++)  // kind 2 keeps only the b = 1 row
         for (int l = 0; l < L; l++) {
-          const double a = 2.0 * kPi * (double)(b * l) / (double)h->NC;
+          const double a = 2.0 * kPi * (double)(b * l) / (double)pl.NC;
           tw[3 * Q + (b - 1) * L + l] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
     } else
@@ -500,7 +303,7 @@ int rebuild_device_state(fdoct_ctx* h) {
     if (p.kind == 0 && p.R3 > 1)
       for (int r = 1; r < p.R3; r++)
         for (int k = 0; k < p.R1 * p.R2; k++) {
-          const double a = 2.0 * kPi * (double)r * (double)k / (double)h->NC;
+          const double a = 2.0 * kPi * (double)r * (double)k / (double)pl.NC;
           tw[o++] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
     if ((rc = upload(h, h->d_tw, tw))) return rc;
@@ -511,13 +314,7 @@ int rebuild_device_state(fdoct_ctx* h) {
     }
     if ((rc = upload(h, h->d_utw, utw))) return rc;
   }
-  {
-    std::vector<float2> ph(h->phase.size() / 2);
-    for (size_t i = 0; i < ph.size(); i++) ph[i] = make_float2(h->phase[2 * i], h->phase[2 * i + 1]);
-    if ((rc = upload(h, h->d_phase, ph))) return rc;
-  }
-  (void)H;
-  h->dirty = false;
+  h->tables_ok |= TABLES_FUSED;
   return FDOCT_OK;
 }
 
@@ -594,38 +391,25 @@ void build_bluestein_tables(int n, int Mb, std::vector<float2>& chirp, std::vect
   for (int m = 0; m < Mb; m++) bhat[m] = make_float2((float)(br[m] / Mb), (float)(bi[m] / Mb));
 }
 
-// Device tables of the generic path.
-int rebuild_generic_state(fdoct_ctx* h) {
+// Tables of the generic path (and of the long-row path, which makes its own DFT tables as it goes: big_plan_get).
+int ensure_generic_tables(fdoct_ctx* h) {
+  const GenericPlan& gp = h->plan.gen;
+  if (gp.rc) return fail(h, gp.rc, gp.why);
+  if (h->tables_ok & TABLES_GENERIC) return FDOCT_OK;
   int rc;
   const int W = h->W, N = h->N, MW = h->W * h->M;
   DEVICE_SCOPE(h);
   {
     std::vector<float> ib, il;
-    reciprocal_words(scaled_copy(h->yb.v, plane_scales(h).yb), ib, il);
+    if ((rc = upload_shared(h, ib, il))) return rc;
     if (h->yb.rows == 1) {
-      if ((rc = upload(h, h->d_ib, ib))) return rc;
-      if ((rc = upload(h, h->d_il, il))) return rc;
       h->d_ib2d.release();
       h->d_il2d.release();
     } else {
       if ((rc = upload(h, h->d_ib2d, ib))) return rc;
       if ((rc = upload(h, h->d_il2d, il))) return rc;
-      h->d_ib.release();
-      h->d_il.release();
     }
   }
-  // (second words: what the float planes leave of the double ones -- read where the row is formed in double, BscanDark's band-pass)
-  auto up_ref = [&](const RefFrame& f, double scale, DevBuf<float>& d, DevBuf<float>& d_lo) -> int {
-    std::vector<float> t(f.v.size()), tl(f.v.size());
-    for (size_t i = 0; i < t.size(); i++) {
-      t[i] = (float)(f.v[i] * scale);
-      tl[i] = (float)(f.v[i] * scale - (double)t[i]);
-    }
-    if (int e = upload(h, d_lo, tl)) return e;
-    return upload(h, d, t);
-  };
-  if ((rc = up_ref(h->yp, plane_scales(h).yp, h->d_yp, h->d_yp_lo))) return rc;
-  if ((rc = up_ref(h->yd, plane_scales(h).yd, h->d_yd, h->d_yd_lo))) return rc;
   std::vector<float> w(W), g(MW);
   for (int i = 0; i < W; i++) w[i] = (float)h->win[i];
   for (int i = 0; i < MW; i++) g[i] = (i < N) ? (float)h->frac[i] : 0.f;  // fractionalk[nearestkindex[q]], 0 past its end
@@ -647,24 +431,24 @@ int rebuild_generic_state(fdoct_ctx* h) {
   };
   if ((rc = up_tw(N, h->d_twg_n))) return rc;
   if ((N % 2) == 0 && (rc = up_tw(N / 2, h->d_twg_nh))) return rc;
-  if (h->blu_m) {
-    const int n = generic_real_half(h) ? N / 2 : N, Mb = h->blu_m;
+  if (gp.blu_m) {
+    const int n = generic_real_half(plan_inputs(h)) ? N / 2 : N, Mb = gp.blu_m;
     std::vector<float2> chirp, bhat;
     build_bluestein_tables(n, Mb, chirp, bhat);
     if ((rc = upload(h, h->d_blu_chirp, chirp))) return rc;
     if ((rc = upload(h, h->d_blu_bhat, bhat))) return rc;
     if ((rc = up_tw(Mb, h->d_twg_blu))) return rc;
   }
-  if (h->M > 1 && h->zp_full) {  // the full-length zero-pad stage's two plans
-    for (fdoct_ctx::GenericDftPlan* p : {&h->gzf, &h->gzi}) {
-      if ((rc = up_tw(p->blu_m ? p->blu_m : p->n, p->d_tw))) return rc;
-      if (p->blu_m) {
-        std::vector<float2> chirp, bhat;
-        build_bluestein_tables(p->n, p->blu_m, chirp, bhat);
-        if ((rc = upload(h, p->d_chirp, chirp))) return rc;
-        if ((rc = upload(h, p->d_bhat, bhat))) return rc;
-      }
-    }
+  if (h->M > 1 && gp.zp_full) {  // the full-length zero-pad stage's two plans
+    auto up_dft = [&](const GenericDftPlan& p, fdoct_ctx::GenericDftTables& d) -> int {
+      if (int e = up_tw(p.blu_m ? p.blu_m : p.n, d.tw)) return e;
+      if (!p.blu_m) return FDOCT_OK;
+      std::vector<float2> chirp, bhat;
+      build_bluestein_tables(p.n, p.blu_m, chirp, bhat);
+      if (int e = upload(h, d.chirp, chirp)) return e;
+      return upload(h, d.bhat, bhat);
+    };
+    if ((rc = up_dft(gp.gzf, h->d_gzf)) || (rc = up_dft(gp.gzi, h->d_gzi))) return rc;
   }
   if (h->M > 1) {
     if ((rc = up_tw(W, h->d_twg_w))) return rc;     // untangle factors of the half-length transforms
@@ -672,20 +456,18 @@ int rebuild_generic_state(fdoct_ctx* h) {
     if ((rc = up_tw(W / 2, h->d_twg_wh))) return rc;
     if ((rc = up_tw(MW / 2, h->d_twg_mwh))) return rc;
   }
-  {
-    std::vector<float2> ph(h->phase.size() / 2);
-    for (size_t i = 0; i < ph.size(); i++) ph[i] = make_float2(h->phase[2 * i], h->phase[2 * i + 1]);
-    if ((rc = upload(h, h->d_phase, ph))) return rc;
-  }
   if (!h->d_gen_tickets && (rc = h->d_gen_tickets.assign(h, 64))) return rc;   // generic_kernel's row counters (launch_family_generic)
-  h->dirty = false;
-  h->generic_tables_ok = true;
+  h->tables_ok |= TABLES_GENERIC;
   return FDOCT_OK;
 }
 
 // Tables of the wave-per-row kernels: packed gather sources and the twiddle blob
-// [N/2 passes][M W/2 passes][W/2 passes][e^(2 pi i k/W), k < W/2][e^(2 pi i k/(M W)), k < W/2][e^(2 pi i k/N), k < D].
-int rebuild_wave_state(fdoct_ctx* h) {
+// [N/2 passes][M W/2 passes][W/2 passes][e^(2 pi i k/W), k < W/2][e^(2 pi i k/(M W)), k < W/2][e^(2 pi i k/N), k < D];
+// with the generic path's, whose device copies of the window and the resample table they read.
+int ensure_wave_tables(fdoct_ctx* h) {
+  int rc;
+  if ((rc = ensure_generic_tables(h))) return rc;
+  if (h->tables_ok & TABLES_WAVE) return FDOCT_OK;
   // complex rows (dispersion phase): the final transform runs over the whole row, one gather source per point
   const bool cplx = !h->phase.empty();
   const int W = h->W, M = h->M, N = h->N, MW = W * M, NC = cplx ? N : N / 2, D = h->D;
@@ -720,10 +502,9 @@ int rebuild_wave_state(fdoct_ctx* h) {
   if (!cplx)
     for (int k = 0; k < (D > N / 2 ? N / 2 + 1 : D); k++) tw.push_back(unit((double)k, (double)N));
   h->wave_tw_count = (int)tw.size();
-  int rc;
   if ((rc = upload(h, h->d_wave_gidx, gi))) return rc;
   if ((rc = upload(h, h->d_wave_tw, tw))) return rc;
-  h->wave_tables_ok = true;
+  h->tables_ok |= TABLES_WAVE;
   return FDOCT_OK;
 }
 

@@ -189,7 +189,7 @@ def fft2048_rowswap_model(x):
 
 # ---------------------------------------------------------------------------------------------------------------
 # Wave-per-row kernels (fdoct_amd/csrc/fdoct_wave.hip): the radix plan, the per-pass twiddle tables the host builds
-# (fdoct_capi.cpp::rebuild_wave_state) and the in-place Stockham passes with clamped partial rounds.
+# (fdoct_state.cpp::ensure_wave_tables) and the in-place Stockham passes with clamped partial rounds.
 def wave_plan(n):
     """fdoct_wave.h::wave_plan: [(R, Ns)], or None when n has a prime factor above 5."""
     plan, ns = [], 1

@@ -116,6 +116,34 @@ def test_out_of_host_memory_in_an_entry_point_is_an_error_code(tmp_path):
     assert lines[-1] == "ok" and len(lines) == 4, out.stdout
 
 
+def test_plan_decisions_match_the_recorded_table(tmp_path):
+    """make_plan (fdoct_amd/csrc/fdoct_plan.h) decides, for every configuration of tests/native/plan_check.cpp's grid -- the
+    BASELINE shapes, the shipped ini shapes, odd widths, Bluestein lengths, in-place half lengths, rows beyond the LDS, with and
+    without a phase, every plan override, with and without force_general --, exactly what plan_check.expected recorded from the
+    planner before the plan was a value: the fused plan and its geometry, or the generic path, and the generic plan."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++")
+    if not cxx:
+        pytest.skip("no g++")
+    exe = tmp_path / "plan_check"
+    native = os.path.join(ROOT, "tests", "native")
+    libdir = os.path.dirname(fdoct_amd.library_path())
+    cmd = [cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "fdoct_amd", "csrc"),
+           os.path.join(native, "plan_check.cpp"), "-o", str(exe),
+           "-L", libdir, "-lfdoct_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    env = {k: v for k, v in os.environ.items() if not k.startswith("FDOCT_")}  # (the planner's measurement switches: off)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = out.stdout.splitlines()
+    want = open(os.path.join(native, "plan_check.expected")).read().splitlines()
+    assert len(got) == len(want)
+    diff = [(w, g) for w, g in zip(want, got) if w != g]
+    assert not diff, "%d decisions differ, first: %s" % (len(diff), diff[0])
+
+
 def test_every_entry_point_catches_at_the_boundary():
     """Each extern "C" definition in fdoct_capi.cpp is a function-try-block that ends in the boundary's catch macro
     (FDOCT_CATCH and its variants), and those definitions are exactly the exported ABI."""
