@@ -88,6 +88,13 @@ ABI_SYMBOLS = [
     "fdoct_last_kernel", "fdoct_set_jit", "fdoct_jit_note", "fdoct_jit_compile_check", "fdoct_set_precise_division", "fdoct_prepare", "fdoct_broadcast_state_rccl",
 ]
 
+# every symbol include/fdoct_roi.h declares: the B-scan readouts (a header and translation unit of their own, so that the ABI
+# of include/fdoct.h above stays as it is)
+ROI_ABI_SYMBOLS = [
+    "fdoct_ascan_minmax", "fdoct_roi_mean", "fdoct_set_peakhold_roi", "fdoct_peakhold", "fdoct_get_peakhold",
+    "fdoct_clear_peakhold", "fdoct_vibration_profile", "fdoct_besseldb_inverse",
+]
+
 # fdoct_kernel (include/fdoct.h): what fdoct_last_kernel returns
 KERNEL_NONE, KERNEL_FUSED, KERNEL_FUSED_TRANSPOSED, KERNEL_FUSED_STAGED, KERNEL_WAVE, KERNEL_WAVE_JIT, KERNEL_GENERIC, KERNEL_LONG_ROWS = range(8)
 
@@ -185,6 +192,17 @@ def load_library():
     lib.fdoct_jit_compile_check.restype = C.c_longlong
     lib.fdoct_export_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.fdoct_import_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    # include/fdoct_roi.h
+    lib.fdoct_ascan_minmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_int]
+    lib.fdoct_roi_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_void_p, C.c_int]
+    lib.fdoct_set_peakhold_roi.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.fdoct_peakhold.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.fdoct_get_peakhold.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fdoct_clear_peakhold.argtypes = [C.c_void_p, C.c_int]
+    lib.fdoct_vibration_profile.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fdoct_besseldb_inverse.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -241,8 +259,28 @@ def build_colormap_jet():
     return t
 
 
+def besseldb_inverse(y):
+    """fdoct_besseldb_inverse: the reference's besseldbinverse table (BscanFFTpeak.cpp:243-395) at every y.  Needs no GPU."""
+    a = np.ascontiguousarray(y, np.float64)
+    out = np.empty_like(a)
+    rc = load_library().fdoct_besseldb_inverse(a.ctypes.data, a.size, out.ctypes.data)
+    if rc:
+        raise FdoctError(rc, "fdoct_besseldb_inverse: bad arguments")
+    return out
+
+
+def _db_batch(db, layout):
+    """A host dB batch as (array, nbscans, depths, ascans): (n, ascans, depths) row-major, (n, depths, ascans) transposed."""
+    a = np.ascontiguousarray(db, np.float32)
+    if a.ndim == 2:
+        a = a[None]
+    n, r, c = a.shape
+    return (a, n, r, c) if layout == LAYOUT_TRANSPOSED else (a, n, c, r)
+
+
 class Reconstructor:
     """One handle = the processing state of one acquisition loop on one GPU."""
+    _roi_w = 0  # width of the peak-hold ROI set last (fdoct_set_peakhold_roi; a clone starts without one)
 
     def __init__(self, cfg: Config):
         self.lib = load_library()
@@ -453,6 +491,64 @@ class Reconstructor:
         out = np.empty((nrows, self.cfg.numfftpoints), np.float64)
         self._check(self.lib.fdoct_get_ylin(self.h, row0, nrows, out.ctypes.data))
         return out
+
+    # -- B-scan readouts (include/fdoct_roi.h).  Host batches are float32 (nbscans, ascans, depths) in the row-major layout,
+    # (nbscans, depths, ascans) in the transposed one; the *_device forms take raw device addresses and enqueue.
+    def ascan_minmax(self, db, ascanat, layout=LAYOUT_ROWMAJOR):
+        """printMinMaxAscan (BscanFFT.cpp:146-171): per B-scan (min, max) of A-scan ascanat, depth rows 0-3 read as row 4."""
+        a, n, d, h = _db_batch(db, layout)
+        lo, hi = np.empty(n, np.float32), np.empty(n, np.float32)
+        self._check(self.lib.fdoct_ascan_minmax(self.h, a.ctypes.data, MEM_HOST, layout, n, d, h, ascanat, lo.ctypes.data,
+                                                hi.ctypes.data, MEM_HOST))
+        return lo, hi
+
+    def ascan_minmax_device(self, d_db_ptr, nbscans, depths, ascans, ascanat, d_min_ptr, d_max_ptr, layout=LAYOUT_ROWMAJOR):
+        self._check(self.lib.fdoct_ascan_minmax(self.h, d_db_ptr, MEM_DEVICE, layout, nbscans, depths, ascans, ascanat,
+                                                d_min_ptr, d_max_ptr, MEM_DEVICE))
+
+    def roi_mean(self, db, ascanat, vertpos, width, layout=LAYOUT_ROWMAJOR):
+        """printAvgROI (BscanFFT.cpp:99-144): per B-scan mean (float64) of depths vertpos..+2 x A-scans ascanat..+width-1."""
+        a, n, d, h = _db_batch(db, layout)
+        out = np.empty(n, np.float64)
+        self._check(self.lib.fdoct_roi_mean(self.h, a.ctypes.data, MEM_HOST, layout, n, d, h, ascanat, vertpos, width,
+                                            out.ctypes.data, MEM_HOST))
+        return out
+
+    def roi_mean_device(self, d_db_ptr, nbscans, depths, ascans, ascanat, vertpos, width, d_out_ptr, layout=LAYOUT_ROWMAJOR):
+        self._check(self.lib.fdoct_roi_mean(self.h, d_db_ptr, MEM_DEVICE, layout, nbscans, depths, ascans, ascanat, vertpos,
+                                            width, d_out_ptr, MEM_DEVICE))
+
+    def set_peakhold_roi(self, x, y, w, h, ascanat):
+        """The peak-hold ROI on the D x H picture (x, w: A-scans; y, h: depths) and the held A-scan; resets the column holds."""
+        self._check(self.lib.fdoct_set_peakhold_roi(self.h, x, y, w, h, ascanat))
+        self._roi_w = w
+
+    def peakhold(self, slot, db, layout=LAYOUT_ROWMAJOR):
+        """Folds a host dB batch into hold slot 1..4."""
+        a, n, d, h = _db_batch(db, layout)
+        self._check(self.lib.fdoct_peakhold(self.h, slot, a.ctypes.data, MEM_HOST, layout, n, d, h))
+
+    def peakhold_device(self, slot, d_db_ptr, nbscans, depths, ascans, layout=LAYOUT_ROWMAJOR):
+        self._check(self.lib.fdoct_peakhold(self.h, slot, d_db_ptr, MEM_DEVICE, layout, nbscans, depths, ascans))
+
+    def peakhold_values(self, slot, roi_width=None):
+        """(colmax float32[w], ascanmax float, B-scans held) of one slot; roi_width=None reads the width of the ROI set last."""
+        w = self._roi_w if roi_width is None else roi_width
+        cols = np.empty(w, np.float32)
+        amax, count = C.c_float(), C.c_longlong()
+        self._check(self.lib.fdoct_get_peakhold(self.h, slot, cols.ctypes.data if w else None, C.byref(amax), C.byref(count)))
+        return cols, amax.value, count.value
+
+    def clear_peakhold(self, slot):
+        self._check(self.lib.fdoct_clear_peakhold(self.h, slot))
+
+    def vibration(self, mode, lambda0=None):
+        """(profile_nm float64[w], disp_nm, err_nm) of BscanFFTpeak's mode 3 (slots 1-3) or 4 (slots 1-4)."""
+        prof = np.empty(self._roi_w, np.float64)
+        disp, err = C.c_double(), C.c_double()
+        self._check(self.lib.fdoct_vibration_profile(self.h, mode, -1.0 if lambda0 is None else float(lambda0),
+                                                     prof.ctypes.data if prof.size else None, C.byref(disp), C.byref(err)))
+        return prof, disp.value, err.value
 
     # -- work
     def _out_shape(self, nframes, layout):

@@ -10,44 +10,7 @@ using namespace fdoct_impl;
 
 using HandlePtr = std::unique_ptr<fdoct_ctx, int (*)(fdoct_handle)>;  // (deleter: fdoct_destroy)
 
-// Waits for everything the handle has enqueued: nothing is left in flight that still points at the caller's buffers or the
-// chunk slots.
-static void drain(fdoct_ctx* h) {
-  if (h->s_in) (void)hipStreamSynchronize(h->s_in);
-  (void)hipStreamSynchronize(h->stream);
-  if (h->s_out) (void)hipStreamSynchronize(h->s_out);
-}
-
-// The one handler of every entry point (include/fdoct.h: nothing throws across the boundary).  Out of host memory is
-// FDOCT_ERR_NOMEM, any other exception FDOCT_ERR_DEVICE, and the text goes where fdoct_last_error finds it.  A handle's device
-// state is rebuilt by its next call (an exception may have cut an upload short) and the handle's streams are drained.
-static int caught(fdoct_ctx* h) noexcept {
-  int code = FDOCT_ERR_DEVICE;
-  const char* what = "unknown exception";
-  try {
-    throw;
-  } catch (const std::bad_alloc&) {
-    code = FDOCT_ERR_NOMEM;
-    what = "out of host memory";
-  } catch (const std::exception& e) {
-    what = e.what();
-  } catch (...) {
-  }
-  std::string& err = h ? h->err : g_create_error;
-  try {
-    err = what;
-  } catch (...) {
-    err.clear();
-  }
-  if (h) {
-    invalidate(h);
-    drain(h);
-  }
-  return code;
-}
-#define FDOCT_CATCH(h) catch (...) { return caught(h); }
-#define FDOCT_CATCH_RETURN(h, value) catch (...) { (void)caught(h); return value; }
-#define FDOCT_CATCH_VOID(h) catch (...) { (void)caught(h); }
+// (drain, caught and the FDOCT_CATCH macros: fdoct_ctx.h, shared with fdoct_roi.cpp)
 
 // ------------------------------------------------------------------ C ABI --
 extern "C" {

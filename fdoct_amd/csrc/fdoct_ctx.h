@@ -1,8 +1,9 @@
-// fdoct_ctx.h -- what the three translation units of the C-ABI layer share: the handle (fdoct_ctx), the error / device-scope /
+// fdoct_ctx.h -- what the translation units of the C-ABI layer share: the handle (fdoct_ctx), the error / device-scope /
 // device-memory helpers, and the declarations of
 //   fdoct_state.cpp   the handle's plan (fdoct_plan.h) and everything a handle uploads to its device (tables, planes, twiddles)
 //   fdoct_route.cpp   the dispatch: choose_route, the passes in front of the chain, one launcher per kernel family, enqueue
 //   fdoct_capi.cpp    the extern "C" entry points of include/fdoct.h
+//   fdoct_roi.cpp     those of include/fdoct_roi.h (the B-scan readouts)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -185,6 +186,18 @@ struct fdoct_ctx {
   DevBuf<double> d_disp_part;
   DevBuf<float> ws_disp_in, ws_disp_in2;
   DevBuf<unsigned char> ws_disp_out;
+  // B-scan readouts (fdoct_roi.cpp): measurement state, not set-up state, so neither fdoct_export_state nor
+  // fdoct_clone_to_device carries it
+  struct PeakHoldRoi {
+    int x = 0, y = 0, w = 0, h = 0, ascanat = 0;  // x, w: A-scans; y, h: depths
+    bool set = false;
+  };
+  PeakHoldRoi roi;
+  DevBuf<uint32_t> d_hold_cols;    // 4 slots x roi.w column holds, as roi_encode words (fdoct_roi_kernels.h)
+  DevBuf<uint32_t> d_hold_scalar;  // 4 scalar holds of A-scan roi.ascanat, likewise
+  long long hold_count[4] = {0, 0, 0, 0};
+  DevBuf<float> ws_roi_in;         // host-memory dB images on their way to the readouts
+  DevBuf<double> ws_roi_out;       // ... and the per-B-scan results on their way back
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
@@ -257,6 +270,46 @@ inline void builtin_jet(unsigned char* bgr) { build_opencv_jet(bgr); }
 // Each family's device tables, built by its ensure_*_tables when they do not match the host state.
 enum : unsigned { TABLES_FUSED = 1, TABLES_GENERIC = 2, TABLES_WAVE = 4 };
 inline void invalidate(fdoct_ctx* h) { h->tables_ok = 0; }
+
+// Waits for everything the handle has enqueued: nothing is left in flight that still points at the caller's buffers or the
+// chunk slots.
+inline void drain(fdoct_ctx* h) {
+  if (h->s_in) (void)hipStreamSynchronize(h->s_in);
+  (void)hipStreamSynchronize(h->stream);
+  if (h->s_out) (void)hipStreamSynchronize(h->s_out);
+}
+
+// The one handler of every entry point (include/fdoct.h, include/fdoct_roi.h: nothing throws across the boundary).  Out of
+// host memory is FDOCT_ERR_NOMEM, any other exception FDOCT_ERR_DEVICE, and the text goes where fdoct_last_error finds it.  A
+// handle's device state is rebuilt by its next call (an exception may have cut an upload short) and its streams are drained.
+inline int caught(fdoct_ctx* h) noexcept {
+  int code = FDOCT_ERR_DEVICE;
+  const char* what = "unknown exception";
+  try {
+    throw;
+  } catch (const std::bad_alloc&) {
+    code = FDOCT_ERR_NOMEM;
+    what = "out of host memory";
+  } catch (const std::exception& e) {
+    what = e.what();
+  } catch (...) {
+  }
+  std::string& err = h ? h->err : g_create_error;
+  try {
+    err = what;
+  } catch (...) {
+    err.clear();
+  }
+  if (h) {
+    invalidate(h);
+    drain(h);
+  }
+  return code;
+}
+#define FDOCT_CATCH(h) catch (...) { return caught(h); }
+#define FDOCT_CATCH_RETURN(h, value) catch (...) { (void)caught(h); return value; }
+#define FDOCT_CATCH_VOID(h) catch (...) { (void)caught(h); }
+
 size_t dtype_size(int dt);
 int copy_ref_frame(fdoct_ctx* h, RefFrame& dst, const void* data, fdoct_dtype dtype, int rows, size_t pitch);
 PlanInputs plan_inputs(const fdoct_ctx* h);

@@ -10,6 +10,7 @@
 //                [--averages A] [--sim] [--lambdamin 816e-9 --lambdamax 884e-9]
 //                [--rowwisenormalize 0|1] [--donotnormalize 0|1] [--repeat K] [--threshold dB] --out prefix
 //                [--gpus N [--devices d0,d1,...]] [--precise-division | --one-word-division]
+//                [--roi-mean ascanat,vertpos,width]
 //
 // --gpus N: one process, N handles (fdoct_clone_to_device), one host thread per handle; the frames are sharded with
 // fdoct_shard_frames (contiguous ranges, averaging groups never split -- the rule of the multi-process path,
@@ -17,6 +18,8 @@
 // exchange is the clone of the constant state.  --devices lists the device of each handle (default 0, 1, ..., wrapping
 // around when fewer GPUs are visible -- several handles then share a device, which is how a 1-GPU box rehearses it).
 //
+// --roi-mean: the ROIreport readout of printAvgROI (BscanFFT.cpp:99-144) on every output B-scan, one line per B-scan in
+// the reference's text ("Mean of ROI at <ascanat> = <mean> dB"), computed on the GPU (include/fdoct_roi.h).
 // --frames holds one or more H x W frames back to back (u8 for --bits 8, little-endian u16 for --bits 16).
 // Outputs: <prefix>_bscan.f32 / <prefix>_bscandb.f32 (reference layout D x H per B-scan, main:1220) and
 // <prefix>.m with `bscan001=[...];` in the Matlab text form the reference's savematasdata writes
@@ -33,6 +36,7 @@
 #include <vector>
 
 #include "../include/fdoct.h"
+#include "../include/fdoct_roi.h"
 #include "ocv_io.h"
 
 static bool ends_with(const std::string& s, const std::string& suf) {
@@ -63,6 +67,7 @@ int main(int argc, char** argv) {
   int precise = -1;  // -1: the library default (both words of 1/background since round 5)
   std::vector<int> devices;
   double bscanthreshold = -30.0;  // main:385
+  int roi[3] = {-1, 0, 0};         // --roi-mean ascanat,vertpos,width (-1: off)
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -91,6 +96,12 @@ int main(int argc, char** argv) {
     else if (a == "--gpus") gpus = std::atoi(next());
     else if (a == "--precise-division") precise = 1;   // main:1132 divides in double: both words of 1/background on the fast path too (the default)
     else if (a == "--one-word-division") precise = 0;  // the opt-out: one f32 reciprocal on the fast path, for fringes above ~1 % of the DC level
+    else if (a == "--roi-mean") {
+      if (std::sscanf(next(), "%d,%d,%d", &roi[0], &roi[1], &roi[2]) != 3) {
+        std::fprintf(stderr, "--roi-mean wants ascanat,vertpos,width\n");
+        return 1;
+      }
+    }
     else if (a == "--devices") {
       for (const char* p = next(); *p;) {
         devices.push_back(std::atoi(p));
@@ -269,6 +280,17 @@ int main(int argc, char** argv) {
       const char rgb[3] = {(char)bgr[3 * i + 2], (char)bgr[3 * i + 1], (char)bgr[3 * i]};
       pp.write(rgb, 3);
     }
+  }
+  if (roi[0] >= 0) {
+    // ROIreport: printAvgROI on each displayed B-scan (main:1289-1290), over the dB image after the DC mask
+    std::vector<double> mean(G);
+    rc = fdoct_roi_mean(h, bscandb.data(), FDOCT_MEM_HOST, FDOCT_LAYOUT_TRANSPOSED_DxH, G, cfg.numdisplaypoints, cfg.height,
+                        roi[0], roi[1], roi[2], mean.data(), FDOCT_MEM_HOST);
+    if (rc) {
+      std::fprintf(stderr, "fdoct_roi_mean: %d %s\n", rc, fdoct_last_error(h));
+      return 1;
+    }
+    for (int g = 0; g < G; g++) std::printf("Mean of ROI at %d = %f dB\n", roi[0], mean[g]);
   }
   for (fdoct_handle x : hs) fdoct_destroy(x);
   return 0;
