@@ -1,7 +1,8 @@
 // fdoct_ctx.h -- what the translation units of the C-ABI layer share: the handle (fdoct_ctx), the error / device-scope /
 // device-memory helpers, and the declarations of
 //   fdoct_state.cpp   the handle's plan (fdoct_plan.h) and everything a handle uploads to its device (tables, planes, twiddles)
-//   fdoct_route.cpp   the dispatch: choose_route, the passes in front of the chain, one launcher per kernel family, enqueue
+//   fdoct_route.cpp   the dispatch: choose_route (with fdoct_launch.h's launch value), the passes in front of the chain, one launcher
+//                     per kernel family, enqueue
 //   fdoct_capi.cpp    the extern "C" entry points of include/fdoct.h
 //   fdoct_roi.cpp     those of include/fdoct_roi.h (the B-scan readouts)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
@@ -27,6 +28,7 @@
 #include "fdoct_big.h"
 #include "fdoct_host.h"
 #include "fdoct_kernels.h"
+#include "fdoct_launch.h"
 #include "fdoct_wave.h"
 #include "fdoct_jit.h"
 #include "fdoct_hostcopy.h"
@@ -314,8 +316,6 @@ size_t dtype_size(int dt);
 int copy_ref_frame(fdoct_ctx* h, RefFrame& dst, const void* data, fdoct_dtype dtype, int rows, size_t pitch);
 PlanInputs plan_inputs(const fdoct_ctx* h);
 int adopt_plan(fdoct_ctx* h, const PlanInputs& in);
-size_t const_lds_bytes(const fdoct_ctx* h, bool planes, bool il_plane, bool il_half, bool tw3 = true, bool gi = true);
-size_t tro_const_lds_bytes(const fdoct_ctx* h, int sample_bytes, bool normalize);  // (of the launch: fused_tro_pf2 depends on both)
 void reciprocal_words(const std::vector<double>& yb, std::vector<float>& ib, std::vector<float>& il);
 struct PlaneScales { double yb, yp, yd; };
 PlaneScales plane_scales(const fdoct_ctx* h);
@@ -327,23 +327,33 @@ int ensure_wave_tables(fdoct_ctx* h);
 
 // ---- fdoct_route.cpp ------------------------------------------------------------------------------------------------------
 // ---- dispatch ----------------------------------------------------------------------------------------------------------
-// Everything a call decides before it launches anything: which passes run in front of the chain, which kernel family takes it
-// and with what.  A function of the handle's state and of the call's geometry only (pointers enter through their alignment), so
-// that fdoct_prepare makes the same decisions -- and pays for a run-time compile -- without frames.
+// Everything a call decides before it enqueues anything: which passes run in front of the chain, which kernel family takes it
+// and that family's launch -- instantiation, block, LDS, grid.  A function of the handle's state and of the call's geometry only
+// (pointers enter through their alignment), so that fdoct_prepare makes the same decisions -- pays for a run-time compile, meets
+// the same refusals -- without frames.  The launchers fill argument blocks from handle and route and launch; they decide nothing.
+enum class PrePass {  // the pass that produces what the chain's kernel reads
+  None,               // the caller's frames (or the front end's output) as they are
+  F64Split,           // data_y doubles split once into two f32 planes, hi + lo (main:987)
+  MovAvg,             // smoothmovavg (main:990-991), one f32 plane
+  MovAvgF64,          // ... of doubles: the tap sums in double, two planes
+  MovAvgF32Wide,      // ... of FLOAT frames likewise (their samples need not be integers)
+};
 struct Route {
   int family = FDOCT_KERNEL_NONE;   // fdoct_kernel: who runs the chain
   bool frontend = false;            // medianBlur + binning pass over the raw frames first (main:953-958)
-  bool narrow_f64 = false;          // data_y doubles narrowed once to float (main:987)
-  bool mov_lo = false;              // smoothmovavg of FLOAT frames: the tap sums in double, handed on as two f32 planes like the doubles'
-  bool movavg = false;              // smoothmovavg pass (main:990-991)
+  PrePass pre = PrePass::None;
   int kdt = -1;                     // sample type the chain's kernel reads (FDOCT_K_*)
   size_t kpitch = 0;                // ... and its row pitch
   bool need_minmax = false;         // whole-frame min / max pre-pass (main:1128)
-  bool tro = false;                 // the fused chain writes the D x H layout itself
-  bool transpose_pass = false;      // ... or a transpose pass does
+  bool transpose_pass = false;      // a transpose pass makes the D x H layout (the fused chain does not write it itself: fused.tro)
   hipFunction_t jit_fn = nullptr;   // FDOCT_KERNEL_WAVE_JIT: the kernel compiled for this handle
   bool bin2_in_kernel = false;      // ... with the 2 x 2 software binning inside its loads (the raw frames go to it as they are)
   int wave_opt = 0;                 // FDOCT_WAVE_OPT_* of that kernel
+  FusedLaunch fused;                // the fused families: the launch (fdoct_launch.h)
+  int waves = 0;                    // the wave-per-row families: waves per workgroup ...
+  size_t lds = 0;                   // ... and, for the generic family too, dynamic LDS ...
+  long long grid = 0;               // ... and workgroups
+  bool frames_lo() const { return pre == PrePass::F64Split || pre == PrePass::MovAvgF64 || pre == PrePass::MovAvgF32Wide; }  // a plane of low words goes along
 };
 
 // Quantities of one call that every family's launch needs.

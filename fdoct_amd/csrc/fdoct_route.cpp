@@ -1,6 +1,7 @@
-// fdoct_route.cpp -- the dispatch of a call: choose_route decides everything before anything is launched, the
-// passes in front of the chain run, one launcher per kernel family fills its argument block, finish_launch is the one epilogue;
-// plus the long-row path's host side (plans, grouped launches) and the front end.  Part of the C-ABI layer (fdoct_ctx.h).
+// fdoct_route.cpp -- the dispatch of a call: choose_route decides everything before anything is enqueued -- the
+// passes in front of the chain, the kernel family and its launch (the fused family's from fdoct_launch.h) --, the passes run, one
+// launcher per kernel family fills its argument block from handle and route, finish_launch is the one epilogue; plus the long-row
+// path's host side (plans, grouped launches) and the front end.  Part of the C-ABI layer (fdoct_ctx.h).
 #include "fdoct_ctx.h"
 
 namespace fdoct_impl {
@@ -13,6 +14,9 @@ int kernel_dtype(int dt) {
     default: return -1;
   }
 }
+
+// rows of the front end's workspaces: packed, 16-byte-pitched
+static size_t frontend_pitch(int w, size_t es) { return ((size_t)w * es + 15) & ~(size_t)15; }
 
 // medianBlur + INTER_AREA binning of device-resident raw frames into a packed, 16-byte-pitched buffer.
 // Returns the binned frames in *out / *out_pitch (library workspace).
@@ -29,14 +33,14 @@ int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_
   const void* src = d_raw;
   size_t src_pitch = raw_pitch;
   if (mediann > 0) {
-    const size_t mp = ((size_t)raw_w * es + 15) & ~(size_t)15;
+    const size_t mp = frontend_pitch(raw_w, es);
     if ((rc = h->ws_med.reserve(h, mp * (size_t)raw_h * nframes))) return rc;
     HIP_TRY(h, launch_median(src, (long long)src_pitch, h->ws_med, (long long)mp, kdt, raw_w, raw_h, mediann, nframes, st));
     src = h->ws_med;
     src_pitch = mp;
   }
   const int ow = raw_w / binx, oh = raw_h / biny;
-  const size_t op = ((size_t)ow * es + 15) & ~(size_t)15;
+  const size_t op = frontend_pitch(ow, es);
   if ((rc = h->ws_front.reserve(h, op * (size_t)oh * nframes))) return rc;
   HIP_TRY(h, launch_bin(src, (long long)src_pitch, h->ws_front, (long long)op, kdt, ow, oh, binx, biny, nframes, st));
   *out = h->ws_front;
@@ -326,43 +330,35 @@ int run_big(fdoct_ctx* h, const void* kframes, const float* kframes_lo, int kdt,
   return FDOCT_OK;
 }
 
-// Can the chain write the reference's D x H layout itself (fused_kernel's TRO instantiations)?  The acquisition
-// configurations on the 1024-point row-swap plan: 8/16-bit frames that go to the kernel as they are, 1-row or full-frame
-// background, none or the whole-frame normalisation, rows in fours and depth bins in whole write-out steps, 16-byte
-// aligned outputs.
-bool fused_transposed_store_applies(const fdoct_ctx* h, fdoct_dtype dtype, const void* d_frames, size_t pitch_bytes,
-                                    const float* d_out_bscan, const float* d_out_db, int nframes) {
-  if (!h->tro_enabled || !h->plan.fused || h->staged || h->force_general || h->plan.cplx) return false;
-  const FusedPlan& p = *h->plan.fused;
-  if (!fused_tro_compiled(p.kind, p.T, p.WCH)) return false;
+// What make_fused_launch reads of the handle and of a call of `nframes` frames whose kernel reads samples of type kdt.
+static FusedLaunchInputs fused_launch_inputs(const fdoct_ctx* h, int kdt, int nframes, bool need_minmax, bool frames_lo, bool want_tro) {
+  static const unsigned ring_cap = [] { const char* e = std::getenv("FDOCT_TRO_RING"); return e ? (unsigned)std::atoi(e) : 0u; }();  // measurement: at most this many slots
+  FusedLaunchInputs in;
+  in.W = h->W; in.H = h->H; in.D = h->D; in.A = h->A;
+  in.kdt = kdt;
+  in.bg_rows = h->yb.rows; in.pi = h->yp.rows > 0; in.dark = h->yd.rows > 0;
+  in.rowwisenormalize = h->cfg.rowwisenormalize != 0; in.minmax = need_minmax; in.frames_lo = frames_lo;
+  in.precise_div = h->precise_div; in.staged = h->staged; in.force_general = h->force_general;
+  in.block_override = h->block_override; in.grid_override = h->grid_override; in.num_cu = h->num_cu;
+  in.groups = nframes / h->A; in.in_rows = (long long)nframes * h->H; in.out_rows = in.groups * h->H;
+  in.want_tro = want_tro; in.ring_cap = ring_cap;
+  return in;
+}
+
+// May the chain write the reference's D x H layout itself, as far as the CALL says (whether the configuration has such a kernel and
+// its launch fits is make_fused_launch's part)?  8/16-bit frames that go to the kernel as they are, 16-byte aligned outputs, and
+// offsets the write-out can address.
+static bool transposed_store_callable(const fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
+                                      uintptr_t out_db_addr, int nframes) {
+  if (!h->tro_enabled || !h->plan.fused || !h->yb.rows) return false;
   if (dtype != FDOCT_U8 && dtype != FDOCT_U16) return false;
   if (h->fe_median > 0 || h->fe_binx > 1 || h->fe_biny > 1 || h->cfg.movavgn > 0) return false;
-  if (h->W != 8 * p.T * p.WCH || !h->yb.rows || h->yp.rows || h->yd.rows || h->cfg.rowwisenormalize) return false;
-  const bool normalize = (h->cfg.variant == FDOCT_VARIANT_SIM) || !h->cfg.donotnormalize;
-  if ((normalize || h->yb.rows > 1) && h->A != 1) return false;  // (those instantiations exist for one frame per B-scan)
-  if (p.kind != 1 && (normalize || h->yb.rows > 1)) return false;  // (... and for the row-swap plan only: the 512-point plan has the plain and the averaging kernel)
-  const size_t es = dtype == FDOCT_U8 ? 1 : 2, valign = dtype == FDOCT_U8 ? 8 : 16;
-  const size_t pitch = pitch_bytes ? pitch_bytes : es * (size_t)h->W;
-  if (((uintptr_t)d_frames % valign) || (pitch % valign)) return false;
-  if ((h->H % 4) || (h->D % fused_tro_step_bins(64 / p.T)) || h->D > h->plan.NC) return false;
-  // (both words: a full-frame background brings its second word along with the prefetched row -- no LDS plane; a 1-row one needs
-  // the plane next to the ring, which then holds one computing wave less)
-  if (h->precise_div && h->yb.rows > 1 && !fused_il_half(true, p.WCH)) return false;
-  const int rpw = 64 / p.T;
-  if (rpw == 4) {
-    // four rows per wave: no ring -- groups of four waves own tiles and write them out from their own row buffers (fused_kernel,
-    // TRO_INPLACE): at least one group must fit, and a launch override must leave whole groups
-    if ((size_t)160 * 1024 - 64 < tro_const_lds_bytes(h, (int)es, normalize) + (size_t)fused_tro_group_waves() * h->plan.scratch_bytes * rpw) return false;
-    if (fused_max_block(h->plan.NC, p.T, true, p.kind) / 64 < fused_tro_group_waves()) return false;
-    if (h->block_override && h->block_override / 64 < fused_tro_group_waves()) return false;
-  } else if (fused_tro_ring_pick((size_t)160 * 1024 - 64 - tro_const_lds_bytes(h, (int)es, normalize) - (size_t)h->plan.scratch_bytes * rpw, h->D, rpw) == 0) {
-    return false;  // (no ring next to one computing wave)
-  }
-  if (((uintptr_t)d_out_bscan % 16) || ((uintptr_t)d_out_db % 16)) return false;
+  const size_t valign = dtype == FDOCT_U8 ? 8 : 16;
+  if ((frames_addr % valign) || (pitch_bytes % valign)) return false;
+  if ((out_bscan_addr % 16) || (out_db_addr % 16)) return false;
   if ((long long)(nframes / h->A) * h->H >= 0x7fffffffLL) return false;
   // the write-out addresses one B-scan with 32-bit byte offsets inside a buffer descriptor of 0x7ffffff0 bytes
-  if ((size_t)h->D * (size_t)h->H * 4 >= 0x7ffffff0u) return false;
-  return true;
+  return (size_t)h->D * (size_t)h->H * 4 < 0x7ffffff0u;
 }
 
 // Decides the route of a call.  frames_addr / pitch_bytes / out addresses: as the caller gave them (fdoct_prepare: an aligned,
@@ -388,6 +384,21 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
                        (h->bandpass && h->M > 1 ? FDOCT_WAVE_OPT_BANDPASS : 0) | (h->cfg.rowwisenormalize ? FDOCT_WAVE_OPT_ROWNORM : 0) |
                        (r->need_minmax ? FDOCT_WAVE_OPT_FRAMENORM : 0) | (!h->phase.empty() ? FDOCT_WAVE_OPT_CPLX : 0) |
                        (h->phase.empty() && D > h->N / 2 ? FDOCT_WAVE_OPT_DEEP : 0);
+  // The wave-per-row kernel's launch, where its tables leave room for at least one wave's buffers: as many waves as LDS and
+  // the shape's register budget allow (two rows per wave on the short zero-padded shapes), at most one workgroup per CU.
+  auto wave_fits = [&](int opt) {
+    const size_t shared = wave_shared_lds_bytes(h->wave_tw_count, W, h->M, h->N, h->yb.rows > 1, opt);
+    const size_t priv = wave_private_lds_bytes(W, h->M, h->N, opt);
+    if (shared + priv > 160 * 1024 - 64) return false;
+    int waves = (int)((160 * 1024 - 64 - shared) / priv);
+    if (waves > wave_max_waves(W, h->M, h->N, opt)) waves = wave_max_waves(W, h->M, h->N, opt);
+    if (h->block_override && h->block_override / 64 >= 1 && h->block_override / 64 <= waves) waves = h->block_override / 64;
+    const long long rows = (long long)waves * wave_rows_per_wave(W, h->M, h->N, opt);
+    r->waves = waves;
+    r->lds = shared + (size_t)waves * priv;
+    r->grid = std::min<long long>(h->grid_override > 0 ? h->grid_override : h->num_cu, (out_rows + rows - 1) / rows);
+    return true;
+  };
   // 2 x 2 binning with nothing else in front of the chain, on a configuration the wave-per-row kernel takes: the kernel compiled
   // for the handle does the binning in its own loads (FDOCT_WAVE_OPT_BIN2) and the pass over the raw frames is skipped.
   // (Measured on the shipped shapes, tools/bench_generic.py with and without FDOCT_JIT=0: + 4.5 % on 160-sample 8-bit rows, + 5 % on
@@ -397,10 +408,9 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
       (frames_addr % 4 == 0) && (pitch_bytes % 4 == 0) && pitch_bytes >= es * 2 * (size_t)W && out_rows < 0x7fffffffLL &&
       wave_jit_shape_ok(W, h->M, h->N, D)) {
     if ((rc = ensure_wave_tables(h))) return rc;
-    const size_t shared = wave_shared_lds_bytes(h->wave_tw_count, W, h->M, h->N, h->yb.rows > 1);
     std::string why;
     hipFunction_t fn = nullptr;
-    if (shared + wave_private_lds_bytes(W, h->M, h->N) > 160 * 1024 - 64) {
+    if (!wave_fits(wave_opt | FDOCT_WAVE_OPT_BIN2)) {
       // no room for even one wave: the ordinary path (binning pass, then whichever kernel fits)
     } else if (wave_jit_get(W, h->M, h->N, kdt, D, wave_opt | FDOCT_WAVE_OPT_BIN2, h->device, &fn, &why) == hipSuccess) {
       r->bin2_in_kernel = true;
@@ -418,20 +428,20 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
     if (pitch_bytes < es * (size_t)W * h->fe_binx) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a raw camera row");
     r->frontend = true;
     kaddr = 0;                                                  // a library workspace: aligned
-    kpitch = ((size_t)W * es + 15) & ~(size_t)15;
+    kpitch = frontend_pitch(W, es);
   }
   if (dtype == FDOCT_F64) {
     if (pitch_bytes % 8) return fail(h, FDOCT_ERR_INVALID, "f64 pitch must be a multiple of 8");
-    r->narrow_f64 = true;
+    r->pre = PrePass::F64Split;
     kaddr = 0;
     kpitch = (size_t)W * 4;
     kdt = FDOCT_K_F32;
   }
   if (h->cfg.movavgn > 0) {
-    r->movavg = true;
     // (float frames: the tap sums of non-integer samples go on as two planes, like the doubles' -- round 6: a float sum rounds at
     // the size of the DC level, 0.87 x the tolerance from the chain in double under fringes of 1e-3 of it in the sweeps)
-    r->mov_lo = dtype == FDOCT_F32 && !r->frontend && (pitch_bytes % 4 == 0) && (frames_addr % 4 == 0);
+    const bool wide = dtype == FDOCT_F32 && !r->frontend && (pitch_bytes % 4 == 0) && (frames_addr % 4 == 0);
+    r->pre = dtype == FDOCT_F64 ? PrePass::MovAvgF64 : wide ? PrePass::MovAvgF32Wide : PrePass::MovAvg;
     kaddr = 0;
     kpitch = (size_t)W * 4;
     kdt = FDOCT_K_F32;
@@ -446,14 +456,17 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
   if (run_generic && h->staged) return fail(h, FDOCT_ERR_UNSUPPORTED, "staged mode needs a specialised kernel for this configuration");
 
   const bool transposed = layout == FDOCT_LAYOUT_TRANSPOSED_DxH;
-  r->tro = transposed && !run_generic && !r->frontend && !r->narrow_f64 && !r->movavg &&
-           fused_transposed_store_applies(h, dtype, reinterpret_cast<const void*>(frames_addr), pitch_bytes,
-                                          reinterpret_cast<const float*>(out_bscan_addr), reinterpret_cast<const float*>(out_db_addr), nframes);
-  r->transpose_pass = transposed && !r->tro;
+  if (!run_generic) {  // the fused family: its whole launch, or why it cannot run
+    const bool want_tro = transposed && !r->frontend && r->pre == PrePass::None &&
+                          transposed_store_callable(h, dtype, frames_addr, pitch_bytes, out_bscan_addr, out_db_addr, nframes);
+    std::string why;
+    if ((rc = make_fused_launch(h->plan, fused_launch_inputs(h, kdt, nframes, r->need_minmax, r->frames_lo(), want_tro), &r->fused, &why))) return fail(h, rc, why);
+  }
+  r->transpose_pass = transposed && !r->fused.tro;
 
   // the acquisition configurations the reference ships: one wave per A-scan (fdoct_wave.hip) instead of one workgroup
   // (frames handed over as doubles carry a low word per sample: the fused any-option, workgroup-per-row and long-row kernels take it)
-  const bool wave_scope = run_generic && !h->plan.gen.use_big && h->plan_override > -2 && kdt >= 0 && !r->narrow_f64 && !r->mov_lo &&
+  const bool wave_scope = run_generic && !h->plan.gen.use_big && h->plan_override > -2 && kdt >= 0 && !r->frames_lo() &&
                           (kaddr % 4 == 0) && (kpitch % 4 == 0) && out_rows < 0x7fffffffLL;
   if (r->bin2_in_kernel && !wave_scope) return fail(h, FDOCT_ERR_DEVICE, "internal: binning left to a kernel that does not run");
   bool run_wave = r->bin2_in_kernel;
@@ -473,11 +486,9 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
     }
     run_wave = wave_builtin || r->jit_fn;
   }
-  if (run_wave) {
+  if (run_wave && !r->bin2_in_kernel) {  // (the kernel that bins is known to fit)
     if ((rc = ensure_wave_tables(h))) return rc;
-    const size_t shared = wave_shared_lds_bytes(h->wave_tw_count, W, h->M, h->N, h->yb.rows > 1, r->wave_opt);
-    if (shared + wave_private_lds_bytes(W, h->M, h->N, r->wave_opt) > 160 * 1024 - 64) {  // not even one wave's buffer next to the tables
-      if (r->bin2_in_kernel) return fail(h, FDOCT_ERR_DEVICE, "internal: binning left to a kernel that did not launch");
+    if (!wave_fits(r->wave_opt)) {  // not even one wave's buffer next to the tables
       run_wave = false;
       r->jit_fn = nullptr;
     }
@@ -486,13 +497,19 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
     r->family = r->jit_fn ? FDOCT_KERNEL_WAVE_JIT : FDOCT_KERNEL_WAVE;
   else if (run_generic) {
     r->family = h->plan.gen.use_big ? FDOCT_KERNEL_LONG_ROWS : FDOCT_KERNEL_GENERIC;
+    if (!h->plan.gen.use_big) {
+      r->lds = generic_lds_bytes(plan_inputs(h), h->plan.gen);
+      // generic_kernel is compiled for 6 waves per SIMD = 6 workgroups of 4 waves per CU
+      const int per_cu = std::clamp((int)((160 * 1024 - 1024) / r->lds), 1, 6);
+      r->grid = std::min<long long>((long long)h->num_cu * per_cu, out_rows);
+    }
     // the cliff an integrator should see: rows in HBM run an order of magnitude below their LDS-resident neighbours
     if (h->plan.gen.use_big)
       h->jit_note = "this geometry runs on the long-row path (rows in HBM, fdoct_big.hip: one launch per group of DFT passes): its transforms do not fit "
                     "the 160 KB of LDS of a compute unit; expect 1e6 ... 1e7 A-scans/s where LDS-resident rows reach 1e8";
   }
   else
-    r->family = h->staged ? FDOCT_KERNEL_FUSED_STAGED : (r->tro ? FDOCT_KERNEL_FUSED_TRANSPOSED : FDOCT_KERNEL_FUSED);
+    r->family = h->staged ? FDOCT_KERNEL_FUSED_STAGED : (r->fused.tro ? FDOCT_KERNEL_FUSED_TRANSPOSED : FDOCT_KERNEL_FUSED);
   return FDOCT_OK;
 }
 
@@ -578,21 +595,11 @@ int launch_family_wave(fdoct_ctx* h, const Route& r, const Call& c) {
     }
   }
 #endif
-  const size_t shared = wave_shared_lds_bytes(wa.tw_count, W, h->M, h->N, wa.ib_2d != 0, r.wave_opt);
-  const size_t priv = wave_private_lds_bytes(W, h->M, h->N, r.wave_opt);
-  int waves = (int)((160 * 1024 - 64 - shared) / priv);  // >= 1: choose_route
-  if (waves > wave_max_waves(W, h->M, h->N, r.wave_opt)) waves = wave_max_waves(W, h->M, h->N, r.wave_opt);
-  if (h->block_override && h->block_override / 64 >= 1 && h->block_override / 64 <= waves) waves = h->block_override / 64;
-  long long wgrid = h->num_cu;
-  const int rpw_ = wave_rows_per_wave(W, h->M, h->N, r.wave_opt);   // (two rows per wave on the short zero-padded shapes)
-  const long long need = (c.out_rows + (long long)waves * rpw_ - 1) / ((long long)waves * rpw_);
-  if (h->grid_override > 0) wgrid = h->grid_override;
-  if (wgrid > need) wgrid = need;
   if (h->record_now && h->rec_first) HIP_TRY(h, hipEventRecord(h->ev[1], c.st));
   if (r.jit_fn)
-    HIP_TRY(h, wave_jit_launch(r.jit_fn, wa, (int)wgrid, waves, shared + (size_t)waves * priv, c.st));
+    HIP_TRY(h, wave_jit_launch(r.jit_fn, wa, (int)r.grid, r.waves, r.lds, c.st));
   else
-    HIP_TRY(h, launch_wave(W, h->M, h->N, wa, (int)wgrid, waves, shared + (size_t)waves * priv, c.st));
+    HIP_TRY(h, launch_wave(W, h->M, h->N, wa, (int)r.grid, r.waves, r.lds, c.st));
   return finish_launch(h, r, c, false);
 }
 
@@ -689,14 +696,8 @@ int launch_family_generic(fdoct_ctx* h, const Route& r, const Call& c) {
       ga.row_ticket = t;
     }
   }
-  const size_t glds = generic_lds_bytes(in, gp);
-  int per_cu = (int)((160 * 1024 - 1024) / glds);
-  if (per_cu > 6) per_cu = 6;  // generic_kernel is compiled for 6 waves per SIMD = 6 workgroups of 4 waves per CU
-  if (per_cu < 1) per_cu = 1;
-  long long ggrid = (long long)h->num_cu * per_cu;
-  if (ggrid > c.out_rows) ggrid = c.out_rows;
   if (h->record_now && h->rec_first) HIP_TRY(h, hipEventRecord(h->ev[1], c.st));
-  HIP_TRY(h, launch_generic(ga, (int)ggrid, glds, c.st));
+  HIP_TRY(h, launch_generic(ga, (int)r.grid, r.lds, c.st));
   return finish_launch(h, r, c, false);
 }
 
@@ -824,91 +825,10 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
 #endif
 
   const FusedPlan& p = *h->plan.fused;
-  const bool cplx = h->plan.cplx;
-  const int NC = h->plan.NC, scratch_bytes = h->plan.scratch_bytes;
-  // the unpredicated fast-path kernel applies to the plain acquisition configuration
-  // (a full-frame background keeps the fast path on the row-swap plan: its resident registers prefetch the frame row)
-  const bool fast_opts = fused_resident_consts(p.kind, true, A > 1, p.WCH, 0) && c.out_rows < 0x7fffffffLL && !h->staged;
-  // (a full-frame background with the two-word reciprocal -- fdoct_set_precise_division -- runs on the any-option
-  // kernel: the fast path's prefetch registers hold one word per sample)
-  const bool bg_ok = h->yb.rows == 1 || (fast_opts && (!h->precise_div || fused_il_half(true, p.WCH)));
-  const bool norm_ok = !a.minmax || fast_opts;  // whole-frame normalisation has a fast-path variant there too
-  const bool lean = (r.kdt == FDOCT_K_U16 || r.kdt == FDOCT_K_U8) && W == 8 * p.T * p.WCH && bg_ok && !a.yp && !a.yd &&
-                    (!a.rowwisenormalize || fast_opts) && norm_ok && !h->force_general;
-  // launch geometry: as many waves per workgroup as LDS and the register budget allow
-  const int rpw = 64 / p.T;
-  a.lds_planes = fused_resident_consts(p.kind, lean, A > 1, p.WCH, 0) ? 0 : 1;
-  // 1/background as two floats (reciprocal_words): always on the any-option kernel, by fdoct_set_precise_division on the fast path
-  a.prec = (lean && !h->precise_div) ? 0 : (h->yb.rows == 1 ? 1 : 2);
-  // (the averaging fast-path kernels that keep their planes in LDS are bound by its capacity: a fourth 4 W-byte plane would cost
-  // C4 a wave per CU, so they read the low words from global memory instead)
-  // (only the kernels with more than 32 samples per lane have that form -- a compile-time property, fused_il_global: the others
-  // read the row's low words at its top from the LDS plane, resident constants or not -- fused_kernel's ILX)
-  // (staged mode: the kernel that reads the samples is the resample stage, compiled WITHOUT averaging whatever A is -- it runs
-  // over input A-scans -- so it takes its low words from the LDS plane like every non-averaging kernel)
-  if (a.prec == 1 && fused_il_global(lean, A > 1 && !h->staged, p.WCH, p.T)) a.prec = 3;
-  const size_t lds_const = const_lds_bytes(h, a.lds_planes != 0, a.prec == 1, fused_il_half(lean, p.WCH));
-  const size_t lds_max = 160 * 1024 - 64;  // the kernel's static row-ticket counter lives in LDS too
-  const int max_block = fused_max_block(NC, p.T, lean, p.kind);
-  int max_waves = max_block / 64;
-  // (a full-frame background with both words: every wave has a slot for the prefetched pattern row of its next A-scan)
-  const size_t dma_per_wave = fused_il16_dma_bytes(lean && h->yb.rows > 1, a.prec == 2 && fused_il_half(lean, p.WCH), r.tro, 8 * p.T * p.WCH);
-  const size_t per_wave = (size_t)scratch_bytes * rpw + dma_per_wave;
-  int waves = (int)((lds_max - lds_const) / per_wave);
-  if (waves > max_waves) waves = max_waves;
-  if (h->block_override) {
-    int w = h->block_override / 64;
-    if (w >= 1 && w <= waves) waves = w;
-  }
-  if (waves < 1) return fail(h, FDOCT_ERR_UNSUPPORTED, "row does not fit in LDS");
-  const size_t lds = lds_const + (size_t)waves * per_wave;
-  const int blocks_per_cu = (int)(lds_max / lds) > 0 ? (int)(lds_max / lds) : 1;
-  const int wave_cap = (max_block / 64) / waves;  // register budget: max_block threads per CU
-  int bpc = blocks_per_cu < wave_cap ? blocks_per_cu : wave_cap;
-  if (bpc < 1) bpc = 1;
-  long long need = (c.out_rows + (long long)waves * rpw - 1) / ((long long)waves * rpw);
-  long long grid = (long long)h->num_cu * bpc;
-  if (h->grid_override > 0) grid = h->grid_override;
-  if (grid > need) grid = need;
-  if (grid < 1) grid = 1;
-
-  size_t lds_launch = lds;
-  int block_launch = waves * 64;
-  if (r.tro) {
-    if (!lean) return fail(h, FDOCT_ERR_DEVICE, "internal: fused transposed store chosen for a configuration off the fast path");
-    // computing waves + the write-out wave; LDS: constants, one row buffer per computing wave, the ring of finished rows.
-    // As many computing waves as the register budget allows, then the largest ring that fits (round 5: the store is bound by
-    // how much of the next tile fits into the ring while a tile drains, so the kernel keeps its once-read tables out of LDS);
-    // a wave is given up only where not even the smallest ring fits next to them.
-    const size_t tro_const = tro_const_lds_bytes(h, r.kdt == FDOCT_K_U8 ? 1 : 2, a.minmax != nullptr);
-    const int ww = fused_tro_writer_waves();
-    int cw = max_waves - ww;
-    if (h->block_override && h->block_override / 64 - ww >= 1 && h->block_override / 64 - ww < cw) cw = h->block_override / 64 - ww;
-    static const unsigned ring_cap = [] { const char* e = std::getenv("FDOCT_TRO_RING"); return e ? (unsigned)std::atoi(e) : 0u; }();  // measurement: at most this many slots
-    unsigned slots = 0;
-    if (rpw == 4) {
-      // whole groups of four waves, as many as registers and LDS allow; no ring (the rows wait in the waves' own buffers)
-      constexpr int GW = fused_tro_group_waves();
-      while (cw >= GW && tro_const + (size_t)cw * scratch_bytes * rpw > lds_max) cw--;
-      cw = cw / GW * GW;
-      if (cw < GW) return fail(h, FDOCT_ERR_DEVICE, "internal: no group of waves fits the LDS (transposed store, four rows per wave)");
-    } else {
-      for (; cw >= 1; cw--) {
-        slots = fused_tro_ring_pick(lds_max - tro_const - (size_t)cw * scratch_bytes * rpw, D, rpw);
-        if (slots) break;
-      }
-      if (cw < 1 || !slots) return fail(h, FDOCT_ERR_DEVICE, "internal: no LDS left for the transposed store's ring");
-      if (ring_cap >= 20 && slots > ring_cap) slots = fused_tro_ring_pick((size_t)ring_cap * (size_t)(D + 4) * 4, D, rpw);
-    }
-    const size_t ring = (size_t)slots * (size_t)(D + 4) * 4;
-    a.tr_ring = slots;
-    block_launch = (cw + ww) * 64;
-    lds_launch = tro_const + (size_t)cw * scratch_bytes * rpw + ring;
-    const unsigned tile_rows = (unsigned)fused_tro_tile_rows(rpw);
-    const unsigned tpf = (unsigned)((H + tile_rows - 1) / tile_rows);
-    const long long tiles = (long long)c.G * tpf;
-    grid = h->grid_override > 0 ? h->grid_override : h->num_cu;   // one workgroup per CU (the ring fills its LDS)
-    if (grid > tiles) grid = tiles;
+  const FusedLaunch& l = r.fused;
+  a.lds_planes = l.lds_planes;
+  a.prec = l.prec;
+  if (l.tro) {
     if (!h->d_tro_fault) {
       // (coherent, mapped host memory: the buffer's flags, fdoct_ctx.h.  The kernels raise the word with a plain system-scope
       // STORE of 1 -- a read-modify-write atomic on host memory would need PCIe AtomicOps on the link and is dropped silently
@@ -919,38 +839,69 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
     h->tro_used = true;
     a.tr_fault = h->d_tro_fault;
     a.tro = 1;
-    a.tr_tpf = tpf;
-    a.tr_tpf_magic = tpf > 1 ? (unsigned)((1ull << 32) / tpf) : 0xffffffffu;
-    a.tr_total_tiles = (unsigned)tiles;
+    a.tr_ring = l.tro->ring;
+    a.tr_tpf = l.tro->tpf;
+    a.tr_tpf_magic = l.tro->tpf_magic;
+    a.tr_total_tiles = l.tro->total_tiles;
   }
   if (h->record_now && h->rec_first) HIP_TRY(h, hipEventRecord(h->ev[1], st));
+  h->ylin_rows = 0;
   if (h->staged) {
-    if (!lean || r.kdt != FDOCT_K_U16)
-      return fail(h, FDOCT_ERR_UNSUPPORTED, "staged mode is built for the plain u16 acquisition configuration only");
     // one k-linear row per INPUT A-scan between the stages: the resample stage runs over the in_rows input rows as they
     // lie (A = 1), the FFT stage gathers the A rows of an output A-scan
-    if ((rc = h->ws_ylin.reserve(h, (size_t)c.in_rows * NC * sizeof(float2)))) return rc;
+    if ((rc = h->ws_ylin.reserve(h, (size_t)c.in_rows * h->plan.NC * sizeof(float2)))) return rc;
     a.ylin = h->ws_ylin;
     h->ylin_rows = c.in_rows;
-    {
-      FusedArgs a1 = a;
-      a1.stage = 1;
-      a1.A = 1;
-      a1.inv_A = 1.f;
-      a1.total_out_rows = c.in_rows;
-      long long need1 = (c.in_rows + (long long)waves * rpw - 1) / ((long long)waves * rpw);
-      long long grid1 = h->grid_override > 0 ? h->grid_override : (long long)h->num_cu * bpc;
-      if (grid1 > need1) grid1 = need1;
-      HIP_TRY(h, launch_fused(p, a1, r.kdt, cplx, lean, (int)grid1, waves * 64, lds, st));
-    }
+    FusedArgs a1 = a;
+    a1.stage = 1;
+    a1.A = 1;
+    a1.inv_A = 1.f;
+    a1.total_out_rows = c.in_rows;
+    HIP_TRY(h, launch_fused(p, a1, r.kdt, h->plan.cplx, l.lean, (int)l.stage1_grid, l.block, l.lds, st));
     if (h->record_now) HIP_TRY(h, hipEventRecord(h->ev[4], st));
     a.stage = 2;
-    HIP_TRY(h, launch_fused(p, a, r.kdt, cplx, lean, (int)grid, waves * 64, lds, st));
-  } else {
-    h->ylin_rows = 0;
-    HIP_TRY(h, launch_fused(p, a, r.kdt, cplx, lean, (int)grid, block_launch, lds_launch, st));
   }
+  HIP_TRY(h, launch_fused(p, a, r.kdt, h->plan.cplx, l.lean, (int)l.grid, l.block, l.lds, st));
   return finish_launch(h, r, c, h->staged);
+}
+
+// The passes in front of the chain, as the route names them; leaves what the chain's kernel reads in c.kframes / c.kframes_lo
+// (r.kdt samples at r.kpitch bytes per row).
+static int run_passes_in_front(fdoct_ctx* h, const Route& r, Call& c, const void* d_frames, fdoct_dtype dtype, size_t pitch_bytes) {
+  const int W = h->W, n = h->cfg.movavgn;
+  hipStream_t st = c.st;
+  int rc;
+  size_t pitch = pitch_bytes;
+  if (r.frontend) {  // raw camera frames: medianBlur + binning first (main:953-958); the caller's pitch describes the RAW rows
+    void* fo = nullptr;
+    if ((rc = run_frontend(h, d_frames, kernel_dtype(dtype), c.nframes, W * h->fe_binx, h->H * h->fe_biny, pitch_bytes, h->fe_median, h->fe_binx,
+                           h->fe_biny, &fo, &pitch)))
+      return rc;
+    c.kframes = fo;
+  }
+  if (r.pre == PrePass::None) return FDOCT_OK;
+  // one f32 plane of packed rows, and where the pass keeps the sums in double a second one with their low words
+  DevBuf<float>& hi = r.pre == PrePass::F64Split ? h->ws_f32 : h->ws_mov;
+  DevBuf<float>& lo = r.pre == PrePass::F64Split ? h->ws_f32_lo : h->ws_mov_lo;
+  if ((rc = hi.reserve(h, (size_t)c.in_rows * W * 4))) return rc;
+  if (r.frames_lo() && (rc = lo.reserve(h, (size_t)c.in_rows * W * 4 + 32))) return rc;
+  switch (r.pre) {
+    case PrePass::F64Split:  // data_y doubles (main:987): split once into two f32 planes on the device, x = hi + lo
+      HIP_TRY(h, launch_f64_split(static_cast<const double*>(d_frames), (long long)(pitch_bytes / 8), hi, lo, W, c.in_rows, st));
+      break;
+    case PrePass::MovAvgF64:  // doubles through smoothmovavg (main:987-991): the tap sums in double, then the two planes
+      HIP_TRY(h, launch_movavg_f64(static_cast<const double*>(d_frames), (long long)(pitch_bytes / 8), W, c.in_rows, n, hi, lo, st));
+      break;
+    case PrePass::MovAvgF32Wide:  // ... of float frames: sums in double, two planes
+      HIP_TRY(h, launch_movavg_f32_wide(static_cast<const float*>(d_frames), (long long)(pitch_bytes / 4), W, c.in_rows, n, hi, lo, st));
+      break;
+    default:  // smoothmovavg (main:990-991) runs before everything else, on the raw samples
+      HIP_TRY(h, launch_movavg(c.kframes, kernel_dtype(dtype), (long long)pitch, W, c.in_rows, n, hi, st));
+      break;
+  }
+  c.kframes = hi;
+  c.kframes_lo = r.frames_lo() ? static_cast<const float*>(lo) : nullptr;
+  return FDOCT_OK;
 }
 
 // Enqueue the whole path for device-resident frames.  d_out_* are row-major or
@@ -983,50 +934,7 @@ int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nfram
   c.kframes = d_frames;
   hipStream_t st = c.st;
   if (h->record_now && h->rec_first) HIP_TRY(h, hipEventRecord(h->ev[0], st));
-  // ---- passes in front of the chain
-  int kdt_now = kernel_dtype(dtype);
-  size_t pitch_now = pitch_bytes;
-  if (r.frontend) {  // raw camera frames: medianBlur + binning first (main:953-958); the caller's pitch describes the RAW rows
-    void* fo = nullptr;
-    size_t fp = 0;
-    if ((rc = run_frontend(h, d_frames, kdt_now, nframes, W * h->fe_binx, H * h->fe_biny, pitch_bytes, h->fe_median, h->fe_binx, h->fe_biny, &fo, &fp)))
-      return rc;
-    c.kframes = fo;
-    pitch_now = fp;
-  }
-  if (r.narrow_f64 && r.movavg) {  // doubles through smoothmovavg (main:987-991): the tap sums in double, then the two planes
-    if ((rc = h->ws_mov.reserve(h, (size_t)c.in_rows * W * 4))) return rc;
-    if ((rc = h->ws_mov_lo.reserve(h, (size_t)c.in_rows * W * 4 + 32))) return rc;
-    HIP_TRY(h, launch_movavg_f64(static_cast<const double*>(d_frames), (long long)(pitch_bytes / 8), W, c.in_rows, h->cfg.movavgn, h->ws_mov, h->ws_mov_lo, st));
-    c.kframes = h->ws_mov;
-    c.kframes_lo = h->ws_mov_lo;
-    pitch_now = (size_t)W * 4;
-    kdt_now = FDOCT_K_F32;
-  } else if (r.narrow_f64) {  // data_y doubles (main:987): split once into two f32 planes on the device, x = hi + lo
-    if ((rc = h->ws_f32.reserve(h, (size_t)c.in_rows * W * 4))) return rc;
-    if ((rc = h->ws_f32_lo.reserve(h, (size_t)c.in_rows * W * 4 + 32))) return rc;
-    HIP_TRY(h, launch_f64_split(static_cast<const double*>(d_frames), (long long)(pitch_bytes / 8), h->ws_f32, h->ws_f32_lo, W, c.in_rows, st));
-    c.kframes = h->ws_f32;
-    c.kframes_lo = h->ws_f32_lo;
-    pitch_now = (size_t)W * 4;
-    kdt_now = FDOCT_K_F32;
-  }
-  if (r.movavg && r.mov_lo && !r.narrow_f64) {  // ... of float frames: sums in double, two planes
-    if ((rc = h->ws_mov.reserve(h, (size_t)c.in_rows * W * 4))) return rc;
-    if ((rc = h->ws_mov_lo.reserve(h, (size_t)c.in_rows * W * 4 + 32))) return rc;
-    HIP_TRY(h, launch_movavg_f32_wide(static_cast<const float*>(c.kframes), (long long)(pitch_now / 4), W, c.in_rows, h->cfg.movavgn, h->ws_mov, h->ws_mov_lo, st));
-    c.kframes = h->ws_mov;
-    c.kframes_lo = h->ws_mov_lo;
-    pitch_now = (size_t)W * 4;
-    kdt_now = FDOCT_K_F32;
-  } else if (r.movavg && !r.narrow_f64) {  // smoothmovavg (main:990-991) runs before everything else, on the raw samples
-    if ((rc = h->ws_mov.reserve(h, (size_t)c.in_rows * W * 4))) return rc;
-    HIP_TRY(h, launch_movavg(c.kframes, kdt_now, (long long)pitch_now, W, c.in_rows, h->cfg.movavgn, h->ws_mov, st));
-    c.kframes = h->ws_mov;
-    pitch_now = (size_t)W * 4;
-    kdt_now = FDOCT_K_F32;
-  }
-  if (kdt_now != r.kdt || pitch_now != r.kpitch) return fail(h, FDOCT_ERR_DEVICE, "internal: the route and the passes in front of the chain disagree");
+  if ((rc = run_passes_in_front(h, r, c, d_frames, dtype, pitch_bytes))) return rc;
   if (r.need_minmax) {
     // [nframes] results followed by the fast kernel's per-workgroup partials
     const size_t mm_elems = (size_t)nframes + (size_t)minmax_partial_count(nframes);
@@ -1071,11 +979,15 @@ int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, 
   long long cg = per_group ? (long long)(h->tr_chunk_bytes / per_group) : G;
   if (cg < 1) cg = 1;
   if (G <= cg) return enqueue_one(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
-  if (fused_transposed_store_applies(h, dtype, d_frames, pitch_bytes, d_out_bscan, d_out_db, nframes))  // no intermediate at all
-    return enqueue_one(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
   const size_t es = dtype_size(dtype);
   if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
   const size_t pitch = pitch_bytes ? pitch_bytes : es * (size_t)h->W * h->fe_binx;
+  {  // the whole call's route: where the chain writes D x H itself there is no intermediate at all, and nothing to cut
+    DEVICE_SCOPE(h);
+    Route whole;
+    if (h->yb.rows && choose_route(h, dtype, (uintptr_t)d_frames, pitch, (uintptr_t)d_out_bscan, (uintptr_t)d_out_db, layout, nframes, &whole) == FDOCT_OK && whole.fused.tro)
+      return enqueue_one(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
+  }
   const size_t frame_stride = pitch * (size_t)h->H * h->fe_biny;  // raw camera rows when a front end is set
   const size_t out_group = (size_t)h->H * h->D;
   uint64_t ascans = 0, bin = 0, bout = 0;

@@ -61,30 +61,6 @@ int adopt_plan(fdoct_ctx* h, const PlanInputs& in) {
   return FDOCT_OK;
 }
 
-// planes: the three constant planes are staged in LDS (kernels that do not keep them in registers); il_plane: so is the low
-// word of the reciprocal background (FusedArgs::prec == 1)
-// il_half: that plane holds half floats (the fast-path kernels with at most 32 samples per lane: fused_il_half)
-// tw3 / gi: the step-5 twiddle table and the gather table are staged (the transposed-store kernels leave out what they hold in
-// registers: fused_tw3_in_lds / fused_gi_in_lds)
-size_t const_lds_bytes(const fdoct_ctx* h, bool planes, bool il_plane, bool il_half, bool tw3, bool gi) {
-  const Plan& pl = h->plan;
-  const int WC = 8 * pl.fused->T * pl.fused->WCH;
-  const size_t tw_entries = tw3 ? (size_t)pl.tw_count : (size_t)(pl.fused->R2 - 1) * pl.fused->R1;
-  return (planes ? (size_t)3 : 0) * WC * 4 + (il_plane ? (size_t)WC * (il_half ? 2 : 4) : 0) + tw_entries * 8 + (pl.cplx ? (size_t)pl.NC * 8 : 0) + (gi ? (size_t)pl.NC * 4 : 0);
-}
-// constants of a transposed-store launch (fast path, 1024-point row-swap plan)
-size_t tro_const_lds_bytes(const fdoct_ctx* h, int sample_bytes, bool normalize) {
-  const FusedPlan& p = *h->plan.fused;
-  const bool both = h->precise_div, ib2d = h->yb.rows > 1, half = fused_il_half(true, p.WCH);
-  // (the row-swap plan's transposed-store kernels hold the constant planes in registers; the 512-point Stockham plan's read them
-  // from LDS like its row-major kernels, and its averaging kernels take the low words from global memory: fused_il_global)
-  const bool planes = !fused_resident_consts(p.kind, true, h->A > 1, p.WCH, 0);
-  const bool il_plane = both && !ib2d && !fused_il_global(true, h->A > 1, p.WCH, p.T);
-  return const_lds_bytes(h, planes, il_plane, half, fused_tw3_in_lds(p.kind, true, 0, true, ib2d && both && half),
-                         fused_gi_in_lds(p.kind, true, 0, false, h->A > 1, true,
-                                         fused_tro_pf2(p.kind, true, 0, false, h->A > 1, true, ib2d, normalize ? 1 : 0, sample_bytes)));
-}
-
 // main:1132 divides by data_yb in double.  The kernels multiply by the reciprocal, held as an unevaluated sum of two floats
 // ib + il = 1/yb to 2^-48: ib = fl32(1/yb) alone is off by up to 6e-8 of the quotient -- a fixed per-column pattern of the
 // size of the DC level, which the chain turns into up to 4e-6 of the DC level per depth bin: more than the whole tolerance

@@ -323,7 +323,8 @@ int fdoct_last_kernel(fdoct_handle h);
  * (fdoct_set_jit below) -- that kernel is compiled (0.3-0.9 s) or loaded from the disk cache.  An acquisition loop calls it once
  * after the setters so that its first frame does not stall.  `dtype` / `layout`: what the loop will pass (device frames,
  * 16-byte aligned, packed rows are assumed; a call that differs still works, it just resolves again).  Returns the
- * fdoct_kernel that fdoct_process* will take (> 0), or a negative error code.  Needs the background. */
+ * fdoct_kernel that fdoct_process* will take (> 0), or a negative error code -- the one that call would return where the
+ * configuration cannot launch (a row that does not fit the LDS, staged mode off its configuration).  Needs the background. */
 int fdoct_prepare(fdoct_handle h, fdoct_dtype dtype, fdoct_layout layout);
 
 /* Run-time specialisation (on by default; fdoct_set_jit(h, 0) or FDOCT_JIT=0 in the environment turns it off).  The

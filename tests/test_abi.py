@@ -116,29 +116,49 @@ def test_out_of_host_memory_in_an_entry_point_is_an_error_code(tmp_path):
     assert lines[-1] == "ok" and len(lines) == 4, out.stdout
 
 
-def test_plan_decisions_match_the_recorded_table(tmp_path):
-    """make_plan (fdoct_amd/csrc/fdoct_plan.h) decides, for every configuration of tests/native/plan_check.cpp's grid -- the
-    BASELINE shapes, the shipped ini shapes, odd widths, Bluestein lengths, in-place half lengths, rows beyond the LDS, with and
-    without a phase, every plan override, with and without force_general --, exactly what plan_check.expected recorded from the
-    planner before the plan was a value: the fused plan and its geometry, or the generic path, and the generic plan."""
+def _native_table(tmp_path, name):
+    """Builds tests/native/<name>.cpp the way a C++ host links the library, runs it with the measurement switches of the
+    environment off, and returns (printed lines, lines of tests/native/<name>.expected)."""
     import shutil
     import subprocess
     cxx = shutil.which("g++")
     if not cxx:
         pytest.skip("no g++")
-    exe = tmp_path / "plan_check"
+    exe = tmp_path / name
     native = os.path.join(ROOT, "tests", "native")
     libdir = os.path.dirname(fdoct_amd.library_path())
     cmd = [cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "fdoct_amd", "csrc"),
-           os.path.join(native, "plan_check.cpp"), "-o", str(exe),
+           os.path.join(native, name + ".cpp"), "-o", str(exe),
            "-L", libdir, "-lfdoct_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
-    env = {k: v for k, v in os.environ.items() if not k.startswith("FDOCT_")}  # (the planner's measurement switches: off)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("FDOCT_")}
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
-    got = out.stdout.splitlines()
-    want = open(os.path.join(native, "plan_check.expected")).read().splitlines()
+    return out.stdout.splitlines(), open(os.path.join(native, name + ".expected")).read().splitlines()
+
+
+def test_fused_launch_decisions_match_the_recorded_table(tmp_path):
+    """make_fused_launch (fdoct_amd/csrc/fdoct_launch.h) decides, for every handle and call of tests/native/launch_check.cpp's
+    grid -- every shape of plan_check.cpp with a fused plan and C1 as stated, with and without a phase; 1 and 16 averages; u8 /
+    u16 / f32 samples; one-row and full-frame background; one and both words of the reciprocal; pi frame, dark frame, row-wise
+    and whole-frame normalisation, low-word plane, the any-option kernel, staged mode; set_launch overrides of block and grid;
+    8 and 262 000 A-scans; the transposed store on 8 / 500 / 1000 rows and 256 / 512 / 1024 depth bins with the ring cap --,
+    exactly what launch_check.expected recorded: kernel form, block, LDS, grid, ring and tiles, or the refusal and its text.  The
+    table was recorded from the arithmetic moved as it stood in launch_family_fused and fused_transposed_store_applies, before
+    their two copies were made one."""
+    got, want = _native_table(tmp_path, "launch_check")
+    assert len(got) == len(want) and len(want) > 600
+    diff = [(w, g) for w, g in zip(want, got) if w != g]
+    assert not diff, "%d launches differ, first: %s" % (len(diff), diff[0])
+
+
+def test_plan_decisions_match_the_recorded_table(tmp_path):
+    """make_plan (fdoct_amd/csrc/fdoct_plan.h) decides, for every configuration of tests/native/plan_check.cpp's grid -- the
+    BASELINE shapes, the shipped ini shapes, odd widths, Bluestein lengths, in-place half lengths, rows beyond the LDS, with and
+    without a phase, every plan override, with and without force_general --, exactly what plan_check.expected recorded from the
+    planner before the plan was a value: the fused plan and its geometry, or the generic path, and the generic plan."""
+    got, want = _native_table(tmp_path, "plan_check")
     assert len(got) == len(want)
     diff = [(w, g) for w, g in zip(want, got) if w != g]
     assert not diff, "%d decisions differ, first: %s" % (len(diff), diff[0])

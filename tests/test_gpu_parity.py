@@ -992,6 +992,34 @@ def test_staged_mode_equals_fused_chain():
     helpers.check_mag(b, mag_o, "complex N=4096 (generic kernel)")
 
 
+def test_staged_refusal_comes_from_the_route_before_anything_is_enqueued():
+    """A handle staged mode is not built for (a pi frame) is refused where the route is decided: prepare() raises what process()
+    raises, with the same text, instead of naming a kernel family the first call cannot run; and the refused process() leaves
+    nothing half-enqueued behind -- with staged mode off again the handle computes bit for bit what a fresh handle does."""
+    cfg = Config(width=2048, height=8, numfftpoints=2048, numdisplaypoints=1024)
+    frames, yb = synth.make_frames(0, 2, 2048, 8), synth.make_background(2048)
+    r = Reconstructor(cfg)
+    r.set_background(yb)
+    r.set_pi_frame(yb // 4)
+    r.set_staged(True)
+    with pytest.raises(FdoctError) as at_prepare:
+        r.prepare()
+    with pytest.raises(FdoctError) as at_process:
+        r.process(frames)
+    assert "staged mode is built for the plain u16 acquisition configuration only" in str(at_process.value)
+    assert str(at_prepare.value) == str(at_process.value) and at_prepare.value.code == at_process.value.code
+    r.set_staged(False)
+    b1, d1 = r.process(frames)
+    r.close()
+    fresh = Reconstructor(cfg)
+    fresh.set_background(yb)
+    fresh.set_pi_frame(yb // 4)
+    b0, d0 = fresh.process(frames)
+    fresh.close()
+    np.testing.assert_array_equal(b1, b0)
+    np.testing.assert_array_equal(d1, d0)
+
+
 def _parity_generic(cfg, frames, yb, what, force_generic=False, **kw):
     r = Reconstructor(cfg)
     r.set_background(yb)
