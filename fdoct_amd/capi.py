@@ -95,6 +95,11 @@ ROI_ABI_SYMBOLS = [
     "fdoct_clear_peakhold", "fdoct_vibration_profile", "fdoct_besseldb_inverse",
 ]
 
+# every symbol include/fdoct_capture.h declares: the reference frames captured from camera frames, likewise on their own
+CAPTURE_ABI_SYMBOLS = ["fdoct_capture_reference", "fdoct_get_reference", "fdoct_frame_minmax", "fdoct_normalize_minmax"]
+# fdoct_ref_role (include/fdoct_capture.h)
+REF_BACKGROUND, REF_PI, REF_DARK, REF_NONE = range(4)
+
 # fdoct_kernel (include/fdoct.h): what fdoct_last_kernel returns
 KERNEL_NONE, KERNEL_FUSED, KERNEL_FUSED_TRANSPOSED, KERNEL_FUSED_STAGED, KERNEL_WAVE, KERNEL_WAVE_JIT, KERNEL_GENERIC, KERNEL_LONG_ROWS = range(8)
 
@@ -203,6 +208,12 @@ def load_library():
     lib.fdoct_clear_peakhold.argtypes = [C.c_void_p, C.c_int]
     lib.fdoct_vibration_profile.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fdoct_besseldb_inverse.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    # include/fdoct_capture.h
+    lib.fdoct_capture_reference.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p]
+    lib.fdoct_get_reference.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+    lib.fdoct_frame_minmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p,
+                                       C.c_int]
+    lib.fdoct_normalize_minmax.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_double]
     _lib = lib
     return lib
 
@@ -267,6 +278,28 @@ def besseldb_inverse(y):
     if rc:
         raise FdoctError(rc, "fdoct_besseldb_inverse: bad arguments")
     return out
+
+
+def normalize_minmax(y, lo=0.0, hi=1.0):
+    """fdoct_normalize_minmax: cv::normalize(y, y, lo, hi, NORM_MINMAX) on a copy of y as float64.  Needs no GPU."""
+    a = np.array(y, np.float64, order="C")
+    rc = load_library().fdoct_normalize_minmax(a.ctypes.data if a.size else None, a.size, lo, hi)
+    if rc:
+        raise FdoctError(rc, "fdoct_normalize_minmax: bad arguments")
+    return a
+
+
+def _frame_batch(frames):
+    """Host camera frames as (array, nframes, row pitch in bytes): (nframes, rows, cols) of u8 / u16 / f32 / f64, rows contiguous."""
+    a = np.asarray(frames)
+    if a.dtype not in _NP2DT:
+        a = a.astype(np.float64)
+    if a.ndim == 2:
+        a = a[None]
+    n, r, c = a.shape
+    if a.strides[2] != a.itemsize or a.strides[0] != a.strides[1] * r or a.strides[1] < c * a.itemsize:
+        a = np.ascontiguousarray(a)
+    return a, n, a.strides[1]
 
 
 def _db_batch(db, layout):
@@ -549,6 +582,45 @@ class Reconstructor:
         self._check(self.lib.fdoct_vibration_profile(self.h, mode, -1.0 if lambda0 is None else float(lambda0),
                                                      prof.ctypes.data if prof.size else None, C.byref(disp), C.byref(err)))
         return prof, disp.value, err.value
+
+    # -- reference frames captured from camera frames (include/fdoct_capture.h).  Host frames are (nframes, rows, cols) arrays in
+    # the format process() takes (RAW camera frames when a front end is set); a view with padded rows passes its pitch on.
+    def capture_reference(self, role, frames, out=False):
+        """The b / p / dark key on host frames: the result becomes the handle's frame of `role` (REF_NONE: no state changes).
+        out=True returns it as float64 (H, W)."""
+        a, n, pitch = _frame_batch(frames)
+        res = np.empty((self.cfg.height, self.cfg.width), np.float64) if out else None
+        self._check(self.lib.fdoct_capture_reference(self.h, role, a.ctypes.data, _NP2DT[a.dtype], MEM_HOST, n, pitch,
+                                                     res.ctypes.data if out else None))
+        return res
+
+    def capture_reference_device(self, role, d_ptr, dtype, nframes, pitch=0, out=False):
+        """... on device-resident frames (raw device address)."""
+        res = np.empty((self.cfg.height, self.cfg.width), np.float64) if out else None
+        self._check(self.lib.fdoct_capture_reference(self.h, role, d_ptr, dtype, MEM_DEVICE, nframes, pitch,
+                                                     res.ctypes.data if out else None))
+        return res
+
+    def get_reference(self, role):
+        """The frame `role` holds as float64 (rows, W), rows 1 or H; None when unset."""
+        rows = C.c_int()
+        self._check(self.lib.fdoct_get_reference(self.h, role, None, 0, C.byref(rows)))
+        if rows.value == 0:
+            return None
+        a = np.empty((rows.value, self.cfg.width), np.float64)
+        self._check(self.lib.fdoct_get_reference(self.h, role, a.ctypes.data, a.size, C.byref(rows)))
+        return a
+
+    def frame_minmax(self, frames):
+        """"Max intensity" (BscanFFT.cpp:1105-1108): (min, max) float64[nframes] of every frame after the front end."""
+        a, n, pitch = _frame_batch(frames)
+        lo, hi = np.empty(n, np.float64), np.empty(n, np.float64)
+        self._check(self.lib.fdoct_frame_minmax(self.h, a.ctypes.data, _NP2DT[a.dtype], MEM_HOST, n, pitch, lo.ctypes.data,
+                                                hi.ctypes.data, MEM_HOST))
+        return lo, hi
+
+    def frame_minmax_device(self, d_ptr, dtype, nframes, pitch, d_min_ptr, d_max_ptr):
+        self._check(self.lib.fdoct_frame_minmax(self.h, d_ptr, dtype, MEM_DEVICE, nframes, pitch, d_min_ptr, d_max_ptr, MEM_DEVICE))
 
     # -- work
     def _out_shape(self, nframes, layout):

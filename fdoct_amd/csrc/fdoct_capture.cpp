@@ -1,0 +1,169 @@
+// fdoct_capture.cpp -- the extern "C" entry points of include/fdoct_capture.h: the handle's background / pi / dark frame
+// captured from camera frames (the b / p key handlers, BscanFFT.cpp:1000-1099; BscanDark.cpp:1005-1190) and the per-frame
+// min / max of the "Max intensity" line, over the kernels of fdoct_capture.hip.  The sums come back as H x W doubles -- the
+// handle keeps its reference frames as host doubles (RefFrame) -- and the normalisations run on them here, in the arithmetic
+// of fdoct_host.cpp::normalize_minmax.
+#include "../../include/fdoct_capture.h"
+
+#include "fdoct_capture_kernels.h"
+#include "fdoct_ctx.h"
+
+using namespace fdoct_impl;
+
+namespace {
+
+bool valid_mem(fdoct_memspace m) { return m == FDOCT_MEM_HOST || m == FDOCT_MEM_DEVICE; }
+bool has_frontend(const fdoct_ctx* h) { return h->fe_median > 0 || h->fe_binx > 1 || h->fe_biny > 1; }
+
+// What a call does with its frames, decided (and refused) before anything is enqueued.
+struct FramePlan {
+  const void* frames = nullptr;
+  fdoct_dtype dtype = FDOCT_U16;
+  bool host = false, frontend = false;
+  int nframes = 0, raw_w = 0, raw_h = 0;
+  size_t es = 0, pitch = 0;
+};
+
+int plan_frames(fdoct_ctx* h, const char* fn, const void* frames, fdoct_dtype dtype, fdoct_memspace space, int nframes,
+                size_t pitch_bytes, FramePlan* p) {
+  const std::string who = std::string(fn) + ": ";
+  if (!frames || !valid_mem(space) || nframes < 1) return fail(h, FDOCT_ERR_INVALID, who + "bad arguments");
+  const size_t es = dtype_size(dtype);
+  if (!es) return fail(h, FDOCT_ERR_INVALID, who + "bad dtype");
+  p->frames = frames, p->dtype = dtype, p->host = space == FDOCT_MEM_HOST, p->nframes = nframes, p->es = es;
+  p->frontend = has_frontend(h);
+  p->raw_w = h->W * (p->frontend ? h->fe_binx : 1);
+  p->raw_h = h->H * (p->frontend ? h->fe_biny : 1);
+  p->pitch = pitch_bytes ? pitch_bytes : es * (size_t)p->raw_w;
+  if (p->pitch < es * (size_t)p->raw_w) return fail(h, FDOCT_ERR_INVALID, who + "pitch smaller than a row");
+  if (p->pitch % es || reinterpret_cast<uintptr_t>(frames) % es)
+    return fail(h, FDOCT_ERR_INVALID, who + "frames and pitch must be aligned to one sample");
+  if (p->frontend) {
+    if (dtype != FDOCT_U8 && dtype != FDOCT_U16)
+      return fail(h, FDOCT_ERR_UNSUPPORTED, who + "the front end (median / binning) takes the camera's 8- or 16-bit frames");
+    if (h->fe_median == 7 && dtype == FDOCT_U16)
+      return fail(h, FDOCT_ERR_INVALID, who + "a 7x7 median exists for 8-bit frames only (cv::medianBlur)");
+  }
+  return FDOCT_OK;
+}
+
+// Enqueues what stands between the caller's frames and the kernels: the upload of host frames, then the front end.
+int stage_frames(fdoct_ctx* h, const FramePlan& p, fdoct::CaptureFrames* cf) {
+  const void* src = p.frames;
+  size_t pitch = p.pitch;
+  if (p.host) {
+    const size_t packed = (p.es * p.raw_w + 15) & ~(size_t)15;
+    if (int rc = h->ws_raw.reserve(h, packed * (size_t)p.raw_h * p.nframes)) return rc;
+    HIP_TRY(h, hipMemcpy2DAsync(h->ws_raw, packed, p.frames, p.pitch, p.es * p.raw_w, (size_t)p.raw_h * p.nframes,
+                                hipMemcpyHostToDevice, h->stream));
+    src = h->ws_raw;
+    pitch = packed;
+  }
+  if (p.frontend) {
+    void* fo = nullptr;
+    if (int rc = run_frontend(h, src, kernel_dtype(p.dtype), p.nframes, p.raw_w, p.raw_h, pitch, h->fe_median, h->fe_binx,
+                              h->fe_biny, &fo, &pitch))
+      return rc;
+    src = fo;
+  }
+  cf->frames = src, cf->dt = p.dtype, cf->pitch = pitch, cf->nframes = p.nframes, cf->H = h->H, cf->W = h->W;
+  return FDOCT_OK;
+}
+
+RefFrame* ref_of(fdoct_ctx* h, int role) {
+  return role == FDOCT_REF_BACKGROUND ? &h->yb : role == FDOCT_REF_PI ? &h->yp : role == FDOCT_REF_DARK ? &h->yd : nullptr;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ C ABI --
+extern "C" {
+
+int fdoct_capture_reference(fdoct_handle h, int role, const void* frames, fdoct_dtype dtype, fdoct_memspace space, int nframes,
+                            size_t pitch_bytes, double* out_host) try {
+  if (!h) return FDOCT_ERR_INVALID;
+  if (role < FDOCT_REF_BACKGROUND || role > FDOCT_REF_NONE) return fail(h, FDOCT_ERR_INVALID, "fdoct_capture_reference: bad role");
+  FramePlan p;
+  if (int rc = plan_frames(h, "fdoct_capture_reference", frames, dtype, space, nframes, pitch_bytes, &p)) return rc;
+  const bool sim = h->cfg.variant == FDOCT_VARIANT_SIM;
+  // sim:803-825: data_yb / data_yp are the binned frame itself
+  const bool plain_copy = sim && (role == FDOCT_REF_BACKGROUND || role == FDOCT_REF_PI);
+  if ((role == FDOCT_REF_PI || plain_copy) && nframes != 1)
+    return fail(h, FDOCT_ERR_INVALID, "fdoct_capture_reference: this role takes exactly one frame (main:1081, sim:803-825)");
+  DEVICE_SCOPE(h);
+  fdoct::CaptureFrames cf;
+  if (int rc = stage_frames(h, p, &cf)) return rc;
+  const size_t count = (size_t)h->H * h->W;
+  if (int rc = h->ws_cap_acc.reserve(h, count * sizeof(double))) return rc;
+  const int movavgn = (!sim && h->cfg.movavgn > 0) ? h->cfg.movavgn : 0;
+  const bool accumulates = !(role == FDOCT_REF_PI || plain_copy);  // (the p key copies one data_y, main:1081)
+  HIP_TRY(h, fdoct::launch_capture_accumulate(cf, movavgn, accumulates, h->ws_cap_acc, h->num_cu, h->stream));
+  std::vector<double> v(count);
+  HIP_TRY(h, hipMemcpyAsync(v.data(), h->ws_cap_acc, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (plain_copy) {
+    // sim:803-825: the frame as it is
+  } else if (role == FDOCT_REF_PI) {  // main:1093-1096
+    if (h->cfg.rowwisenormalize) normalize_rows(v.data(), h->H, h->W, 0, 1);
+    if (!h->cfg.donotnormalize) normalize_minmax(v.data(), count, 0, 1);
+  } else {  // main:1050-1057, BscanDark.cpp:1056-1063
+    if (h->cfg.rowwisenormalize) normalize_rows(v.data(), h->H, h->W, 0.0001, 1);
+    if (!h->cfg.donotnormalize)
+      normalize_minmax(v.data(), count, 0.0001, 1);
+    else
+      for (double& x : v) x = x / nframes;
+  }
+  if (out_host) std::memcpy(out_host, v.data(), count * sizeof(double));
+  if (RefFrame* dst = ref_of(h, role)) {  // the commit: nothing above changed the handle's state
+    dst->v = std::move(v);
+    dst->rows = h->H;
+    invalidate(h);
+  }
+  return FDOCT_OK;
+} FDOCT_CATCH(h)
+
+int fdoct_get_reference(fdoct_handle h, int role, double* out, size_t cap_doubles, int* rows) try {
+  if (!h) return FDOCT_ERR_INVALID;
+  const RefFrame* ref = ref_of(h, role);
+  if (!ref) return fail(h, FDOCT_ERR_INVALID, "fdoct_get_reference: role must be background, pi or dark");
+  if (!out && !rows) return fail(h, FDOCT_ERR_INVALID, "fdoct_get_reference: no output");
+  if (rows) *rows = ref->rows;
+  if (out) {
+    if (cap_doubles < ref->v.size()) return fail(h, FDOCT_ERR_INVALID, "fdoct_get_reference: buffer smaller than rows * width doubles");
+    if (!ref->v.empty()) std::memcpy(out, ref->v.data(), ref->v.size() * sizeof(double));
+  }
+  return FDOCT_OK;
+} FDOCT_CATCH(h)
+
+int fdoct_frame_minmax(fdoct_handle h, const void* frames, fdoct_dtype dtype, fdoct_memspace space, int nframes,
+                       size_t pitch_bytes, double* out_min, double* out_max, fdoct_memspace out_space) try {
+  if (!h) return FDOCT_ERR_INVALID;
+  if (!valid_mem(out_space) || (!out_min && !out_max)) return fail(h, FDOCT_ERR_INVALID, "fdoct_frame_minmax: no output");
+  if (nframes > 65535) return fail(h, FDOCT_ERR_INVALID, "fdoct_frame_minmax: at most 65535 frames per call");
+  FramePlan p;
+  if (int rc = plan_frames(h, "fdoct_frame_minmax", frames, dtype, space, nframes, pitch_bytes, &p)) return rc;
+  DEVICE_SCOPE(h);
+  fdoct::CaptureFrames cf;
+  if (int rc = stage_frames(h, p, &cf)) return rc;
+  const size_t n = (size_t)nframes;
+  if (int rc = h->ws_cap_mm.reserve(h, (2 * n + fdoct::frame_minmax_partials(cf, h->num_cu)) * sizeof(double))) return rc;
+  double* ws = h->ws_cap_mm;
+  const bool to_host = out_space == FDOCT_MEM_HOST;
+  double* d_min = to_host ? ws : out_min;
+  double* d_max = to_host ? ws + n : out_max;
+  HIP_TRY(h, fdoct::launch_frame_minmax(cf, ws + 2 * n, d_min, d_max, h->num_cu, h->stream));
+  if (to_host) {
+    if (out_min) HIP_TRY(h, hipMemcpyAsync(out_min, d_min, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (out_max) HIP_TRY(h, hipMemcpyAsync(out_max, d_max, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  if (to_host || p.host) HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return FDOCT_OK;
+} FDOCT_CATCH(h)
+
+int fdoct_normalize_minmax(double* y, size_t n, double lo, double hi) try {
+  if (n > 0 && !y) return FDOCT_ERR_INVALID;
+  normalize_minmax(y, n, lo, hi);
+  return FDOCT_OK;
+} FDOCT_CATCH(nullptr)
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 //                     per kernel family, enqueue
 //   fdoct_capi.cpp    the extern "C" entry points of include/fdoct.h
 //   fdoct_roi.cpp     those of include/fdoct_roi.h (the B-scan readouts)
+//   fdoct_capture.cpp those of include/fdoct_capture.h (reference frames captured from camera frames)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -200,6 +201,9 @@ struct fdoct_ctx {
   long long hold_count[4] = {0, 0, 0, 0};
   DevBuf<float> ws_roi_in;         // host-memory dB images on their way to the readouts
   DevBuf<double> ws_roi_out;       // ... and the per-B-scan results on their way back
+  // reference-frame capture (fdoct_capture.cpp): host frames go up through ws_raw, the front end through ws_med / ws_front
+  DevBuf<double> ws_cap_acc;       // the H x W sums on their way to the host
+  DevBuf<double> ws_cap_mm;        // per-frame min / max: the results (2 * nframes), then the per-block partials
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;

@@ -2,6 +2,7 @@
 // precision on the host, exactly in the reference's order of operations.
 #include "fdoct_host.h"
 
+#include <cfloat>
 #include <cmath>
 
 namespace fdoct {
@@ -99,6 +100,23 @@ void build_opencv_jet(unsigned char* bgr) {
       long v = std::lrint((double)scaled);  // round half to even (the default rounding mode), as cvRound / cvtps2dq
       bgr[3 * i + ch] = (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
     }
+}
+
+void normalize_minmax(double* y, size_t n, double lo, double hi) {
+  if (n == 0) return;
+  double smin = y[0], smax = y[0];
+  for (size_t i = 1; i < n; i++) {
+    if (y[i] < smin) smin = y[i];
+    if (y[i] > smax) smax = y[i];
+  }
+  const double dmin = lo < hi ? lo : hi, dmax = lo < hi ? hi : lo;
+  const double scale = (dmax - dmin) * (smax - smin > DBL_EPSILON ? 1. / (smax - smin) : 0);
+  const double shift = dmin - smin * scale;
+  for (size_t i = 0; i < n; i++) y[i] = y[i] * scale + shift;
+}
+
+void normalize_rows(double* y, int H, int W, double lo, double hi) {
+  for (int r = 0; r < H; r++) normalize_minmax(y + (size_t)r * W, (size_t)W, lo, hi);
 }
 
 }  // namespace fdoct

@@ -1,5 +1,6 @@
 // fdoct_host.h -- host-side (double precision) set-up arithmetic of the path.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <vector>
@@ -13,6 +14,12 @@ void build_resample_table(int W, int M, int N, double lambdamin, double lambdama
 void build_barthann(int W, std::vector<double>& win);
 // applyColorMap(.., COLORMAP_JET), BscanFFT.cpp:1284: OpenCV's 256-entry B,G,R table, built the way OpenCV builds it.
 void build_opencv_jet(unsigned char* bgr256);
+
+// cv::normalize(y, y, lo, hi, NORM_MINMAX) on n doubles (BscanFFT.cpp:1031, 1055, 1096): scale and shift from the min and
+// max, then y * scale + shift with the multiply and the add rounded separately (this file is built with -ffp-contract=off).
+void normalize_minmax(double* y, size_t n, double lo, double hi);
+// normalizerows, BscanFFT.cpp:88-97: every row on its own.
+void normalize_rows(double* y, int H, int W, double lo, double hi);
 
 struct GatherLayout {
   int split;      // 1: even samples at [0,WC/2), odd at [WC/2,WC)

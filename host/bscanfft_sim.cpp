@@ -10,7 +10,7 @@
 //                [--averages A] [--sim] [--lambdamin 816e-9 --lambdamax 884e-9]
 //                [--rowwisenormalize 0|1] [--donotnormalize 0|1] [--repeat K] [--threshold dB] --out prefix
 //                [--gpus N [--devices d0,d1,...]] [--precise-division | --one-word-division]
-//                [--roi-mean ascanat,vertpos,width]
+//                [--roi-mean ascanat,vertpos,width] [--capture-background N] [--max-intensity]
 //
 // --gpus N: one process, N handles (fdoct_clone_to_device), one host thread per handle; the frames are sharded with
 // fdoct_shard_frames (contiguous ranges, averaging groups never split -- the rule of the multi-process path,
@@ -20,12 +20,17 @@
 //
 // --roi-mean: the ROIreport readout of printAvgROI (BscanFFT.cpp:99-144) on every output B-scan, one line per B-scan in
 // the reference's text ("Mean of ROI at <ascanat> = <mean> dB"), computed on the GPU (include/fdoct_roi.h).
+// --capture-background N: the 'b' key of the acquisition programs (BscanFFT.cpp:1000-1075) instead of a background file: the
+// first N frames of --frames are accumulated and normalised into data_yb on the GPU (include/fdoct_capture.h) and are not
+// reconstructed; --background is then not needed.
+// --max-intensity: the status line's "Max intensity = <floor(max)>" (BscanFFT.cpp:1105-1108) for every reconstructed frame.
 // --frames holds one or more H x W frames back to back (u8 for --bits 8, little-endian u16 for --bits 16).
 // Outputs: <prefix>_bscan.f32 / <prefix>_bscandb.f32 (reference layout D x H per B-scan, main:1220) and
 // <prefix>.m with `bscan001=[...];` in the Matlab text form the reference's savematasdata writes
 // (main:333-339) for the first B-scan, plus the display images the reference shows/saves (main:1242-1255, 1284,
 // savematasimage): <prefix>_bscan001.pgm (grey) and <prefix>_bscanc001.ppm (colour-mapped).  Prints A-scans/s like the reference prints fps (sim:827-838).
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +41,7 @@
 #include <vector>
 
 #include "../include/fdoct.h"
+#include "../include/fdoct_capture.h"
 #include "../include/fdoct_roi.h"
 #include "ocv_io.h"
 
@@ -68,6 +74,8 @@ int main(int argc, char** argv) {
   std::vector<int> devices;
   double bscanthreshold = -30.0;  // main:385
   int roi[3] = {-1, 0, 0};         // --roi-mean ascanat,vertpos,width (-1: off)
+  int capture_bg = 0;              // --capture-background N (0: read --background)
+  bool max_intensity = false;      // --max-intensity
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -102,6 +110,8 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
+    else if (a == "--capture-background") capture_bg = std::atoi(next());
+    else if (a == "--max-intensity") max_intensity = true;
     else if (a == "--devices") {
       for (const char* p = next(); *p;) {
         devices.push_back(std::atoi(p));
@@ -114,7 +124,7 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
-  if (frames_path.empty() || bg_path.empty() || cfg.width <= 0 || cfg.height <= 0 || cfg.numfftpoints <= 0) {
+  if (frames_path.empty() || (bg_path.empty() && capture_bg <= 0) || capture_bg < 0 || cfg.width <= 0 || cfg.height <= 0 || cfg.numfftpoints <= 0) {
     std::fprintf(stderr, "usage: see the header of host/bscanfft_sim.cpp\n");
     return 1;
   }
@@ -143,10 +153,14 @@ int main(int argc, char** argv) {
     }
   };
   load(frames_path, &frames);
-  load(bg_path, &bg);
-  const int nframes_file = (int)(frames.size() / frame_bytes);
+  if (capture_bg == 0) load(bg_path, &bg);
+  const int nframes_file = (int)(frames.size() / frame_bytes) - capture_bg;  // (the captured frames are not reconstructed)
+  const unsigned char* live = frames.data() + (size_t)capture_bg * frame_bytes;
   if (nframes_file < 1) {
-    std::fprintf(stderr, "%s holds no complete %dx%d frame\n", frames_path.c_str(), cfg.width, cfg.height);
+    if (capture_bg > 0)
+      std::fprintf(stderr, "%s: no frames are left to reconstruct after the %d captured as the background\n", frames_path.c_str(), capture_bg);
+    else
+      std::fprintf(stderr, "%s holds no complete %dx%d frame\n", frames_path.c_str(), cfg.width, cfg.height);
     return 1;
   }
   const int nframes = nframes_file / cfg.averages * cfg.averages;
@@ -155,7 +169,8 @@ int main(int argc, char** argv) {
     return 1;
   }
   int bg_rows = 0;
-  if (bg.size() >= frame_bytes) bg_rows = cfg.height;
+  if (capture_bg > 0) bg_rows = cfg.height;
+  else if (bg.size() >= frame_bytes) bg_rows = cfg.height;
   else if (bg.size() >= (size_t)cfg.width * es) bg_rows = 1;
   else {
     std::fprintf(stderr, "background file too small\n");
@@ -169,9 +184,12 @@ int main(int argc, char** argv) {
     return 1;
   }
   // the 'b' key: data_yb <- backg (sim:803-813)
-  rc = fdoct_set_background(h, bg.data(), dt, bg_rows, 0);
+  if (capture_bg > 0)  // ... or the live 'b' key: accumulate(data_y, baccum) over the first frames, main:1041-1064
+    rc = fdoct_capture_reference(h, FDOCT_REF_BACKGROUND, frames.data(), dt, FDOCT_MEM_HOST, capture_bg, 0, nullptr);
+  else
+    rc = fdoct_set_background(h, bg.data(), dt, bg_rows, 0);
   if (rc) {
-    std::fprintf(stderr, "fdoct_set_background: %s\n", fdoct_last_error(h));
+    std::fprintf(stderr, "%s: %s\n", capture_bg > 0 ? "fdoct_capture_reference" : "fdoct_set_background", fdoct_last_error(h));
     return 1;
   }
   if (precise >= 0 && (rc = fdoct_set_precise_division(h, precise))) {
@@ -209,7 +227,7 @@ int main(int argc, char** argv) {
     if (count == 0) return;
     const size_t o0 = (size_t)(first / cfg.averages) * bscan_elems;
     for (int k = 0; k < repeat && !rcs[g]; k++)  // the while(1) loop, bounded; sim:842-955 per iteration
-      rcs[g] = fdoct_process(hs[g], frames.data() + (size_t)first * frame_bytes, dt, FDOCT_MEM_HOST, count, 0, bscan.data() + o0,
+      rcs[g] = fdoct_process(hs[g], live + (size_t)first * frame_bytes, dt, FDOCT_MEM_HOST, count, 0, bscan.data() + o0,
                              bscandb.data() + o0, FDOCT_MEM_HOST, FDOCT_LAYOUT_TRANSPOSED_DxH);
   };
   const auto t0 = std::chrono::steady_clock::now();
@@ -291,6 +309,16 @@ int main(int argc, char** argv) {
       return 1;
     }
     for (int g = 0; g < G; g++) std::printf("Mean of ROI at %d = %f dB\n", roi[0], mean[g]);
+  }
+  if (max_intensity) {
+    // minMaxLoc(opmvector, &minVal, &maxVal) of the status line, main:1105-1108, per frame
+    std::vector<double> mx(nframes);
+    rc = fdoct_frame_minmax(h, live, dt, FDOCT_MEM_HOST, nframes, 0, nullptr, mx.data(), FDOCT_MEM_HOST);
+    if (rc) {
+      std::fprintf(stderr, "fdoct_frame_minmax: %d %s\n", rc, fdoct_last_error(h));
+      return 1;
+    }
+    for (int f = 0; f < nframes; f++) std::printf("Max intensity = %d\n", int(std::floor(mx[f])));
   }
   for (fdoct_handle x : hs) fdoct_destroy(x);
   return 0;
