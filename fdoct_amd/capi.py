@@ -97,6 +97,8 @@ ROI_ABI_SYMBOLS = [
 
 # every symbol include/fdoct_capture.h declares: the reference frames captured from camera frames, likewise on their own
 CAPTURE_ABI_SYMBOLS = ["fdoct_capture_reference", "fdoct_get_reference", "fdoct_frame_minmax", "fdoct_normalize_minmax"]
+# every symbol include/fdoct_lowpass.h declares: BscanDark's lpfilter and the capture's two options, likewise on their own
+LOWPASS_ABI_SYMBOLS = ["fdoct_set_capture_options", "fdoct_get_capture_options", "fdoct_lowpass_rows"]
 # fdoct_ref_role (include/fdoct_capture.h)
 REF_BACKGROUND, REF_PI, REF_DARK, REF_NONE = range(4)
 
@@ -214,6 +216,10 @@ def load_library():
     lib.fdoct_frame_minmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p,
                                        C.c_int]
     lib.fdoct_normalize_minmax.argtypes = [C.c_void_p, C.c_size_t, C.c_double, C.c_double]
+    # include/fdoct_lowpass.h
+    lib.fdoct_set_capture_options.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.fdoct_get_capture_options.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.fdoct_lowpass_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int]
     _lib = lib
     return lib
 
@@ -621,6 +627,40 @@ class Reconstructor:
 
     def frame_minmax_device(self, d_ptr, dtype, nframes, pitch, d_min_ptr, d_max_ptr):
         self._check(self.lib.fdoct_frame_minmax(self.h, d_ptr, dtype, MEM_DEVICE, nframes, pitch, d_min_ptr, d_max_ptr, MEM_DEVICE))
+
+    # -- BscanDark's lpfilter and the capture's options (include/fdoct_lowpass.h)
+    def set_capture_options(self, lowpass=False, raw_accumulate=False):
+        """BscanDark.ini's lowpassfilter (lpfilter ends the capture of BACKGROUND / DARK / NONE) and saveinterferograms (the
+        capture skips the moving average)."""
+        self._check(self.lib.fdoct_set_capture_options(self.h, int(bool(lowpass)), int(bool(raw_accumulate))))
+
+    def get_capture_options(self):
+        """(lowpass, raw_accumulate) as bools."""
+        lp, raw = C.c_int(), C.c_int()
+        self._check(self.lib.fdoct_get_capture_options(self.h, C.byref(lp), C.byref(raw)))
+        return bool(lp.value), bool(raw.value)
+
+    def lowpass_rows(self, rows, out=None):
+        """lpfilter (BscanDark.cpp:119-167) on a float64 (rows, width) array, or one row, in host memory.  Returns a new array;
+        or filters into `out`, which has the rows' shape and strides (a view with padded rows passes its pitch on) and may be
+        `rows` itself."""
+        a = np.asarray(rows)
+        if out is None:
+            a = np.ascontiguousarray(a)
+            out = np.empty_like(a)
+        if a.dtype != np.float64 or a.ndim not in (1, 2) or a.size == 0 or a.strides[-1] != 8:
+            raise FdoctError(-1, "lowpass_rows takes float64 rows of contiguous samples")
+        if out.dtype != np.float64 or out.shape != a.shape or out.strides != a.strides:
+            raise FdoctError(-1, "out must be float64 of the rows' shape and strides")
+        nrows, width = (1, a.shape[0]) if a.ndim == 1 else a.shape
+        pitch = a.strides[0] if a.ndim == 2 and nrows > 1 else 0
+        self._check(self.lib.fdoct_lowpass_rows(self.h, a.ctypes.data, MEM_HOST, nrows, width, pitch, out.ctypes.data, MEM_HOST))
+        return out
+
+    def lowpass_rows_device(self, d_in_ptr, rows, width, pitch=0, d_out_ptr=None):
+        """... on device-resident rows (raw device addresses; d_out_ptr None: in place).  Enqueues on the handle's stream."""
+        self._check(self.lib.fdoct_lowpass_rows(self.h, d_in_ptr, MEM_DEVICE, rows, width, pitch,
+                                                d_in_ptr if d_out_ptr is None else d_out_ptr, MEM_DEVICE))
 
     # -- work
     def _out_shape(self, nframes, layout):

@@ -835,6 +835,8 @@ int fdoct_clone_to_device(fdoct_handle h, int device, fdoct_handle* out) try {
   c->fe_median = h->fe_median;
   c->fe_binx = h->fe_binx;
   c->fe_biny = h->fe_biny;
+  c->cap_lowpass = h->cap_lowpass;
+  c->cap_raw = h->cap_raw;
   c->bandpass = h->bandpass;
   c->jit = h->jit;
   c->precise_div = h->precise_div;

@@ -2,7 +2,8 @@
 // captured from camera frames (the b / p key handlers, BscanFFT.cpp:1000-1099; BscanDark.cpp:1005-1190) and the per-frame
 // min / max of the "Max intensity" line, over the kernels of fdoct_capture.hip.  The sums come back as H x W doubles -- the
 // handle keeps its reference frames as host doubles (RefFrame) -- and the normalisations run on them here, in the arithmetic
-// of fdoct_host.cpp::normalize_minmax.
+// of fdoct_host.cpp::normalize_minmax.  With the handle's low-pass option on (include/fdoct_lowpass.h) the normalised doubles go
+// back to the device once more, for lpfilter.
 #include "../../include/fdoct_capture.h"
 
 #include "fdoct_capture_kernels.h"
@@ -95,7 +96,8 @@ int fdoct_capture_reference(fdoct_handle h, int role, const void* frames, fdoct_
   if (int rc = stage_frames(h, p, &cf)) return rc;
   const size_t count = (size_t)h->H * h->W;
   if (int rc = h->ws_cap_acc.reserve(h, count * sizeof(double))) return rc;
-  const int movavgn = (!sim && h->cfg.movavgn > 0) ? h->cfg.movavgn : 0;
+  // saveinterferograms (fdoct_set_capture_options): the binned frames are accumulated as they are (main:1024)
+  const int movavgn = (!sim && h->cfg.movavgn > 0 && !h->cap_raw) ? h->cfg.movavgn : 0;
   const bool accumulates = !(role == FDOCT_REF_PI || plain_copy);  // (the p key copies one data_y, main:1081)
   HIP_TRY(h, fdoct::launch_capture_accumulate(cf, movavgn, accumulates, h->ws_cap_acc, h->num_cu, h->stream));
   std::vector<double> v(count);
@@ -112,6 +114,13 @@ int fdoct_capture_reference(fdoct_handle h, int role, const void* frames, fdoct_
       normalize_minmax(v.data(), count, 0.0001, 1);
     else
       for (double& x : v) x = x / nframes;
+    if (h->cap_lowpass) {  // lowpassfilter: lpfilter on the finished frame (BscanDark.cpp:1070-1074), in place on the device
+      const size_t row = sizeof(double) * (size_t)h->W;
+      HIP_TRY(h, hipMemcpyAsync(h->ws_cap_acc, v.data(), count * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      if (int rc = enqueue_lowpass(h, h->ws_cap_acc, row, h->ws_cap_acc, row, h->H, h->W)) return rc;
+      HIP_TRY(h, hipMemcpyAsync(v.data(), h->ws_cap_acc, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
   }
   if (out_host) std::memcpy(out_host, v.data(), count * sizeof(double));
   if (RefFrame* dst = ref_of(h, role)) {  // the commit: nothing above changed the handle's state

@@ -6,6 +6,7 @@
 //   fdoct_capi.cpp    the extern "C" entry points of include/fdoct.h
 //   fdoct_roi.cpp     those of include/fdoct_roi.h (the B-scan readouts)
 //   fdoct_capture.cpp those of include/fdoct_capture.h (reference frames captured from camera frames)
+//   fdoct_lowpass.cpp those of include/fdoct_lowpass.h (BscanDark's lpfilter, the capture's options)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -204,6 +205,11 @@ struct fdoct_ctx {
   // reference-frame capture (fdoct_capture.cpp): host frames go up through ws_raw, the front end through ws_med / ws_front
   DevBuf<double> ws_cap_acc;       // the H x W sums on their way to the host
   DevBuf<double> ws_cap_mm;        // per-frame min / max: the results (2 * nframes), then the per-block partials
+  // fdoct_set_capture_options (fdoct_lowpass.cpp): BscanDark.ini's lowpassfilter and the ini's saveinterferograms.  Run-time
+  // settings like the front end's: fdoct_clone_to_device carries them, the state blob does not.
+  int cap_lowpass = 0, cap_raw = 0;
+  DevBuf<double> ws_lp_io;         // fdoct_lowpass_rows: host rows on their way to the kernel and back (packed)
+  DevBuf<double> ws_lp_bins;       // rows too long for LDS: their bins (LowpassShape::ws_doubles)
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
@@ -379,5 +385,10 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
                  uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r);
 int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes,
             float* d_out_bscan, float* d_out_db, fdoct_layout layout);
+
+// ---- fdoct_lowpass.cpp ----------------------------------------------------------------------------------------------------
+// Enqueues lpfilter (BscanDark.cpp:119-167) on device rows of W doubles (d_in == d_out: in place) and reserves the workspace a
+// long row needs.  The arguments are the caller's to check.
+int enqueue_lowpass(fdoct_ctx* h, const double* d_in, size_t in_pitch, double* d_out, size_t out_pitch, int rows, int W);
 
 }  // namespace fdoct_impl

@@ -10,7 +10,7 @@
 //                [--averages A] [--sim] [--lambdamin 816e-9 --lambdamax 884e-9]
 //                [--rowwisenormalize 0|1] [--donotnormalize 0|1] [--repeat K] [--threshold dB] --out prefix
 //                [--gpus N [--devices d0,d1,...]] [--precise-division | --one-word-division]
-//                [--roi-mean ascanat,vertpos,width] [--capture-background N] [--max-intensity]
+//                [--roi-mean ascanat,vertpos,width] [--capture-background N [--capture-lowpass] [--capture-raw]] [--max-intensity]
 //
 // --gpus N: one process, N handles (fdoct_clone_to_device), one host thread per handle; the frames are sharded with
 // fdoct_shard_frames (contiguous ranges, averaging groups never split -- the rule of the multi-process path,
@@ -22,7 +22,9 @@
 // the reference's text ("Mean of ROI at <ascanat> = <mean> dB"), computed on the GPU (include/fdoct_roi.h).
 // --capture-background N: the 'b' key of the acquisition programs (BscanFFT.cpp:1000-1075) instead of a background file: the
 // first N frames of --frames are accumulated and normalised into data_yb on the GPU (include/fdoct_capture.h) and are not
-// reconstructed; --background is then not needed.
+// reconstructed; --background is then not needed.  --capture-lowpass ends that capture with BscanDark's lpfilter (the ini's
+// lowpassfilter), --capture-raw skips its moving average (the ini's saveinterferograms; include/fdoct_lowpass.h); with either,
+// the captured frame is also written as <prefix>_background.f64 (H x W doubles).
 // --max-intensity: the status line's "Max intensity = <floor(max)>" (BscanFFT.cpp:1105-1108) for every reconstructed frame.
 // --frames holds one or more H x W frames back to back (u8 for --bits 8, little-endian u16 for --bits 16).
 // Outputs: <prefix>_bscan.f32 / <prefix>_bscandb.f32 (reference layout D x H per B-scan, main:1220) and
@@ -42,6 +44,7 @@
 
 #include "../include/fdoct.h"
 #include "../include/fdoct_capture.h"
+#include "../include/fdoct_lowpass.h"
 #include "../include/fdoct_roi.h"
 #include "ocv_io.h"
 
@@ -75,6 +78,7 @@ int main(int argc, char** argv) {
   double bscanthreshold = -30.0;  // main:385
   int roi[3] = {-1, 0, 0};         // --roi-mean ascanat,vertpos,width (-1: off)
   int capture_bg = 0;              // --capture-background N (0: read --background)
+  int capture_lowpass = 0, capture_raw = 0;  // --capture-lowpass, --capture-raw: fdoct_set_capture_options
   bool max_intensity = false;      // --max-intensity
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -111,6 +115,8 @@ int main(int argc, char** argv) {
       }
     }
     else if (a == "--capture-background") capture_bg = std::atoi(next());
+    else if (a == "--capture-lowpass") capture_lowpass = 1;
+    else if (a == "--capture-raw") capture_raw = 1;
     else if (a == "--max-intensity") max_intensity = true;
     else if (a == "--devices") {
       for (const char* p = next(); *p;) {
@@ -184,9 +190,20 @@ int main(int argc, char** argv) {
     return 1;
   }
   // the 'b' key: data_yb <- backg (sim:803-813)
-  if (capture_bg > 0)  // ... or the live 'b' key: accumulate(data_y, baccum) over the first frames, main:1041-1064
-    rc = fdoct_capture_reference(h, FDOCT_REF_BACKGROUND, frames.data(), dt, FDOCT_MEM_HOST, capture_bg, 0, nullptr);
-  else
+  if (capture_bg > 0) {  // ... or the live 'b' key: accumulate(data_y, baccum) over the first frames, main:1041-1064
+    const bool options = capture_lowpass || capture_raw;
+    std::vector<double> captured(options ? (size_t)cfg.width * cfg.height : 0);
+    if (options && (rc = fdoct_set_capture_options(h, capture_lowpass, capture_raw))) {
+      std::fprintf(stderr, "fdoct_set_capture_options: %s\n", fdoct_last_error(h));
+      return 1;
+    }
+    rc = fdoct_capture_reference(h, FDOCT_REF_BACKGROUND, frames.data(), dt, FDOCT_MEM_HOST, capture_bg, 0,
+                                 options ? captured.data() : nullptr);
+    if (!rc && options) {
+      std::ofstream f(out + "_background.f64", std::ios::binary);
+      f.write(reinterpret_cast<const char*>(captured.data()), (std::streamsize)(captured.size() * sizeof(double)));
+    }
+  } else
     rc = fdoct_set_background(h, bg.data(), dt, bg_rows, 0);
   if (rc) {
     std::fprintf(stderr, "%s: %s\n", capture_bg > 0 ? "fdoct_capture_reference" : "fdoct_set_background", fdoct_last_error(h));

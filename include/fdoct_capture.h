@@ -35,10 +35,11 @@
  *   FDOCT_VARIANT_SIM BACKGROUND and PI are the (binned) frame as doubles: no moving average, no normalisation, no
  *                     division, nframes must be 1 (BscanFFTsim.cpp:803-825).  DARK and NONE follow the rule above with the
  *                     config's flags (and no moving average: the sim variant has none).
- * Not covered: the reference's saveinterferograms branch (1003-1036) accumulates the binned frames WITHOUT the moving
- * average (1024) -- a host that wants that result captures with a handle whose movavgn is 0; BscanDark's lpfilter; and
- * BscanDark's composition data_yb = (yr - yd) + (ys - yd), which a host forms from three FDOCT_REF_NONE captures and passes
- * to the background setter of fdoct.h; INTEGRATION.md 2d shows it.
+ *   options           fdoct_lowpass.h adds two switches of the handle, both off by default: BscanDark's lpfilter as the last
+ *                     step of BACKGROUND, DARK and NONE, and the saveinterferograms branch (1003-1036), which accumulates the
+ *                     binned frames without the moving average (1024).
+ * Not covered: an asynchronous form of the capture, and BscanDark's composition data_yb = (yr - yd) + (ys - yd), which a host
+ * forms from three FDOCT_REF_NONE captures and passes to the background setter of fdoct.h; INTEGRATION.md 2d shows it.
  * The division is a division (acc[i] / nframes), as the CPU restatement of this project divides everywhere the reference
  * writes `Mat / scalar`.
  */
