@@ -99,6 +99,8 @@ ROI_ABI_SYMBOLS = [
 CAPTURE_ABI_SYMBOLS = ["fdoct_capture_reference", "fdoct_get_reference", "fdoct_frame_minmax", "fdoct_normalize_minmax"]
 # every symbol include/fdoct_lowpass.h declares: BscanDark's lpfilter and the capture's two options, likewise on their own
 LOWPASS_ABI_SYMBOLS = ["fdoct_set_capture_options", "fdoct_get_capture_options", "fdoct_lowpass_rows"]
+# every symbol include/fdoct_bscanbin.h declares: spinjnt's output binning between the linear B-scan and its dB, likewise on its own
+BSCANBIN_ABI_SYMBOLS = ["fdoct_bscanbin_size", "fdoct_bscanbin_taps", "fdoct_bscan_bin"]
 # fdoct_ref_role (include/fdoct_capture.h)
 REF_BACKGROUND, REF_PI, REF_DARK, REF_NONE = range(4)
 
@@ -220,6 +222,11 @@ def load_library():
     lib.fdoct_set_capture_options.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.fdoct_get_capture_options.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.fdoct_lowpass_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int]
+    # include/fdoct_bscanbin.h
+    lib.fdoct_bscanbin_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.fdoct_bscanbin_taps.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    lib.fdoct_bscan_bin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
     _lib = lib
     return lib
 
@@ -293,6 +300,26 @@ def normalize_minmax(y, lo=0.0, hi=1.0):
     if rc:
         raise FdoctError(rc, "fdoct_normalize_minmax: bad arguments")
     return a
+
+
+def bscanbin_size(depths, ascans, binx, biny, upx=None, upy=None):
+    """fdoct_bscanbin_size: (out_depths, out_ascans) of the output binning; upx / upy default to binx / biny.  Needs no GPU."""
+    od, oa = C.c_int(), C.c_int()
+    rc = load_library().fdoct_bscanbin_size(depths, ascans, binx, biny, binx if upx is None else upx, biny if upy is None else upy,
+                                            C.byref(od), C.byref(oa))
+    if rc:
+        raise FdoctError(rc, "fdoct_bscanbin_size: factors outside 1..16 / 1..64, or sizes they do not divide")
+    return od.value, oa.value
+
+
+def bscanbin_taps(up):
+    """fdoct_bscanbin_taps: (taps float64 (up, 4), first source offset int32 (up,)) of INTER_CUBIC at scale 1 / up.  Needs no GPU."""
+    taps = np.zeros((max(up, 0), 4), np.float64)
+    off = np.zeros(max(up, 0), np.int32)
+    rc = load_library().fdoct_bscanbin_taps(up, taps.ctypes.data if taps.size else None, off.ctypes.data if off.size else None)
+    if rc:
+        raise FdoctError(rc, "fdoct_bscanbin_taps: up must be 1..64")
+    return taps, off
 
 
 def _frame_batch(frames):
@@ -661,6 +688,40 @@ class Reconstructor:
         """... on device-resident rows (raw device addresses; d_out_ptr None: in place).  Enqueues on the handle's stream."""
         self._check(self.lib.fdoct_lowpass_rows(self.h, d_in_ptr, MEM_DEVICE, rows, width, pitch,
                                                 d_in_ptr if d_out_ptr is None else d_out_ptr, MEM_DEVICE))
+
+    # -- spinjnt's output binning (include/fdoct_bscanbin.h).  Host batches are float32 like the readouts'.
+    def bscan_bin(self, bscan, binx, biny, upx=None, upy=None, multiplyfactor=None, jscan=None, layout=LAYOUT_ROWMAJOR,
+                  want_db=True, want_bscan=True):
+        """BscanFFTspinjnt.cpp:1856-1874 on host B-scans: INTER_AREA by binx x biny, INTER_CUBIC back up by upx x upy (defaults
+        binx, biny) of multiplyfactor (default binx * biny) times the binned image, and the dB of the result.  Returns
+        (bscan, bscandb) float32 in the input's layout (None when not requested); a 2-D input gives 2-D results."""
+        single = np.ndim(bscan) == 2
+        a, n, d, h = _db_batch(bscan, layout)
+        upx, upy = binx if upx is None else upx, biny if upy is None else upy
+        mf = float(binx * biny) if multiplyfactor is None else float(multiplyfactor)
+        od, oa = bscanbin_size(d, h, binx, biny, upx, upy)
+        shp = (n, od, oa) if layout == LAYOUT_TRANSPOSED else (n, oa, od)
+        j = None
+        if jscan is not None:
+            j = np.ascontiguousarray(jscan, np.float32)
+            if j.shape != a.shape[1:]:
+                raise FdoctError(-1, "jscan must be one image of the B-scans' shape")
+        lin = np.empty(shp, np.float32) if want_bscan else None
+        db = np.empty(shp, np.float32) if want_db else None
+        self._check(self.lib.fdoct_bscan_bin(self.h, a.ctypes.data, None if j is None else j.ctypes.data, MEM_HOST, layout, n, d, h,
+                                             binx, biny, upx, upy, mf, None if lin is None else lin.ctypes.data,
+                                             None if db is None else db.ctypes.data, MEM_HOST))
+        if single:
+            lin, db = (None if lin is None else lin[0]), (None if db is None else db[0])
+        return lin, db
+
+    def bscan_bin_device(self, d_bscan_ptr, nbscans, depths, ascans, binx, biny, d_out_bscan_ptr, d_out_db_ptr, upx=None, upy=None,
+                         multiplyfactor=None, d_jscan_ptr=None, layout=LAYOUT_ROWMAJOR):
+        """... on device-resident B-scans (raw device addresses; either output may be None).  Enqueues on the handle's stream."""
+        self._check(self.lib.fdoct_bscan_bin(self.h, d_bscan_ptr, d_jscan_ptr, MEM_DEVICE, layout, nbscans, depths, ascans, binx, biny,
+                                             binx if upx is None else upx, biny if upy is None else upy,
+                                             float(binx * biny) if multiplyfactor is None else float(multiplyfactor),
+                                             d_out_bscan_ptr, d_out_db_ptr, MEM_DEVICE))
 
     # -- work
     def _out_shape(self, nframes, layout):

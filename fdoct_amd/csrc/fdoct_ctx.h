@@ -7,6 +7,7 @@
 //   fdoct_roi.cpp     those of include/fdoct_roi.h (the B-scan readouts)
 //   fdoct_capture.cpp those of include/fdoct_capture.h (reference frames captured from camera frames)
 //   fdoct_lowpass.cpp those of include/fdoct_lowpass.h (BscanDark's lpfilter, the capture's options)
+//   fdoct_bscanbin.cpp those of include/fdoct_bscanbin.h (spinjnt's output binning between the linear B-scan and its dB)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -210,6 +211,11 @@ struct fdoct_ctx {
   int cap_lowpass = 0, cap_raw = 0;
   DevBuf<double> ws_lp_io;         // fdoct_lowpass_rows: host rows on their way to the kernel and back (packed)
   DevBuf<double> ws_lp_bins;       // rows too long for LDS: their bins (LowpassShape::ws_doubles)
+  // spinjnt's output binning (fdoct_bscanbin.cpp)
+  DevBuf<double> d_bin_taps;       // the cubic's phases for bin_taps_upx / bin_taps_upy (fdoct_bscanbin_kernels.h), uploaded when they change
+  int bin_taps_upx = 0, bin_taps_upy = 0;
+  DevBuf<float> ws_bin_in;         // host-memory B-scans (and jscan behind them) on their way to the kernel
+  DevBuf<float> ws_bin_out;        // ... and out_bscan, then out_db, on their way back
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;

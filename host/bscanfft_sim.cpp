@@ -11,6 +11,7 @@
 //                [--rowwisenormalize 0|1] [--donotnormalize 0|1] [--repeat K] [--threshold dB] --out prefix
 //                [--gpus N [--devices d0,d1,...]] [--precise-division | --one-word-division]
 //                [--roi-mean ascanat,vertpos,width] [--capture-background N [--capture-lowpass] [--capture-raw]] [--max-intensity]
+//                [--bscan-bin BX,BY[,BINVALUEX,BINVALUEY]]
 //
 // --gpus N: one process, N handles (fdoct_clone_to_device), one host thread per handle; the frames are sharded with
 // fdoct_shard_frames (contiguous ranges, averaging groups never split -- the rule of the multi-process path,
@@ -25,6 +26,10 @@
 // reconstructed; --background is then not needed.  --capture-lowpass ends that capture with BscanDark's lpfilter (the ini's
 // lowpassfilter), --capture-raw skips its moving average (the ini's saveinterferograms; include/fdoct_lowpass.h); with either,
 // the captured frame is also written as <prefix>_background.f64 (H x W doubles).
+// --bscan-bin BX,BY[,BINVALUEX,BINVALUEY]: spinjnt's output binning (bscanbinx, bscanbiny and the software binvalues;
+// BscanFFTspinjnt.cpp:1856-1861) on every output B-scan between the chain and everything written below, on the GPU
+// (include/fdoct_bscanbin.h), with the reference's own arguments: upx = BX * BINVALUEY, upy = BY and multiplyfactor =
+// BX * BY * BINVALUEX * BINVALUEY (835).  The outputs then have (D / BY) * upy depths and (H / BX) * upx A-scans.
 // --max-intensity: the status line's "Max intensity = <floor(max)>" (BscanFFT.cpp:1105-1108) for every reconstructed frame.
 // --frames holds one or more H x W frames back to back (u8 for --bits 8, little-endian u16 for --bits 16).
 // Outputs: <prefix>_bscan.f32 / <prefix>_bscandb.f32 (reference layout D x H per B-scan, main:1220) and
@@ -43,6 +48,7 @@
 #include <vector>
 
 #include "../include/fdoct.h"
+#include "../include/fdoct_bscanbin.h"
 #include "../include/fdoct_capture.h"
 #include "../include/fdoct_lowpass.h"
 #include "../include/fdoct_roi.h"
@@ -80,6 +86,7 @@ int main(int argc, char** argv) {
   int capture_bg = 0;              // --capture-background N (0: read --background)
   int capture_lowpass = 0, capture_raw = 0;  // --capture-lowpass, --capture-raw: fdoct_set_capture_options
   bool max_intensity = false;      // --max-intensity
+  int bbin[4] = {0, 0, 1, 1};      // --bscan-bin bscanbinx,bscanbiny[,binvaluex,binvaluey] (0: off)
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -111,6 +118,13 @@ int main(int argc, char** argv) {
     else if (a == "--roi-mean") {
       if (std::sscanf(next(), "%d,%d,%d", &roi[0], &roi[1], &roi[2]) != 3) {
         std::fprintf(stderr, "--roi-mean wants ascanat,vertpos,width\n");
+        return 1;
+      }
+    }
+    else if (a == "--bscan-bin") {
+      const int n = std::sscanf(next(), "%d,%d,%d,%d", &bbin[0], &bbin[1], &bbin[2], &bbin[3]);
+      if ((n != 2 && n != 4) || bbin[0] < 1 || bbin[1] < 1 || bbin[2] < 1 || bbin[3] < 1) {
+        std::fprintf(stderr, "--bscan-bin wants BX,BY or BX,BY,BINVALUEX,BINVALUEY\n");
         return 1;
       }
     }
@@ -271,13 +285,34 @@ int main(int argc, char** argv) {
               (double)nframes * cfg.height * repeat / sec, tm.last_process_ms, tm.last_kernel_ms,
               fam >= 0 && fam < 8 ? family[fam] : "?", *fdoct_jit_note(h) ? "; " : "", fdoct_jit_note(h));
 
+  // spinjnt's output stage (BscanFFTspinjnt.cpp:1856-1874): the averaged linear B-scan is binned and resized back, and the dB
+  // (with the DC mask) is taken of the result; everything below sees these images, as in the reference
+  int OD = cfg.numdisplaypoints, OH = cfg.height;
+  if (bbin[0] > 0) {
+    const int upx = bbin[0] * bbin[3], upy = bbin[1];  // 1861: bscanbinx * binvaluey (the reference's own quirk), bscanbiny
+    const double multiplyfactor = (double)bbin[0] * bbin[1] * bbin[2] * bbin[3];  // 835
+    const int size_rc = rc = fdoct_bscanbin_size(cfg.numdisplaypoints, cfg.height, bbin[0], bbin[1], upx, upy, &OD, &OH);
+    std::vector<float> lin, db;
+    if (!rc) {
+      lin.resize((size_t)G * OD * OH), db.resize(lin.size());
+      rc = fdoct_bscan_bin(h, bscan.data(), nullptr, FDOCT_MEM_HOST, FDOCT_LAYOUT_TRANSPOSED_DxH, G, cfg.numdisplaypoints, cfg.height,
+                           bbin[0], bbin[1], upx, upy, multiplyfactor, lin.data(), db.data(), FDOCT_MEM_HOST);
+    }
+    if (rc) {
+      std::fprintf(stderr, "fdoct_bscan_bin: %d %s\n", rc, fdoct_last_error(size_rc ? nullptr : h));
+      return 1;
+    }
+    bscan.swap(lin);
+    bscandb.swap(db);
+  }
+
   {
     std::ofstream f(out + "_bscan.f32", std::ios::binary);
     f.write(reinterpret_cast<const char*>(bscan.data()), bscan.size() * sizeof(float));
     std::ofstream g(out + "_bscandb.f32", std::ios::binary);
     g.write(reinterpret_cast<const char*>(bscandb.data()), bscandb.size() * sizeof(float));
     // and the first B-scan as an .ocv Mat dump (CV_32F, D x H), the format savematasbin uses
-    ocv_write(out + "_bscan001.ocv", cfg.numdisplaypoints, cfg.height, 5, bscan.data());
+    ocv_write(out + "_bscan001.ocv", OD, OH, 5, bscan.data());
   }
   {
     // Matlab text, as savematasdata writes it (main:333-339: name "=" operator<<(Mat) ";"): rows separated by ";\n ",
@@ -286,31 +321,31 @@ int main(int argc, char** argv) {
     std::ofstream m(out + ".m");
     m << "bscan001=[";
     char num[40];
-    for (int d = 0; d < cfg.numdisplaypoints; d++) {
-      for (int r = 0; r < cfg.height; r++) {
-        std::snprintf(num, sizeof num, "%.16g", (double)bscan[(size_t)d * cfg.height + r]);
+    for (int d = 0; d < OD; d++) {
+      for (int r = 0; r < OH; r++) {
+        std::snprintf(num, sizeof num, "%.16g", (double)bscan[(size_t)d * OH + r]);
         m << num;
-        if (r + 1 < cfg.height) m << ", ";
+        if (r + 1 < OH) m << ", ";
       }
-      if (d + 1 < cfg.numdisplaypoints) m << ";\n ";
+      if (d + 1 < OD) m << ";\n ";
     }
     m << "];\n";
   }
   {
     // the display chain of main:1242-1255 + 1284 for the first B-scan, as portable grey/pix maps
-    const size_t px = (size_t)cfg.numdisplaypoints * cfg.height;
+    const size_t px = (size_t)OD * OH;
     std::vector<unsigned char> gray(px), bgr(3 * px);
-    rc = fdoct_display(h, bscandb.data(), FDOCT_MEM_HOST, 1, cfg.numdisplaypoints, cfg.height, bscanthreshold, 0, gray.data(),
+    rc = fdoct_display(h, bscandb.data(), FDOCT_MEM_HOST, 1, OD, OH, bscanthreshold, 0, gray.data(),
                        bgr.data(), FDOCT_MEM_HOST);
     if (rc) {
       std::fprintf(stderr, "fdoct_display: %d %s\n", rc, fdoct_last_error(h));
       return 1;
     }
     std::ofstream pg(out + "_bscan001.pgm", std::ios::binary);
-    pg << "P5\n" << cfg.height << " " << cfg.numdisplaypoints << "\n255\n";
+    pg << "P5\n" << OH << " " << OD << "\n255\n";
     pg.write(reinterpret_cast<const char*>(gray.data()), px);
     std::ofstream pp(out + "_bscanc001.ppm", std::ios::binary);
-    pp << "P6\n" << cfg.height << " " << cfg.numdisplaypoints << "\n255\n";
+    pp << "P6\n" << OH << " " << OD << "\n255\n";
     for (size_t i = 0; i < px; i++) {  // cv::Mat colour order is B,G,R; PPM wants R,G,B
       const char rgb[3] = {(char)bgr[3 * i + 2], (char)bgr[3 * i + 1], (char)bgr[3 * i]};
       pp.write(rgb, 3);
@@ -319,7 +354,7 @@ int main(int argc, char** argv) {
   if (roi[0] >= 0) {
     // ROIreport: printAvgROI on each displayed B-scan (main:1289-1290), over the dB image after the DC mask
     std::vector<double> mean(G);
-    rc = fdoct_roi_mean(h, bscandb.data(), FDOCT_MEM_HOST, FDOCT_LAYOUT_TRANSPOSED_DxH, G, cfg.numdisplaypoints, cfg.height,
+    rc = fdoct_roi_mean(h, bscandb.data(), FDOCT_MEM_HOST, FDOCT_LAYOUT_TRANSPOSED_DxH, G, OD, OH,
                         roi[0], roi[1], roi[2], mean.data(), FDOCT_MEM_HOST);
     if (rc) {
       std::fprintf(stderr, "fdoct_roi_mean: %d %s\n", rc, fdoct_last_error(h));

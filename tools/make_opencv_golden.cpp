@@ -17,13 +17,16 @@
 //   opencv_normalize_96x128.f64, opencv_normalizerows_96x128.f64     normalize(.., 0, 1, NORM_MINMAX) whole frame / per row
 //                                    (main:88-97, 1126-1129)
 //   opencv_median{3,5}_u16_96x128.bin, opencv_median{3,5,7}_u8_96x128.bin      medianBlur borders (main:953-956)
+//   opencv_bscanbin_{2x2,3x1,1x4}_bv{1,2}.bin  spinjnt's INTER_AREA + INTER_CUBIC output binning (BscanFFTspinjnt.cpp:1856-1861)
 //   opencv_resize_2x2_{u8,u16}_48x64.bin, opencv_resize_4x3_{u8,u16}_32x32.bin  resize(INTER_AREA) rounding (main:958)
 //   opencv_div0_96x128.f64           Mat / Mat with zeros in the divisor (main:1132)
 //   opencv_display_512x96.u8         threshold, min-max normalise, x255 -> CV_8U of the bscandb above (main:1242-1255)
 //   opencv_jet_256x3.u8              applyColorMap(COLORMAP_JET) of the 0..255 ramp, B,G,R (main:1284)
 #include <cmath>
 #include <cstdio>
+#include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <opencv2/opencv.hpp>
 #include <string>
 #include <vector>
@@ -207,6 +210,32 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 256; i++) ramp.at<unsigned char>(0, i) = (unsigned char)i;
     applyColorMap(ramp, jet, COLORMAP_JET);                             // main:1284
     dump(dir + "/opencv_jet_256x3.u8", jet);
+  }
+  // ---- spinjnt's output binning (BscanFFTspinjnt.cpp:1856-1861) on the linear bscan above, as floats (what the library is
+  // given): int32 depths, ascans, binx, biny, upx, upy, out_depths, out_ascans; float64 multiplyfactor; the float32 input; the
+  // float64 result (tests/test_bscanbin_model.py::test_opencv_golden_vectors_if_present)
+  {
+    Mat b32, in64;
+    bscan.convertTo(b32, CV_32F);
+    b32.convertTo(in64, CV_64F);
+    const int factors[3][2] = {{2, 2}, {3, 1}, {1, 4}};
+    for (const auto& f : factors)
+      for (int binvaluey : {1, 2}) {
+        const int bscanbinx = f[0], bscanbiny = f[1], binvaluex = 1;
+        const double multiplyfactor = bscanbinx * bscanbiny * binvaluex * binvaluey;   // 835
+        Mat bscanbinned, out;
+        resize(in64, bscanbinned, Size(), 1.0 / bscanbinx, 1.0 / bscanbiny, INTER_AREA);
+        resize(multiplyfactor * bscanbinned, out, Size(), bscanbinx * binvaluey, bscanbiny, INTER_CUBIC);
+        const int32_t hdr[8] = {in64.rows, in64.cols, bscanbinx, bscanbiny, bscanbinx * binvaluey, bscanbiny, out.rows, out.cols};
+        std::vector<unsigned char> blob(sizeof hdr + 8 + b32.total() * 4 + out.total() * 8);
+        unsigned char* q = blob.data();
+        memcpy(q, hdr, sizeof hdr), q += sizeof hdr;
+        memcpy(q, &multiplyfactor, 8), q += 8;
+        memcpy(q, b32.ptr(), b32.total() * 4), q += b32.total() * 4;
+        memcpy(q, out.ptr(), out.total() * 8);
+        dump(dir + "/opencv_bscanbin_" + std::to_string(bscanbinx) + "x" + std::to_string(bscanbiny) + "_bv" + std::to_string(binvaluey) + ".bin",
+             blob.data(), blob.size());
+      }
   }
   printf("OpenCV %s\n", CV_VERSION);
   return 0;
