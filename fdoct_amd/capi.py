@@ -101,6 +101,8 @@ CAPTURE_ABI_SYMBOLS = ["fdoct_capture_reference", "fdoct_get_reference", "fdoct_
 LOWPASS_ABI_SYMBOLS = ["fdoct_set_capture_options", "fdoct_get_capture_options", "fdoct_lowpass_rows"]
 # every symbol include/fdoct_bscanbin.h declares: spinjnt's output binning between the linear B-scan and its dB, likewise on its own
 BSCANBIN_ABI_SYMBOLS = ["fdoct_bscanbin_size", "fdoct_bscanbin_taps", "fdoct_bscan_bin"]
+# every symbol include/fdoct_colour.h declares: the webcam's interleaved B,G,R frames (channelnum), likewise on their own
+COLOUR_ABI_SYMBOLS = ["fdoct_set_colour_input", "fdoct_get_colour_input", "fdoct_colour_extract", "fdoct_colour_sum_scale"]
 # fdoct_ref_role (include/fdoct_capture.h)
 REF_BACKGROUND, REF_PI, REF_DARK, REF_NONE = range(4)
 
@@ -227,6 +229,13 @@ def load_library():
     lib.fdoct_bscanbin_taps.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     lib.fdoct_bscan_bin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
+    # include/fdoct_colour.h
+    lib.fdoct_set_colour_input.argtypes = [C.c_void_p, C.c_int]
+    lib.fdoct_get_colour_input.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    lib.fdoct_colour_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.fdoct_colour_sum_scale.argtypes = []
+    lib.fdoct_colour_sum_scale.restype = C.c_double
     _lib = lib
     return lib
 
@@ -302,6 +311,11 @@ def normalize_minmax(y, lo=0.0, hi=1.0):
     return a
 
 
+def colour_sum_scale():
+    """fdoct_colour_sum_scale: 0.00130718954, the factor of BscanFFTwebcam.cpp:1031's channel sum.  Needs no GPU."""
+    return float(load_library().fdoct_colour_sum_scale())
+
+
 def bscanbin_size(depths, ascans, binx, biny, upx=None, upy=None):
     """fdoct_bscanbin_size: (out_depths, out_ascans) of the output binning; upx / upy default to binx / biny.  Needs no GPU."""
     od, oa = C.c_int(), C.c_int()
@@ -323,12 +337,20 @@ def bscanbin_taps(up):
 
 
 def _frame_batch(frames):
-    """Host camera frames as (array, nframes, row pitch in bytes): (nframes, rows, cols) of u8 / u16 / f32 / f64, rows contiguous."""
+    """Host camera frames as (array, nframes, row pitch in bytes): (nframes, rows, cols) of u8 / u16 / f32 / f64, rows contiguous;
+    or (nframes, rows, cols, 3) uint8, the B,G,R frames of a handle with set_colour_input."""
     a = np.asarray(frames)
     if a.dtype not in _NP2DT:
         a = a.astype(np.float64)
     if a.ndim == 2:
         a = a[None]
+    if a.ndim == 4:
+        n, r, c, ch = a.shape
+        if ch != 3 or a.dtype != np.uint8:
+            raise FdoctError(-1, "colour frames are (nframes, rows, cols, 3) uint8")
+        if a.strides[3] != 1 or a.strides[2] != 3 or a.strides[0] != a.strides[1] * r or a.strides[1] < 3 * c:
+            a = np.ascontiguousarray(a)
+        return a, n, a.strides[1]
     n, r, c = a.shape
     if a.strides[2] != a.itemsize or a.strides[0] != a.strides[1] * r or a.strides[1] < c * a.itemsize:
         a = np.ascontiguousarray(a)
@@ -456,6 +478,37 @@ class Reconstructor:
         self._check(self.lib.fdoct_frontend(self.h, a.ctypes.data, _NP2DT[a.dtype], n, ww, hh, a.strides[1], mediann, binx, biny,
                                             out.ctypes.data))
         return out
+
+    # -- the webcam's B,G,R frames (include/fdoct_colour.h)
+    def set_colour_input(self, channelnum=-1):
+        """BscanFFTwebcam.ini's channelnum: process* / capture_reference* / frame_minmax then take 8-bit (nframes, raw_h, raw_w, 3)
+        B,G,R frames.  0 / 1 / 2: that channel; 3: (B + G + R) * colour_sum_scale() as doubles; -1: mono frames again."""
+        self._check(self.lib.fdoct_set_colour_input(self.h, int(channelnum)))
+
+    def get_colour_input(self):
+        c = C.c_int()
+        self._check(self.lib.fdoct_get_colour_input(self.h, C.byref(c)))
+        return c.value
+
+    def colour_extract(self, bgr, channelnum, mediann=0, binx=1, biny=1):
+        """The colour stage on its own: bgr (nframes, raw_h, raw_w, 3) uint8 on the host (a view with padded rows passes its pitch
+        on) -> (nframes, raw_h / biny, raw_w / binx) uint8 (channelnum 0-2) or float64 (3)."""
+        a = np.asarray(bgr)
+        if a.ndim == 3:
+            a = a[None]
+        a, n, pitch = _frame_batch(a)
+        if a.ndim != 4:
+            raise FdoctError(-1, "colour frames are (nframes, rows, cols, 3) uint8")
+        hh, ww = a.shape[1], a.shape[2]
+        out = np.empty((n, hh // max(biny, 1), ww // max(binx, 1)), np.float64 if channelnum == 3 else np.uint8)
+        self._check(self.lib.fdoct_colour_extract(self.h, a.ctypes.data, MEM_HOST, n, ww, hh, pitch, channelnum, mediann, binx, biny,
+                                                  out.ctypes.data, MEM_HOST))
+        return out
+
+    def colour_extract_device(self, d_bgr_ptr, nframes, raw_w, raw_h, pitch, channelnum, d_out_ptr, mediann=0, binx=1, biny=1):
+        """... on device-resident frames (raw device addresses, any alignment; the output packed).  Enqueues on the handle's stream."""
+        self._check(self.lib.fdoct_colour_extract(self.h, d_bgr_ptr, MEM_DEVICE, nframes, raw_w, raw_h, pitch, channelnum, mediann,
+                                                  binx, biny, d_out_ptr, MEM_DEVICE))
 
     # -- display post-chain (BscanFFT.cpp:1242-1255, 1284, 1225-1230)
     def set_colormap(self, bgr256=None):
@@ -731,7 +784,7 @@ class Reconstructor:
         return (g, self.cfg.height, self.cfg.numdisplaypoints)
 
     def process(self, frames, want_db=True, want_bscan=True, layout=LAYOUT_ROWMAJOR, out_bscan=None, out_db=None):
-        """frames: numpy (nframes, H, W) u8/u16/f32/f64 on the host.  Returns (bscan, bscandb)
+        """frames: numpy (nframes, H, W) u8/u16/f32/f64 on the host -- with set_colour_input, (nframes, raw_h, raw_w, 3) uint8.  Returns (bscan, bscandb)
         float32 arrays (None when not requested).  PCIe-inclusive, synchronous.  out_bscan / out_db: caller-owned
         float32 result arrays (e.g. PinnedArray(...).array) instead of fresh ones -- a loop should pass them: a fresh
         array's first-touch page faults cost a 64-frame call four fifths of its rate (profiles/r06_pcie_rate.txt)."""
@@ -740,6 +793,8 @@ class Reconstructor:
             a = a[None]
         if a.dtype not in _NP2DT:
             raise FdoctError(-1, "unsupported frame dtype %s" % a.dtype)
+        if a.ndim == 4 and (a.shape[3] != 3 or a.dtype != np.uint8):
+            raise FdoctError(-1, "colour frames are (nframes, rows, cols, 3) uint8")
         nframes = a.shape[0]
         shp = self._out_shape(nframes, layout)
         def _result(given, want):

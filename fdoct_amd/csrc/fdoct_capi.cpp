@@ -224,7 +224,7 @@ static int sim_last_frames(fdoct_ctx* h, const void** frames, fdoct_memspace* sp
   if (S <= 1) return FDOCT_OK;
   if (!*frames || *nframes <= 0) return fail(h, FDOCT_ERR_INVALID, "no frames");
   if (*nframes % S) return fail(h, FDOCT_ERR_INVALID, "nframes must be a multiple of averages");
-  const size_t es = dtype_size(dtype);
+  const size_t es = frame_pixel_bytes(h, dtype);  // (a colour handle's frames: rows of B,G,R pixels)
   if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
   const size_t pitch = pitch_bytes ? pitch_bytes : es * (size_t)h->W * h->fe_binx;
   const size_t frame_bytes = pitch * (size_t)h->H * h->fe_biny;  // raw camera rows when a front end is set
@@ -244,6 +244,8 @@ int fdoct_process_async(fdoct_handle h, const void* d_frames, fdoct_dtype dtype,
                         float* d_out_bscan, float* d_out_db, fdoct_layout layout) try {
   if (!h) return FDOCT_ERR_INVALID;
   fdoct_memspace space = FDOCT_MEM_DEVICE;
+  if (h->colour >= 0)  // refused before the gather below enqueues anything
+    if (int rc = colour_check(h, "colour input", h->colour, dtype, h->fe_median)) return rc;
   if (int rc = sim_last_frames(h, &d_frames, &space, dtype, &nframes, pitch_bytes)) return rc;
   h->record_now = h->async_timing;
   return enqueue(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
@@ -472,7 +474,9 @@ int fdoct_process(fdoct_handle h, const void* frames, fdoct_dtype dtype, fdoct_m
                   fdoct_layout layout) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!frames || nframes <= 0) return fail(h, FDOCT_ERR_INVALID, "no frames");
-  const size_t es = dtype_size(dtype);
+  if (h->colour >= 0)  // refused before an upload is enqueued
+    if (int rc = colour_check(h, "colour input", h->colour, dtype, h->fe_median)) return rc;
+  const size_t es = frame_pixel_bytes(h, dtype);  // a colour handle's rows hold 3 bytes per pixel: chunks, strides and staging follow
   if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
   const size_t row_samples = (size_t)h->W * h->fe_binx;
   size_t d_pitch = pitch_bytes ? pitch_bytes : es * row_samples;
@@ -749,7 +753,7 @@ int fdoct_set_staged(fdoct_handle h, int on) try {
 int fdoct_prepare(fdoct_handle h, fdoct_dtype dtype, fdoct_layout layout) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!h->yb.rows) return fail(h, FDOCT_ERR_STATE, "no background set (fdoct_set_background)");
-  const size_t es = dtype_size(dtype);
+  const size_t es = frame_pixel_bytes(h, dtype);
   if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
   DEVICE_SCOPE(h);
   // the call fdoct_process* will see: aligned device frames, packed rows, one averaging group, both images asked for
@@ -837,6 +841,7 @@ int fdoct_clone_to_device(fdoct_handle h, int device, fdoct_handle* out) try {
   c->fe_biny = h->fe_biny;
   c->cap_lowpass = h->cap_lowpass;
   c->cap_raw = h->cap_raw;
+  c->colour = h->colour;
   c->bandpass = h->bandpass;
   c->jit = h->jit;
   c->precise_div = h->precise_div;

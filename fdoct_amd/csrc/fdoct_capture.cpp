@@ -21,6 +21,7 @@ struct FramePlan {
   const void* frames = nullptr;
   fdoct_dtype dtype = FDOCT_U16;
   bool host = false, frontend = false;
+  bool colour = false;  // interleaved B,G,R frames (fdoct_set_colour_input): es is 3, the colour stage runs in the front end's place
   int nframes = 0, raw_w = 0, raw_h = 0;
   size_t es = 0, pitch = 0;
 };
@@ -29,7 +30,11 @@ int plan_frames(fdoct_ctx* h, const char* fn, const void* frames, fdoct_dtype dt
                 size_t pitch_bytes, FramePlan* p) {
   const std::string who = std::string(fn) + ": ";
   if (!frames || !valid_mem(space) || nframes < 1) return fail(h, FDOCT_ERR_INVALID, who + "bad arguments");
-  const size_t es = dtype_size(dtype);
+  if (h->colour >= 0) {
+    if (int rc = colour_check(h, fn, h->colour, dtype, h->fe_median)) return rc;
+    p->colour = true;
+  }
+  const size_t es = frame_pixel_bytes(h, dtype);
   if (!es) return fail(h, FDOCT_ERR_INVALID, who + "bad dtype");
   p->frames = frames, p->dtype = dtype, p->host = space == FDOCT_MEM_HOST, p->nframes = nframes, p->es = es;
   p->frontend = has_frontend(h);
@@ -37,9 +42,9 @@ int plan_frames(fdoct_ctx* h, const char* fn, const void* frames, fdoct_dtype dt
   p->raw_h = h->H * (p->frontend ? h->fe_biny : 1);
   p->pitch = pitch_bytes ? pitch_bytes : es * (size_t)p->raw_w;
   if (p->pitch < es * (size_t)p->raw_w) return fail(h, FDOCT_ERR_INVALID, who + "pitch smaller than a row");
-  if (p->pitch % es || reinterpret_cast<uintptr_t>(frames) % es)
+  if (!p->colour && (p->pitch % es || reinterpret_cast<uintptr_t>(frames) % es))
     return fail(h, FDOCT_ERR_INVALID, who + "frames and pitch must be aligned to one sample");
-  if (p->frontend) {
+  if (p->frontend && !p->colour) {
     if (dtype != FDOCT_U8 && dtype != FDOCT_U16)
       return fail(h, FDOCT_ERR_UNSUPPORTED, who + "the front end (median / binning) takes the camera's 8- or 16-bit frames");
     if (h->fe_median == 7 && dtype == FDOCT_U16)
@@ -60,14 +65,20 @@ int stage_frames(fdoct_ctx* h, const FramePlan& p, fdoct::CaptureFrames* cf) {
     src = h->ws_raw;
     pitch = packed;
   }
-  if (p.frontend) {
+  fdoct_dtype dt = p.dtype;
+  if (p.colour) {  // webcam:1015-1038 ahead of everything, the median / binning with it
+    void* co = nullptr;
+    if (int rc = run_colour(h, src, p.nframes, p.raw_w, p.raw_h, pitch, h->colour, h->fe_median, h->fe_binx, h->fe_biny, &co, &pitch)) return rc;
+    src = co;
+    if (h->colour == 3) dt = FDOCT_F64;
+  } else if (p.frontend) {
     void* fo = nullptr;
     if (int rc = run_frontend(h, src, kernel_dtype(p.dtype), p.nframes, p.raw_w, p.raw_h, pitch, h->fe_median, h->fe_binx,
                               h->fe_biny, &fo, &pitch))
       return rc;
     src = fo;
   }
-  cf->frames = src, cf->dt = p.dtype, cf->pitch = pitch, cf->nframes = p.nframes, cf->H = h->H, cf->W = h->W;
+  cf->frames = src, cf->dt = dt, cf->pitch = pitch, cf->nframes = p.nframes, cf->H = h->H, cf->W = h->W;
   return FDOCT_OK;
 }
 

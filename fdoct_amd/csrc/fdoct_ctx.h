@@ -8,6 +8,7 @@
 //   fdoct_capture.cpp those of include/fdoct_capture.h (reference frames captured from camera frames)
 //   fdoct_lowpass.cpp those of include/fdoct_lowpass.h (BscanDark's lpfilter, the capture's options)
 //   fdoct_bscanbin.cpp those of include/fdoct_bscanbin.h (spinjnt's output binning between the linear B-scan and its dB)
+//   fdoct_colour.cpp  those of include/fdoct_colour.h (the webcam's interleaved B,G,R frames: channelnum)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -216,6 +217,12 @@ struct fdoct_ctx {
   int bin_taps_upx = 0, bin_taps_upy = 0;
   DevBuf<float> ws_bin_in;         // host-memory B-scans (and jscan behind them) on their way to the kernel
   DevBuf<float> ws_bin_out;        // ... and out_bscan, then out_db, on their way back
+  // fdoct_set_colour_input (fdoct_colour.cpp): BscanFFTwebcam.ini's channelnum.  -1: mono frames; 0 / 1 / 2: 8-bit frames are
+  // interleaved B,G,R and that channel is taken; 3: their scaled sum, a frame of doubles.  A run-time setting like the front
+  // end's: fdoct_clone_to_device carries it, the state blob does not.
+  int colour = -1;
+  DevBuf<unsigned char> ws_col;    // the full-resolution channel on its way to the median (run_colour)
+  DevBuf<double> ws_col_sum;       // the (binned) sum frames
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
@@ -357,6 +364,7 @@ enum class PrePass {  // the pass that produces what the chain's kernel reads
 struct Route {
   int family = FDOCT_KERNEL_NONE;   // fdoct_kernel: who runs the chain
   bool frontend = false;            // medianBlur + binning pass over the raw frames first (main:953-958)
+  bool colour = false;              // the colour stage first (webcam:1015-1038), median / binning included: the rest is routed as its output is
   PrePass pre = PrePass::None;
   int kdt = -1;                     // sample type the chain's kernel reads (FDOCT_K_*)
   size_t kpitch = 0;                // ... and its row pitch
@@ -385,6 +393,15 @@ struct Call {
 };
 
 int kernel_dtype(int dt);
+// Bytes per pixel of the frames a call takes: the sample's size, or 3 for the 8-bit frames of a colour handle.
+inline size_t frame_pixel_bytes(const fdoct_ctx* h, int dtype) { return h->colour >= 0 && dtype == FDOCT_U8 ? 3 : dtype_size(dtype); }
+// What a colour stage can do, checked before anything is enqueued (`who` prefixes the message): 8-bit frames only, no median in
+// front of the sum (cv::medianBlur rejects CV_64F: there is no reference behaviour to match).
+int colour_check(fdoct_ctx* h, const char* who, int channelnum, fdoct_dtype dtype, int mediann);
+// The colour stage on device-resident interleaved frames (fdoct_colour.hip), with the median / binning behind it: leaves packed,
+// 16-byte-pitched bytes (channelnum 0-2) or doubles (3) in a library workspace, *out / *out_pitch.  Enqueues only.
+int run_colour(fdoct_ctx* h, const void* d_bgr, int nframes, int raw_w, int raw_h, size_t pitch, int channelnum, int mediann, int binx,
+               int biny, void** out, size_t* out_pitch);
 int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_w, int raw_h, size_t raw_pitch, int mediann,
                  int binx, int biny, void** out, size_t* out_pitch);
 int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,

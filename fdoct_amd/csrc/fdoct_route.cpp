@@ -3,6 +3,7 @@
 // launcher per kernel family fills its argument block from handle and route, finish_launch is the one epilogue; plus the long-row
 // path's host side (plans, grouped launches) and the front end.  Part of the C-ABI layer (fdoct_ctx.h).
 #include "fdoct_ctx.h"
+#include "fdoct_colour_kernels.h"
 
 namespace fdoct_impl {
 
@@ -45,6 +46,53 @@ int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_
   HIP_TRY(h, launch_bin(src, (long long)src_pitch, h->ws_front, (long long)op, kdt, ow, oh, binx, biny, nframes, st));
   *out = h->ws_front;
   *out_pitch = op;
+  return FDOCT_OK;
+}
+
+int colour_check(fdoct_ctx* h, const char* who, int channelnum, fdoct_dtype dtype, int mediann) {
+  const std::string w = std::string(who) + ": ";
+  if (channelnum < 0 || channelnum > 3) return fail(h, FDOCT_ERR_INVALID, w + "channelnum must be 0, 1, 2 (B, G, R) or 3 (their sum)");
+  if (dtype != FDOCT_U8)
+    return fail(h, FDOCT_ERR_UNSUPPORTED, w + "colour input takes 8-bit interleaved B,G,R frames (what cv::VideoCapture::read delivers), no other sample type");
+  if (mediann != 0 && mediann != 3 && mediann != 5 && mediann != 7) return fail(h, FDOCT_ERR_INVALID, w + "mediann must be 0, 3, 5 or 7");
+  if (channelnum == 3 && mediann > 0)
+    return fail(h, FDOCT_ERR_UNSUPPORTED, w + "the channel sum is a frame of doubles and cv::medianBlur rejects CV_64F: no median with channelnum 3");
+  return FDOCT_OK;
+}
+
+// webcam:1015-1038 and the block behind it.  Sum: one kernel, the binning in it.  Select without a median: likewise, into the
+// front end's output buffer.  Select with a median: the full-resolution channel goes to ws_col and from there through the mono
+// front end as it is (launch_median, launch_bin).
+int run_colour(fdoct_ctx* h, const void* d_bgr, int nframes, int raw_w, int raw_h, size_t pitch, int channelnum, int mediann, int binx,
+               int biny, void** out, size_t* out_pitch) {
+  if (int rc = colour_check(h, "colour stage", channelnum, FDOCT_U8, mediann)) return rc;
+  if (!d_bgr || nframes < 1 || raw_w < 1 || raw_h < 1) return fail(h, FDOCT_ERR_INVALID, "colour stage: no frames");
+  if (binx < 1 || biny < 1 || raw_w % binx || raw_h % biny) return fail(h, FDOCT_ERR_INVALID, "frame size must be a multiple of the bin factors");
+  if (pitch < 3 * (size_t)raw_w) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a row of B,G,R pixels");
+  const bool via_median = mediann > 0;
+  ColourArgs a;
+  a.bgr = static_cast<const unsigned char*>(d_bgr);
+  a.pitch = (long long)pitch;
+  a.channelnum = channelnum;
+  a.binx = via_median ? 1 : binx;
+  a.biny = via_median ? 1 : biny;
+  a.ow = raw_w / a.binx;
+  a.out_rows = (long long)nframes * (raw_h / a.biny);
+  a.out_pitch = (long long)frontend_pitch(a.ow, channelnum == 3 ? 8 : 1);
+  const size_t bytes = (size_t)a.out_pitch * (size_t)a.out_rows;
+  int rc;
+  if (channelnum == 3) {
+    if ((rc = h->ws_col_sum.reserve(h, bytes))) return rc;
+    a.out = h->ws_col_sum;
+  } else {
+    DevBuf<unsigned char>& ws = via_median ? h->ws_col : h->ws_front;
+    if ((rc = ws.reserve(h, bytes))) return rc;
+    a.out = ws;
+  }
+  HIP_TRY(h, launch_colour(a, h->stream));
+  if (via_median) return run_frontend(h, a.out, FDOCT_K_U8, nframes, raw_w, raw_h, (size_t)a.out_pitch, mediann, binx, biny, out, out_pitch);
+  *out = a.out;
+  *out_pitch = (size_t)a.out_pitch;
   return FDOCT_OK;
 }
 
@@ -370,8 +418,23 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
   if (h->D > h->N) return fail(h, FDOCT_ERR_INVALID, "numdisplaypoints > numfftpoints");
   const int W = h->W, H = h->H, D = h->D, A = h->A;
   const long long out_rows = (long long)(nframes / A) * H;
-  const size_t es = dtype_size(dtype);
   *r = Route{};
+  // A colour handle: the colour stage runs first and takes the median / binning with it; from here on the call is routed as
+  // what that stage leaves -- the front end's bytes in a library workspace (channelnum 0-2), or packed doubles (3).
+  const bool colour = h->colour >= 0;
+  if (colour) {
+    if ((rc = colour_check(h, "colour input", h->colour, dtype, h->fe_median))) return rc;
+    if (pitch_bytes < 3 * (size_t)W * h->fe_binx) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a row of B,G,R pixels");
+    r->colour = true;
+    frames_addr = 0;
+    if (h->colour == 3) {
+      dtype = FDOCT_F64;
+      pitch_bytes = frontend_pitch(W, 8);
+    } else {
+      pitch_bytes = frontend_pitch(W * h->fe_binx, 1);  // (the unbinned channel: what a kernel that bins in its own loads would read)
+    }
+  }
+  const size_t es = dtype_size(dtype);
   h->jit_note.clear();   // (the note describes THIS call's route: a refused run-time compile, or the long-row path)
   int kdt = kernel_dtype(dtype);
   const bool normalize = (h->cfg.variant == FDOCT_VARIANT_SIM) || !h->cfg.donotnormalize;
@@ -422,7 +485,9 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
   // ---- passes in front of the chain, and what they leave for its kernel to read
   uintptr_t kaddr = frames_addr;
   size_t kpitch = pitch_bytes;
-  if (!r->bin2_in_kernel && (h->fe_median > 0 || h->fe_binx > 1 || h->fe_biny > 1)) {
+  if (colour) {
+    if (h->colour != 3 && !r->bin2_in_kernel) kpitch = frontend_pitch(W, 1);
+  } else if (!r->bin2_in_kernel && (h->fe_median > 0 || h->fe_binx > 1 || h->fe_biny > 1)) {
     if (dtype != FDOCT_U8 && dtype != FDOCT_U16)
       return fail(h, FDOCT_ERR_UNSUPPORTED, "the front end (median / binning) takes the camera's 8- or 16-bit frames");
     if (pitch_bytes < es * (size_t)W * h->fe_binx) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a raw camera row");
@@ -871,6 +936,14 @@ static int run_passes_in_front(fdoct_ctx* h, const Route& r, Call& c, const void
   const int W = h->W, n = h->cfg.movavgn;
   hipStream_t st = c.st;
   int rc;
+  if (r.colour) {  // interleaved B,G,R frames: the colour stage, which bins unless the chain's kernel does
+    void* co = nullptr;
+    if ((rc = run_colour(h, d_frames, c.nframes, W * h->fe_binx, h->H * h->fe_biny, pitch_bytes, h->colour, h->fe_median,
+                         r.bin2_in_kernel ? 1 : h->fe_binx, r.bin2_in_kernel ? 1 : h->fe_biny, &co, &pitch_bytes)))
+      return rc;
+    d_frames = c.kframes = co;
+    dtype = h->colour == 3 ? FDOCT_F64 : FDOCT_U8;
+  }
   size_t pitch = pitch_bytes;
   if (r.frontend) {  // raw camera frames: medianBlur + binning first (main:953-958); the caller's pitch describes the RAW rows
     void* fo = nullptr;
@@ -913,7 +986,7 @@ int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nfram
   if (nframes % h->A) return fail(h, FDOCT_ERR_INVALID, "nframes must be a multiple of averages");
   if (!h->yb.rows) return fail(h, FDOCT_ERR_STATE, "no background set (fdoct_set_background)");
   if (!d_out_bscan && !d_out_db) return fail(h, FDOCT_ERR_INVALID, "no output requested");
-  const size_t es = dtype_size(dtype);
+  const size_t es = frame_pixel_bytes(h, dtype);
   if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
   if (pitch_bytes == 0) pitch_bytes = es * h->W * h->fe_binx;
   if (pitch_bytes < es * h->W) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a row");
@@ -979,7 +1052,7 @@ int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, 
   long long cg = per_group ? (long long)(h->tr_chunk_bytes / per_group) : G;
   if (cg < 1) cg = 1;
   if (G <= cg) return enqueue_one(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
-  const size_t es = dtype_size(dtype);
+  const size_t es = frame_pixel_bytes(h, dtype);
   if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
   const size_t pitch = pitch_bytes ? pitch_bytes : es * (size_t)h->W * h->fe_binx;
   {  // the whole call's route: where the chain writes D x H itself there is no intermediate at all, and nothing to cut

@@ -11,7 +11,7 @@
 //                [--rowwisenormalize 0|1] [--donotnormalize 0|1] [--repeat K] [--threshold dB] --out prefix
 //                [--gpus N [--devices d0,d1,...]] [--precise-division | --one-word-division]
 //                [--roi-mean ascanat,vertpos,width] [--capture-background N [--capture-lowpass] [--capture-raw]] [--max-intensity]
-//                [--bscan-bin BX,BY[,BINVALUEX,BINVALUEY]]
+//                [--bscan-bin BX,BY[,BINVALUEX,BINVALUEY]] [--channel N]
 //
 // --gpus N: one process, N handles (fdoct_clone_to_device), one host thread per handle; the frames are sharded with
 // fdoct_shard_frames (contiguous ranges, averaging groups never split -- the rule of the multi-process path,
@@ -30,6 +30,10 @@
 // BscanFFTspinjnt.cpp:1856-1861) on every output B-scan between the chain and everything written below, on the GPU
 // (include/fdoct_bscanbin.h), with the reference's own arguments: upx = BX * BINVALUEY, upy = BY and multiplyfactor =
 // BX * BY * BINVALUEX * BINVALUEY (835).  The outputs then have (D / BY) * upy depths and (H / BX) * upx A-scans.
+// --channel N: BscanFFTwebcam.ini's channelnum (BscanFFTwebcam.cpp:1015-1038).  --frames then holds 8-bit, 3-channel
+// interleaved B,G,R frames -- a 3-channel .ocv dump, or raw H x W x 3 bytes -- and the GPU takes channel N (0, 1, 2 = B, G, R) or
+// the scaled sum (3) of every frame (include/fdoct_colour.h) ahead of the capture, the chain and the max-intensity line.  A
+// --background file stays a mono frame or spectrum of --bits samples.
 // --max-intensity: the status line's "Max intensity = <floor(max)>" (BscanFFT.cpp:1105-1108) for every reconstructed frame.
 // --frames holds one or more H x W frames back to back (u8 for --bits 8, little-endian u16 for --bits 16).
 // Outputs: <prefix>_bscan.f32 / <prefix>_bscandb.f32 (reference layout D x H per B-scan, main:1220) and
@@ -50,6 +54,7 @@
 #include "../include/fdoct.h"
 #include "../include/fdoct_bscanbin.h"
 #include "../include/fdoct_capture.h"
+#include "../include/fdoct_colour.h"
 #include "../include/fdoct_lowpass.h"
 #include "../include/fdoct_roi.h"
 #include "ocv_io.h"
@@ -87,6 +92,7 @@ int main(int argc, char** argv) {
   int capture_lowpass = 0, capture_raw = 0;  // --capture-lowpass, --capture-raw: fdoct_set_capture_options
   bool max_intensity = false;      // --max-intensity
   int bbin[4] = {0, 0, 1, 1};      // --bscan-bin bscanbinx,bscanbiny[,binvaluex,binvaluey] (0: off)
+  int channel = -1;                // --channel channelnum (-1: mono frames)
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -132,6 +138,7 @@ int main(int argc, char** argv) {
     else if (a == "--capture-lowpass") capture_lowpass = 1;
     else if (a == "--capture-raw") capture_raw = 1;
     else if (a == "--max-intensity") max_intensity = true;
+    else if (a == "--channel") channel = std::atoi(next());
     else if (a == "--devices") {
       for (const char* p = next(); *p;) {
         devices.push_back(std::atoi(p));
@@ -151,16 +158,21 @@ int main(int argc, char** argv) {
   if (cfg.numdisplaypoints <= 0) cfg.numdisplaypoints = cfg.numfftpoints / 2;
   const fdoct_dtype dt = bits == 8 ? FDOCT_U8 : FDOCT_U16;
   const size_t es = bits == 8 ? 1 : 2;
-  const size_t frame_bytes = (size_t)cfg.width * cfg.height * es;
+  if (channel >= 0 && bits != 8) {
+    std::fprintf(stderr, "--channel takes 8-bit B,G,R frames: give --bits 8\n");
+    return 1;
+  }
+  const int frame_channels = channel >= 0 ? 3 : 1;
+  const size_t frame_bytes = (size_t)cfg.width * cfg.height * es * frame_channels;
 
   // frames saved by the instrument programs as .ocv Mat dumps (BscanFFTspinj.cpp:672-738) carry their own
   // geometry; raw .bin files take it from the command line
   std::vector<unsigned char> frames, bg;
-  auto load = [&](const std::string& path, std::vector<unsigned char>* out) {
+  auto load = [&](const std::string& path, std::vector<unsigned char>* out, int channels) {
     if (ends_with(path, ".ocv")) {
       OcvMat m;
-      if (!ocv_read(path, &m) || (m.depth != 0 && m.depth != 2) || m.channels != 1 || m.cols != cfg.width) {
-        std::fprintf(stderr, "%s: not a single-channel 8/16-bit .ocv frame of width %d\n", path.c_str(), cfg.width);
+      if (!ocv_read(path, &m) || (m.depth != 0 && m.depth != 2) || m.channels != channels || m.cols != cfg.width) {
+        std::fprintf(stderr, "%s: not a %d-channel 8/16-bit .ocv frame of width %d\n", path.c_str(), channels, cfg.width);
         std::exit(1);
       }
       if ((m.depth == 0 ? 8 : 16) != bits) {
@@ -172,8 +184,8 @@ int main(int argc, char** argv) {
       *out = read_file(path);
     }
   };
-  load(frames_path, &frames);
-  if (capture_bg == 0) load(bg_path, &bg);
+  load(frames_path, &frames, frame_channels);
+  if (capture_bg == 0) load(bg_path, &bg, 1);
   const int nframes_file = (int)(frames.size() / frame_bytes) - capture_bg;  // (the captured frames are not reconstructed)
   const unsigned char* live = frames.data() + (size_t)capture_bg * frame_bytes;
   if (nframes_file < 1) {
@@ -190,7 +202,7 @@ int main(int argc, char** argv) {
   }
   int bg_rows = 0;
   if (capture_bg > 0) bg_rows = cfg.height;
-  else if (bg.size() >= frame_bytes) bg_rows = cfg.height;
+  else if (bg.size() >= (size_t)cfg.width * cfg.height * es) bg_rows = cfg.height;
   else if (bg.size() >= (size_t)cfg.width * es) bg_rows = 1;
   else {
     std::fprintf(stderr, "background file too small\n");
@@ -201,6 +213,10 @@ int main(int argc, char** argv) {
   int rc = fdoct_create(&cfg, &h);  // replaces the one-time set-up sim:385-534, 765-773
   if (rc) {
     std::fprintf(stderr, "fdoct_create: %d %s\n", rc, fdoct_last_error(nullptr));
+    return 1;
+  }
+  if (channel >= 0 && (rc = fdoct_set_colour_input(h, channel))) {  // webcam:1015-1038: every frame below is B,G,R
+    std::fprintf(stderr, "fdoct_set_colour_input: %s\n", fdoct_last_error(h));
     return 1;
   }
   // the 'b' key: data_yb <- backg (sim:803-813)
