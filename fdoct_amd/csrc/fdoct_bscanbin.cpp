@@ -9,9 +9,6 @@ using namespace fdoct_impl;
 
 namespace {
 
-bool valid_layout(fdoct_layout l) { return l == FDOCT_LAYOUT_ROWMAJOR_HxD || l == FDOCT_LAYOUT_TRANSPOSED_DxH; }
-bool valid_mem(fdoct_memspace m) { return m == FDOCT_MEM_HOST || m == FDOCT_MEM_DEVICE; }
-
 // The geometry's checks, shared by fdoct_bscanbin_size and fdoct_bscan_bin.  h may be null (the host-only entry point).
 int check_geometry(fdoct_ctx* h, const char* fn, int depths, int ascans, int binx, int biny, int upx, int upy) {
   const std::string f(fn);
@@ -25,11 +22,6 @@ int check_geometry(fdoct_ctx* h, const char* fn, int depths, int ascans, int bin
   if ((long long)(depths / biny) * upy > (1 << 30) || (long long)(ascans / binx) * upx > (1 << 30))
     return fail(h, FDOCT_ERR_INVALID, f + ": the result is too large");
   return FDOCT_OK;
-}
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return a && b && x < y + nb && y < x + na;
 }
 
 // The device's tap table follows the up factors of the last call.  A change waits for the kernels that still read the old one.
@@ -100,37 +92,24 @@ int fdoct_bscan_bin(fdoct_handle h, const float* bscan, const float* jscan, fdoc
   a.NR = a.R / a.binr, a.NC = a.C / a.binc, a.OR = a.NR * a.upr, a.OC = a.NC * a.upc;
   a.in_bs = (long long)image, a.out_bs = (long long)od * oa;
   a.mask = !jscan && h->cfg.dc_mask && od > 4;                            // 1873-1874; none behind the lock-in (1902-1903)
-  a.eps = (double)((h->cfg.variant == FDOCT_VARIANT_SIM) ? 1e-6f : 1e-5f);  // the chain's own epsilon
+  a.eps = (double)chain_eps(h);
   a.inv_area = 1.0 / ((double)binx * biny);
   a.mf = multiplyfactor;
 
   // everything that can fail without the kernel comes before anything is enqueued: workspaces, the tap table
-  const bool in_host = mem == FDOCT_MEM_HOST, out_host = out_mem == FDOCT_MEM_HOST;
-  if (in_host)
-    if (int rc = h->ws_bin_in.reserve(h, (in_floats + (jscan ? image : 0)) * sizeof(float))) return rc;
-  if (out_host)
-    if (int rc = h->ws_bin_out.reserve(h, out_floats * sizeof(float) * ((out_bscan ? 1 : 0) + (out_db ? 1 : 0)))) return rc;
+  StagePlan sp;
+  const int in = sp.in(bscan, mem, in_floats * sizeof(float)), js = sp.in(jscan, mem, image * sizeof(float));
+  const int lin = sp.out(out_bscan, out_mem, out_floats * sizeof(float)), db = sp.out(out_db, out_mem, out_floats * sizeof(float));
+  if (int rc = stage_reserve(h, &sp)) return rc;
   if (int rc = ensure_taps(h, upx, upy)) return rc;
-  a.taps = h->d_bin_taps;
-  a.in = in_host ? static_cast<float*>(h->ws_bin_in) : bscan;
-  a.jscan = !jscan ? nullptr : (in_host ? static_cast<float*>(h->ws_bin_in) + in_floats : jscan);
-  a.out_lin = !out_bscan ? nullptr : (out_host ? static_cast<float*>(h->ws_bin_out) : out_bscan);
-  a.out_db = !out_db ? nullptr : (out_host ? static_cast<float*>(h->ws_bin_out) + (out_bscan ? out_floats : 0) : out_db);
+  a.taps = h->d_bin_taps, a.in = sp.dev<const float>(in), a.jscan = sp.dev<const float>(js);
+  a.out_lin = sp.dev<float>(lin), a.out_db = sp.dev<float>(db);
   fdoct::bscanbin_plan(&a, h->num_cu);
   if (a.blocks < 1 || a.lds_bytes > 64 * 1024)  // (no factors within the limits get here: 32 x 128 outputs need 45 KiB at most)
     return fail(h, FDOCT_ERR_UNSUPPORTED, "fdoct_bscan_bin: the tile does not fit a workgroup's LDS");
-
-  if (in_host) {
-    HIP_TRY(h, hipMemcpyAsync(h->ws_bin_in, bscan, in_floats * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (jscan) HIP_TRY(h, hipMemcpyAsync(static_cast<float*>(h->ws_bin_in) + in_floats, jscan, image * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  }
+  if (int rc = stage_upload(h, sp)) return rc;
   HIP_TRY(h, fdoct::launch_bscan_bin(a, h->stream));
-  if (out_host) {
-    if (out_bscan) HIP_TRY(h, hipMemcpyAsync(out_bscan, a.out_lin, out_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (out_db) HIP_TRY(h, hipMemcpyAsync(out_db, a.out_db, out_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  }
-  if (in_host || out_host) HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return FDOCT_OK;
+  return stage_finish(h, sp);
 } FDOCT_CATCH(h)
 
 }  // extern "C"

@@ -632,17 +632,18 @@ int fdoct_frontend(fdoct_handle h, const void* raw, fdoct_dtype dtype, int nfram
   if (pitch_bytes < es * raw_w) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a raw camera row");
   DEVICE_SCOPE(h);
   int rc;
-  const size_t packed = (es * raw_w + 15) & ~(size_t)15;
-  if ((rc = h->ws_raw.reserve(h, packed * (size_t)raw_h * nframes))) return rc;
-  HIP_TRY(h, hipMemcpy2DAsync(h->ws_raw, packed, raw, pitch_bytes, es * raw_w, (size_t)raw_h * nframes, hipMemcpyHostToDevice,
-                              h->stream));
+  StagePlan sp;
+  const int in = sp.in(raw, FDOCT_MEM_HOST, es * raw_w, (size_t)raw_h * nframes, pitch_bytes);
+  sp.sync = true;  // (out is host memory: copied from the front end's own workspace)
+  if ((rc = stage_reserve(h, &sp))) return rc;
+  if ((rc = run_frontend(h, nullptr, kdt, nframes, raw_w, raw_h, 0, mediann, binx, biny, nullptr, nullptr))) return rc;
+  if ((rc = stage_upload(h, sp))) return rc;
   void* fo = nullptr;
   size_t fp = 0;
-  if ((rc = run_frontend(h, h->ws_raw, kdt, nframes, raw_w, raw_h, packed, mediann, binx, biny, &fo, &fp))) return rc;
+  if ((rc = run_frontend(h, sp.dev<void>(in), kdt, nframes, raw_w, raw_h, sp.pitch(in), mediann, binx, biny, &fo, &fp))) return rc;
   const int ow = raw_w / binx, oh = raw_h / biny;
   HIP_TRY(h, hipMemcpy2DAsync(out, es * ow, fo, fp, es * ow, (size_t)oh * nframes, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return FDOCT_OK;
+  return stage_finish(h, sp);
 } FDOCT_CATCH(h)
 
 int fdoct_set_colormap(fdoct_handle h, const unsigned char* bgr256) try {
@@ -672,36 +673,21 @@ int fdoct_display(fdoct_handle h, const float* bscandb, fdoct_memspace in_mem, i
   int rc;
   const long long count = (long long)rows * cols;
   const size_t total = (size_t)count * nbscans;
-  const float* d_in = bscandb;
-  if (in_mem == FDOCT_MEM_HOST) {
-    if ((rc = h->ws_disp_in.reserve(h, total * sizeof(float)))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->ws_disp_in, bscandb, total * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    d_in = h->ws_disp_in;
-  }
-  if (h->lut_dirty || !h->d_lut) {
-    if (!h->d_lut && (rc = h->d_lut.assign(h, 768))) return rc;
+  StagePlan sp;
+  const int in = sp.in(bscandb, in_mem, total * sizeof(float)), gray = sp.out(out_gray, out_mem, total), bgr = sp.out(out_bgr, out_mem, 3 * total);
+  if ((rc = stage_reserve(h, &sp))) return rc;
+  if (!h->d_lut && (rc = h->d_lut.assign(h, 768))) return rc;
+  if ((rc = h->d_disp_part.reserve(h, (size_t)nbscans * display_parts(count) * 2 * sizeof(double)))) return rc;
+  if ((rc = stage_upload(h, sp))) return rc;
+  if (h->lut_dirty) {  // (true until an upload has succeeded: a d_lut just made is covered)
     HIP_TRY(h, hipMemcpyAsync(h->d_lut, h->lut, 768, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // h->lut may change right after we return
     h->lut_dirty = false;
   }
-  if ((rc = h->d_disp_part.reserve(h, (size_t)nbscans * display_parts(count) * 2 * sizeof(double))))
-    return rc;
-  unsigned char *d_gray = out_gray, *d_bgr = out_bgr;
-  if (out_mem == FDOCT_MEM_HOST) {
-    const size_t need = (out_gray ? total : 0) + (out_bgr ? 3 * total : 0);
-    if ((rc = h->ws_disp_out.reserve(h, need))) return rc;
-    unsigned char* w = static_cast<unsigned char*>(h->ws_disp_out);
-    d_bgr = out_bgr ? w : nullptr;  // colour first: its 12-byte groups stay 4-byte aligned
-    d_gray = out_gray ? w + (out_bgr ? 3 * total : 0) : nullptr;
-  }
   const long long clamp_at = clampupper ? 5LL * cols + 5 : -1;  // bscandisp.at<double>(5, 5), main:1252
-  HIP_TRY(h, launch_display(d_in, count, nbscans, bscanthreshold, clamp_at, h->d_disp_part, h->d_lut, d_gray, d_bgr, h->stream));
-  if (out_mem == FDOCT_MEM_HOST) {
-    if (out_gray) HIP_TRY(h, hipMemcpyAsync(out_gray, d_gray, total, hipMemcpyDeviceToHost, h->stream));
-    if (out_bgr) HIP_TRY(h, hipMemcpyAsync(out_bgr, d_bgr, 3 * total, hipMemcpyDeviceToHost, h->stream));
-  }
-  if (in_mem == FDOCT_MEM_HOST || out_mem == FDOCT_MEM_HOST) HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return FDOCT_OK;
+  HIP_TRY(h, launch_display(sp.dev<const float>(in), count, nbscans, bscanthreshold, clamp_at, h->d_disp_part, h->d_lut,
+                            sp.dev<unsigned char>(gray), sp.dev<unsigned char>(bgr), h->stream));
+  return stage_finish(h, sp);
 } FDOCT_CATCH(h)
 
 int fdoct_lockin_db(fdoct_handle h, const float* bscan, const float* jscan, fdoct_memspace mem, int nbscans, size_t count,
@@ -710,21 +696,13 @@ int fdoct_lockin_db(fdoct_handle h, const float* bscan, const float* jscan, fdoc
   if (!bscan || !jscan || !out_db || nbscans <= 0 || count == 0) return fail(h, FDOCT_ERR_INVALID, "fdoct_lockin_db: bad arguments");
   DEVICE_SCOPE(h);
   const size_t total = count * (size_t)nbscans;
-  if (mem == FDOCT_MEM_DEVICE) {
-    HIP_TRY(h, launch_lockin_db(bscan, jscan, (long long)total, (long long)count, out_db, h->stream));
-    return FDOCT_OK;
-  }
-  int rc;
-  if ((rc = h->ws_disp_in.reserve(h, total * sizeof(float)))) return rc;
-  if ((rc = h->ws_disp_in2.reserve(h, count * sizeof(float)))) return rc;
-  if ((rc = h->ws_disp_out.reserve(h, total * sizeof(float)))) return rc;
-  HIP_TRY(h, hipMemcpyAsync(h->ws_disp_in, bscan, total * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(h->ws_disp_in2, jscan, count * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, launch_lockin_db(h->ws_disp_in, h->ws_disp_in2, (long long)total, (long long)count,
-                              reinterpret_cast<float*>(static_cast<unsigned char*>(h->ws_disp_out)), h->stream));
-  HIP_TRY(h, hipMemcpyAsync(out_db, h->ws_disp_out, total * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return FDOCT_OK;
+  if (mem != FDOCT_MEM_DEVICE) mem = FDOCT_MEM_HOST;  // (every other value has always read as host memory here)
+  StagePlan sp;
+  const int b = sp.in(bscan, mem, total * sizeof(float)), j = sp.in(jscan, mem, count * sizeof(float));
+  const int o = sp.out(out_db, mem, total * sizeof(float));
+  if (int rc = stage_begin(h, &sp)) return rc;
+  HIP_TRY(h, launch_lockin_db(sp.dev<const float>(b), sp.dev<const float>(j), (long long)total, (long long)count, sp.dev<float>(o), h->stream));
+  return stage_finish(h, sp);
 } FDOCT_CATCH(h)
 
 int fdoct_set_averages(fdoct_handle h, int averages) try {

@@ -13,14 +13,14 @@ using namespace fdoct_impl;
 
 namespace {
 
-bool valid_mem(fdoct_memspace m) { return m == FDOCT_MEM_HOST || m == FDOCT_MEM_DEVICE; }
 bool has_frontend(const fdoct_ctx* h) { return h->fe_median > 0 || h->fe_binx > 1 || h->fe_biny > 1; }
 
 // What a call does with its frames, decided (and refused) before anything is enqueued.
 struct FramePlan {
-  const void* frames = nullptr;
+  StagePlan stage;  // the frames are its item 0; a call adds its outputs
+  fdoct::CaptureFrames cf;  // what the kernels read: front_passes fills it
   fdoct_dtype dtype = FDOCT_U16;
-  bool host = false, frontend = false;
+  bool frontend = false;
   bool colour = false;  // interleaved B,G,R frames (fdoct_set_colour_input): es is 3, the colour stage runs in the front end's place
   int nframes = 0, raw_w = 0, raw_h = 0;
   size_t es = 0, pitch = 0;
@@ -36,7 +36,7 @@ int plan_frames(fdoct_ctx* h, const char* fn, const void* frames, fdoct_dtype dt
   }
   const size_t es = frame_pixel_bytes(h, dtype);
   if (!es) return fail(h, FDOCT_ERR_INVALID, who + "bad dtype");
-  p->frames = frames, p->dtype = dtype, p->host = space == FDOCT_MEM_HOST, p->nframes = nframes, p->es = es;
+  p->dtype = dtype, p->nframes = nframes, p->es = es;
   p->frontend = has_frontend(h);
   p->raw_w = h->W * (p->frontend ? h->fe_binx : 1);
   p->raw_h = h->H * (p->frontend ? h->fe_biny : 1);
@@ -50,35 +50,24 @@ int plan_frames(fdoct_ctx* h, const char* fn, const void* frames, fdoct_dtype dt
     if (h->fe_median == 7 && dtype == FDOCT_U16)
       return fail(h, FDOCT_ERR_INVALID, who + "a 7x7 median exists for 8-bit frames only (cv::medianBlur)");
   }
+  p->stage.in(frames, space, es * p->raw_w, (size_t)p->raw_h * nframes, p->pitch);
   return FDOCT_OK;
 }
 
-// Enqueues what stands between the caller's frames and the kernels: the upload of host frames, then the front end.
-int stage_frames(fdoct_ctx* h, const FramePlan& p, fdoct::CaptureFrames* cf) {
-  const void* src = p.frames;
-  size_t pitch = p.pitch;
-  if (p.host) {
-    const size_t packed = (p.es * p.raw_w + 15) & ~(size_t)15;
-    if (int rc = h->ws_raw.reserve(h, packed * (size_t)p.raw_h * p.nframes)) return rc;
-    HIP_TRY(h, hipMemcpy2DAsync(h->ws_raw, packed, p.frames, p.pitch, p.es * p.raw_w, (size_t)p.raw_h * p.nframes,
-                                hipMemcpyHostToDevice, h->stream));
-    src = h->ws_raw;
-    pitch = packed;
-  }
+// What stands between the frames on the device (the caller's, or the plan's item 0 after its upload) and the kernels: the colour
+// stage or the front end.  src null: their checks and workspaces only, and p.cf gets its shape -- nothing is enqueued.
+int front_passes(fdoct_ctx* h, FramePlan& p, const void* src) {
+  size_t pitch = p.stage.pitch(0);
   fdoct_dtype dt = p.dtype;
+  void* o = nullptr;
   if (p.colour) {  // webcam:1015-1038 ahead of everything, the median / binning with it
-    void* co = nullptr;
-    if (int rc = run_colour(h, src, p.nframes, p.raw_w, p.raw_h, pitch, h->colour, h->fe_median, h->fe_binx, h->fe_biny, &co, &pitch)) return rc;
-    src = co;
+    if (int rc = run_colour(h, src, p.nframes, p.raw_w, p.raw_h, pitch, h->colour, h->fe_median, h->fe_binx, h->fe_biny, &o, &pitch)) return rc;
     if (h->colour == 3) dt = FDOCT_F64;
   } else if (p.frontend) {
-    void* fo = nullptr;
-    if (int rc = run_frontend(h, src, kernel_dtype(p.dtype), p.nframes, p.raw_w, p.raw_h, pitch, h->fe_median, h->fe_binx,
-                              h->fe_biny, &fo, &pitch))
+    if (int rc = run_frontend(h, src, kernel_dtype(p.dtype), p.nframes, p.raw_w, p.raw_h, pitch, h->fe_median, h->fe_binx, h->fe_biny, &o, &pitch))
       return rc;
-    src = fo;
   }
-  cf->frames = src, cf->dt = dt, cf->pitch = pitch, cf->nframes = p.nframes, cf->H = h->H, cf->W = h->W;
+  p.cf.frames = o ? o : src, p.cf.dt = dt, p.cf.pitch = pitch, p.cf.nframes = p.nframes, p.cf.H = h->H, p.cf.W = h->W;
   return FDOCT_OK;
 }
 
@@ -103,14 +92,17 @@ int fdoct_capture_reference(fdoct_handle h, int role, const void* frames, fdoct_
   if ((role == FDOCT_REF_PI || plain_copy) && nframes != 1)
     return fail(h, FDOCT_ERR_INVALID, "fdoct_capture_reference: this role takes exactly one frame (main:1081, sim:803-825)");
   DEVICE_SCOPE(h);
-  fdoct::CaptureFrames cf;
-  if (int rc = stage_frames(h, p, &cf)) return rc;
   const size_t count = (size_t)h->H * h->W;
+  if (int rc = stage_reserve(h, &p.stage)) return rc;
+  if (int rc = front_passes(h, p, nullptr)) return rc;
   if (int rc = h->ws_cap_acc.reserve(h, count * sizeof(double))) return rc;
+  if (int rc = h->cap_lowpass ? enqueue_lowpass(h, nullptr, 0, nullptr, 0, h->H, h->W) : FDOCT_OK) return rc;
+  if (int rc = stage_upload(h, p.stage)) return rc;  // (no stage_finish: no staged output, and the call synchronises itself)
+  if (int rc = front_passes(h, p, p.stage.dev<const void>(0))) return rc;
   // saveinterferograms (fdoct_set_capture_options): the binned frames are accumulated as they are (main:1024)
   const int movavgn = (!sim && h->cfg.movavgn > 0 && !h->cap_raw) ? h->cfg.movavgn : 0;
   const bool accumulates = !(role == FDOCT_REF_PI || plain_copy);  // (the p key copies one data_y, main:1081)
-  HIP_TRY(h, fdoct::launch_capture_accumulate(cf, movavgn, accumulates, h->ws_cap_acc, h->num_cu, h->stream));
+  HIP_TRY(h, fdoct::launch_capture_accumulate(p.cf, movavgn, accumulates, h->ws_cap_acc, h->num_cu, h->stream));
   std::vector<double> v(count);
   HIP_TRY(h, hipMemcpyAsync(v.data(), h->ws_cap_acc, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -163,21 +155,15 @@ int fdoct_frame_minmax(fdoct_handle h, const void* frames, fdoct_dtype dtype, fd
   FramePlan p;
   if (int rc = plan_frames(h, "fdoct_frame_minmax", frames, dtype, space, nframes, pitch_bytes, &p)) return rc;
   DEVICE_SCOPE(h);
-  fdoct::CaptureFrames cf;
-  if (int rc = stage_frames(h, p, &cf)) return rc;
   const size_t n = (size_t)nframes;
-  if (int rc = h->ws_cap_mm.reserve(h, (2 * n + fdoct::frame_minmax_partials(cf, h->num_cu)) * sizeof(double))) return rc;
-  double* ws = h->ws_cap_mm;
-  const bool to_host = out_space == FDOCT_MEM_HOST;
-  double* d_min = to_host ? ws : out_min;
-  double* d_max = to_host ? ws + n : out_max;
-  HIP_TRY(h, fdoct::launch_frame_minmax(cf, ws + 2 * n, d_min, d_max, h->num_cu, h->stream));
-  if (to_host) {
-    if (out_min) HIP_TRY(h, hipMemcpyAsync(out_min, d_min, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (out_max) HIP_TRY(h, hipMemcpyAsync(out_max, d_max, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
-  if (to_host || p.host) HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return FDOCT_OK;
+  const int lo = p.stage.out(out_min, out_space, n * sizeof(double)), hi = p.stage.out(out_max, out_space, n * sizeof(double));
+  if (int rc = stage_reserve(h, &p.stage)) return rc;
+  if (int rc = front_passes(h, p, nullptr)) return rc;  // (the partials follow from the frames' shape)
+  if (int rc = h->ws_cap_mm.reserve(h, fdoct::frame_minmax_partials(p.cf, h->num_cu) * sizeof(double))) return rc;
+  if (int rc = stage_upload(h, p.stage)) return rc;
+  if (int rc = front_passes(h, p, p.stage.dev<const void>(0))) return rc;
+  HIP_TRY(h, fdoct::launch_frame_minmax(p.cf, h->ws_cap_mm, p.stage.dev<double>(lo), p.stage.dev<double>(hi), h->num_cu, h->stream));
+  return stage_finish(h, p.stage);
 } FDOCT_CATCH(h)
 
 int fdoct_normalize_minmax(double* y, size_t n, double lo, double hi) try {

@@ -206,7 +206,6 @@ __global__ __launch_bounds__(CAP_BLOCK) void frame_minmax_fold_kernel(const doub
 bool vec_ok(const CaptureFrames& in) {
   return (reinterpret_cast<uintptr_t>(in.frames) % 16 == 0) && (in.pitch % 16 == 0);  // (a frame is H rows: its stride follows)
 }
-int resident_blocks(int num_cu) { return (num_cu > 0 ? num_cu : 256) * (CAP_WAVES_PER_CU / (CAP_BLOCK / 64)); }
 long long runs_of(const CaptureFrames& in, int es) { return (long long)in.H * ((in.W + 16 / es - 1) / (16 / es)); }
 int sample_bytes(int dt) { return dt == FDOCT_U8 ? 1 : dt == FDOCT_U16 ? 2 : dt == FDOCT_F32 ? 4 : 8; }
 
@@ -222,7 +221,7 @@ hipError_t launch_capture_accumulate(const CaptureFrames& in, int movavgn, bool 
   a.zero_start = zero_start;
   a.out = out;
   const long long items = runs_of(in, sample_bytes(in.dt));
-  const int blocks = (int)std::min<long long>((items + CAP_BLOCK - 1) / CAP_BLOCK, resident_blocks(num_cu));
+  const int blocks = (int)std::min<long long>((items + CAP_BLOCK - 1) / CAP_BLOCK, resident_blocks(num_cu, CAP_WAVES_PER_CU, CAP_BLOCK));
   switch (in.dt) {
     case FDOCT_U8: hipLaunchKernelGGL(capture_accumulate_kernel<uint8_t>, dim3(blocks), dim3(CAP_BLOCK), 0, st, a); break;
     case FDOCT_U16: hipLaunchKernelGGL(capture_accumulate_kernel<uint16_t>, dim3(blocks), dim3(CAP_BLOCK), 0, st, a); break;
@@ -236,7 +235,7 @@ hipError_t launch_capture_accumulate(const CaptureFrames& in, int movavgn, bool 
 int frame_minmax_blocks(const CaptureFrames& in, int num_cu) {
   const long long items = runs_of(in, sample_bytes(in.dt));
   const long long want = (items + CAP_BLOCK - 1) / CAP_BLOCK;
-  const long long share = std::max(1, resident_blocks(num_cu) / std::max(1, in.nframes));
+  const long long share = std::max(1, resident_blocks(num_cu, CAP_WAVES_PER_CU, CAP_BLOCK) / std::max(1, in.nframes));
   return (int)std::max<long long>(1, std::min(want, share));
 }
 

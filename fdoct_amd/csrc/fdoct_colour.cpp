@@ -9,12 +9,6 @@
 
 using namespace fdoct_impl;
 
-namespace {
-
-bool valid_mem(fdoct_memspace m) { return m == FDOCT_MEM_HOST || m == FDOCT_MEM_DEVICE; }
-
-}  // namespace
-
 // ------------------------------------------------------------------ C ABI --
 extern "C" {
 
@@ -42,28 +36,23 @@ int fdoct_colour_extract(fdoct_handle h, const void* bgr, fdoct_memspace space, 
   if (binx < 1 || biny < 1 || raw_w % binx || raw_h % biny)
     return fail(h, FDOCT_ERR_INVALID, "fdoct_colour_extract: frame size must be a multiple of the bin factors");
   const size_t row = 3 * (size_t)raw_w;
-  size_t pitch = pitch_bytes ? pitch_bytes : row;
+  const size_t pitch = pitch_bytes ? pitch_bytes : row;
   if (pitch < row) return fail(h, FDOCT_ERR_INVALID, "fdoct_colour_extract: pitch smaller than a row of B,G,R pixels");
   if (!h) return FDOCT_ERR_INVALID;
   DEVICE_SCOPE(h);
-  const bool in_host = space == FDOCT_MEM_HOST, out_host = out_space == FDOCT_MEM_HOST;
-  const size_t rows = (size_t)raw_h * nframes;
-  const void* src = bgr;
-  if (in_host) {  // host frames go up as packed, 16-byte-pitched rows
-    const size_t packed = (row + 15) & ~(size_t)15;
-    if (int rc = h->ws_raw.reserve(h, packed * rows)) return rc;
-    HIP_TRY(h, hipMemcpy2DAsync(h->ws_raw, packed, bgr, pitch, row, rows, hipMemcpyHostToDevice, h->stream));
-    src = h->ws_raw;
-    pitch = packed;
-  }
+  StagePlan sp;
+  const int in = sp.in(bgr, space, row, (size_t)raw_h * nframes, pitch);  // host frames go up as packed, 16-byte-pitched rows
+  sp.sync |= out_space == FDOCT_MEM_HOST;                                    // (out: copied from the stage's own workspace)
+  if (int rc = stage_reserve(h, &sp)) return rc;
+  if (int rc = run_colour(h, nullptr, nframes, raw_w, raw_h, sp.pitch(in), channelnum, mediann, binx, biny, nullptr, nullptr)) return rc;
+  if (int rc = stage_upload(h, sp)) return rc;
   void* co = nullptr;
   size_t cp = 0;
-  if (int rc = run_colour(h, src, nframes, raw_w, raw_h, pitch, channelnum, mediann, binx, biny, &co, &cp)) return rc;
+  if (int rc = run_colour(h, sp.dev<const void>(in), nframes, raw_w, raw_h, sp.pitch(in), channelnum, mediann, binx, biny, &co, &cp)) return rc;
   const size_t out_row = (size_t)(raw_w / binx) * (channelnum == 3 ? sizeof(double) : 1);
   HIP_TRY(h, hipMemcpy2DAsync(out, out_row, co, cp, out_row, (size_t)(raw_h / biny) * nframes,
-                              out_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
-  if (in_host || out_host) HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return FDOCT_OK;
+                              out_space == FDOCT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+  return stage_finish(h, sp);
 } FDOCT_CATCH(h)
 
 double fdoct_colour_sum_scale(void) try { return fdoct::kColourSumScale; } FDOCT_CATCH_RETURN(nullptr, 0.0)

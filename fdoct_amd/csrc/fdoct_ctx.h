@@ -9,6 +9,7 @@
 //   fdoct_lowpass.cpp those of include/fdoct_lowpass.h (BscanDark's lpfilter, the capture's options)
 //   fdoct_bscanbin.cpp those of include/fdoct_bscanbin.h (spinjnt's output binning between the linear B-scan and its dB)
 //   fdoct_colour.cpp  those of include/fdoct_colour.h (the webcam's interleaved B,G,R frames: channelnum)
+//   fdoct_stage.h     the staging plan of those side entry points' host-memory arguments (stage_reserve / stage_upload / stage_finish, below, commit it)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +34,7 @@
 #include "fdoct_host.h"
 #include "fdoct_kernels.h"
 #include "fdoct_launch.h"
+#include "fdoct_stage.h"
 #include "fdoct_wave.h"
 #include "fdoct_jit.h"
 #include "fdoct_hostcopy.h"
@@ -172,7 +174,8 @@ struct fdoct_ctx {
   DevBuf<float2> ws_ylin;
   long long ylin_rows = 0;  // A-scans the last staged run left in ws_ylin (0: none)
   DevBuf<float> ws_mov;
-  DevBuf<unsigned char> ws_front, ws_med, ws_raw;
+  DevBuf<unsigned char> ws_front, ws_med;
+  DevBuf<unsigned char> stage_in, stage_out;  // host-memory arguments of the side entry points on their way up and down (stage_reserve)
   int fe_median = 0, fe_binx = 1, fe_biny = 1;
   // display post-chain
   // host-pointer pipeline (fdoct_process with host buffers): copy-in / kernels / copy-out on three streams
@@ -190,8 +193,6 @@ struct fdoct_ctx {
   bool lut_dirty = true;
   DevBuf<unsigned char> d_lut;
   DevBuf<double> d_disp_part;
-  DevBuf<float> ws_disp_in, ws_disp_in2;
-  DevBuf<unsigned char> ws_disp_out;
   // B-scan readouts (fdoct_roi.cpp): measurement state, not set-up state, so neither fdoct_export_state nor
   // fdoct_clone_to_device carries it
   struct PeakHoldRoi {
@@ -202,21 +203,16 @@ struct fdoct_ctx {
   DevBuf<uint32_t> d_hold_cols;    // 4 slots x roi.w column holds, as roi_encode words (fdoct_roi_kernels.h)
   DevBuf<uint32_t> d_hold_scalar;  // 4 scalar holds of A-scan roi.ascanat, likewise
   long long hold_count[4] = {0, 0, 0, 0};
-  DevBuf<float> ws_roi_in;         // host-memory dB images on their way to the readouts
-  DevBuf<double> ws_roi_out;       // ... and the per-B-scan results on their way back
-  // reference-frame capture (fdoct_capture.cpp): host frames go up through ws_raw, the front end through ws_med / ws_front
+  // reference-frame capture (fdoct_capture.cpp): the front end goes through ws_med / ws_front
   DevBuf<double> ws_cap_acc;       // the H x W sums on their way to the host
-  DevBuf<double> ws_cap_mm;        // per-frame min / max: the results (2 * nframes), then the per-block partials
+  DevBuf<double> ws_cap_mm;        // per-frame min / max: the per-block partials
   // fdoct_set_capture_options (fdoct_lowpass.cpp): BscanDark.ini's lowpassfilter and the ini's saveinterferograms.  Run-time
   // settings like the front end's: fdoct_clone_to_device carries them, the state blob does not.
   int cap_lowpass = 0, cap_raw = 0;
-  DevBuf<double> ws_lp_io;         // fdoct_lowpass_rows: host rows on their way to the kernel and back (packed)
   DevBuf<double> ws_lp_bins;       // rows too long for LDS: their bins (LowpassShape::ws_doubles)
   // spinjnt's output binning (fdoct_bscanbin.cpp)
   DevBuf<double> d_bin_taps;       // the cubic's phases for bin_taps_upx / bin_taps_upy (fdoct_bscanbin_kernels.h), uploaded when they change
   int bin_taps_upx = 0, bin_taps_upy = 0;
-  DevBuf<float> ws_bin_in;         // host-memory B-scans (and jscan behind them) on their way to the kernel
-  DevBuf<float> ws_bin_out;        // ... and out_bscan, then out_db, on their way back
   // fdoct_set_colour_input (fdoct_colour.cpp): BscanFFTwebcam.ini's channelnum.  -1: mono frames; 0 / 1 / 2: 8-bit frames are
   // interleaved B,G,R and that channel is taken; 3: their scaled sum, a frame of doubles.  A run-time setting like the front
   // end's: fdoct_clone_to_device carries it, the state blob does not.
@@ -284,6 +280,35 @@ template <typename T>
 int upload(fdoct_ctx* h, DevBuf<T>& d, const std::vector<T>& v) {
   if (int rc = d.assign(h, v.size())) return rc;
   if (!v.empty()) HIP_TRY(h, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return FDOCT_OK;
+}
+
+// The commit of a staging plan (fdoct_stage.h).  stage_reserve grows the handle's two staging buffers and sets the items' device
+// pointers; every other reservation and refusal of the call follows it, then stage_upload enqueues the host-to-device copies on
+// h->stream (stage_begin: both at once), and stage_finish the device-to-host copies and the synchronise host memory asks for.
+inline int stage_reserve(fdoct_ctx* h, StagePlan* p) {
+  if (p->rc) return fail(h, p->rc, "staging: the arguments' sizes do not fit size_t");
+  if (int rc = p->in_bytes ? h->stage_in.reserve(h, p->in_bytes) : FDOCT_OK) return rc;
+  if (int rc = p->out_bytes ? h->stage_out.reserve(h, p->out_bytes) : FDOCT_OK) return rc;
+  for (StageItem& it : p->item) it.dev = !it.staged ? it.ptr : (it.output && !it.on_input ? h->stage_out : h->stage_in) + it.offset;
+  return FDOCT_OK;
+}
+inline int stage_copy(fdoct_ctx* h, const StagePlan& p, bool down) {  // the staged inputs up, or the staged outputs down
+  for (const StageItem& it : p.item) {
+    if (!it.staged || !it.ptr || it.output != down) continue;
+    if (!it.dev) return fail(h, FDOCT_ERR_STATE, "staging: a copy before reserve");
+    void *const dst = down ? it.ptr : it.dev, *const src = down ? it.dev : it.ptr;
+    const size_t dp = down ? it.pitch : it.dev_pitch, sp = down ? it.dev_pitch : it.pitch;
+    const hipMemcpyKind kind = down ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
+    HIP_TRY(h, it.rows == 1 ? hipMemcpyAsync(dst, src, it.row, kind, h->stream) : hipMemcpy2DAsync(dst, dp, src, sp, it.row, it.rows, kind, h->stream));
+  }
+  return FDOCT_OK;
+}
+inline int stage_upload(fdoct_ctx* h, const StagePlan& p) { return stage_copy(h, p, false); }
+inline int stage_begin(fdoct_ctx* h, StagePlan* p) { const int rc = stage_reserve(h, p); return rc ? rc : stage_upload(h, *p); }
+inline int stage_finish(fdoct_ctx* h, const StagePlan& p) {
+  if (int rc = stage_copy(h, p, true)) return rc;
+  if (p.sync) HIP_TRY(h, hipStreamSynchronize(h->stream));
   return FDOCT_OK;
 }
 
@@ -399,11 +424,13 @@ inline size_t frame_pixel_bytes(const fdoct_ctx* h, int dtype) { return h->colou
 // front of the sum (cv::medianBlur rejects CV_64F: there is no reference behaviour to match).
 int colour_check(fdoct_ctx* h, const char* who, int channelnum, fdoct_dtype dtype, int mediann);
 // The colour stage on device-resident interleaved frames (fdoct_colour.hip), with the median / binning behind it: leaves packed,
-// 16-byte-pitched bytes (channelnum 0-2) or doubles (3) in a library workspace, *out / *out_pitch.  Enqueues only.
+// 16-byte-pitched bytes (channelnum 0-2) or doubles (3) in a library workspace, *out / *out_pitch.  Enqueues only.  With null
+// frames, both: their checks and workspaces alone, nothing enqueued (a call that uploads host frames does that first).
 int run_colour(fdoct_ctx* h, const void* d_bgr, int nframes, int raw_w, int raw_h, size_t pitch, int channelnum, int mediann, int binx,
                int biny, void** out, size_t* out_pitch);
 int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_w, int raw_h, size_t raw_pitch, int mediann,
                  int binx, int biny, void** out, size_t* out_pitch);
+float chain_eps(const fdoct_ctx* h);  // the epsilon under the chain's log (sim:949 / main:1222)
 int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
                  uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r);
 int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes,
@@ -411,7 +438,7 @@ int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, 
 
 // ---- fdoct_lowpass.cpp ----------------------------------------------------------------------------------------------------
 // Enqueues lpfilter (BscanDark.cpp:119-167) on device rows of W doubles (d_in == d_out: in place) and reserves the workspace a
-// long row needs.  The arguments are the caller's to check.
+// long row needs -- with d_in null that alone, like run_frontend.  The arguments are the caller's to check.
 int enqueue_lowpass(fdoct_ctx* h, const double* d_in, size_t in_pitch, double* d_out, size_t out_pitch, int rows, int W);
 
 }  // namespace fdoct_impl

@@ -13,17 +13,12 @@ int enqueue_lowpass(fdoct_ctx* h, const double* d_in, size_t in_pitch, double* d
   const fdoct::LowpassShape s = fdoct::lowpass_shape(rows, W, h->num_cu);
   if (s.ws_doubles)
     if (int rc = h->ws_lp_bins.reserve(h, s.ws_doubles * sizeof(double))) return rc;
+  if (!d_in) return FDOCT_OK;
   HIP_TRY(h, fdoct::launch_lowpass_rows(d_in, in_pitch, d_out, out_pitch, rows, W, h->ws_lp_bins, h->num_cu, h->stream));
   return FDOCT_OK;
 }
 
 }  // namespace fdoct_impl
-
-namespace {
-
-bool valid_mem(fdoct_memspace m) { return m == FDOCT_MEM_HOST || m == FDOCT_MEM_DEVICE; }
-
-}  // namespace
 
 // ------------------------------------------------------------------ C ABI --
 extern "C" {
@@ -54,21 +49,14 @@ int fdoct_lowpass_rows(fdoct_handle h, const double* in, fdoct_memspace in_space
   if (pitch % sizeof(double) || reinterpret_cast<uintptr_t>(in) % sizeof(double) || reinterpret_cast<uintptr_t>(out) % sizeof(double))
     return fail(h, FDOCT_ERR_INVALID, "fdoct_lowpass_rows: rows and pitch must be aligned to one double");
   DEVICE_SCOPE(h);
-  const bool in_host = in_space == FDOCT_MEM_HOST, out_host = out_space == FDOCT_MEM_HOST;
-  // host rows pass through a packed copy on the device; device rows are read and written where they lie
-  const double* d_in = in;
-  double* d_out = out;
-  size_t d_in_pitch = pitch, d_out_pitch = pitch;
-  if (in_host || out_host) {
-    if (int rc = h->ws_lp_io.reserve(h, row * (size_t)rows)) return rc;
-    if (in_host) d_in = h->ws_lp_io, d_in_pitch = row;
-    if (out_host) d_out = h->ws_lp_io, d_out_pitch = row;
-  }
-  if (in_host) HIP_TRY(h, hipMemcpy2DAsync(h->ws_lp_io, row, in, pitch, row, (size_t)rows, hipMemcpyHostToDevice, h->stream));
-  if (int rc = enqueue_lowpass(h, d_in, d_in_pitch, d_out, d_out_pitch, rows, width)) return rc;
-  if (out_host) HIP_TRY(h, hipMemcpy2DAsync(out, pitch, h->ws_lp_io, row, row, (size_t)rows, hipMemcpyDeviceToHost, h->stream));
-  if (in_host || out_host) HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return FDOCT_OK;
+  // host rows pass through a packed copy on the device (one, filtered in place, if both sides are host memory); device rows stay
+  StagePlan sp;
+  const int i = sp.in(in, in_space, row, (size_t)rows, pitch), o = sp.out_on(i, out, out_space, pitch);
+  if (int rc = stage_reserve(h, &sp)) return rc;
+  if (int rc = enqueue_lowpass(h, nullptr, 0, nullptr, 0, rows, width)) return rc;
+  if (int rc = stage_upload(h, sp)) return rc;
+  if (int rc = enqueue_lowpass(h, sp.dev<const double>(i), sp.pitch(i), sp.dev<double>(o), sp.pitch(o), rows, width)) return rc;
+  return stage_finish(h, sp);
 } FDOCT_CATCH(h)
 
 }  // extern "C"

@@ -158,7 +158,7 @@ LowpassShape lowpass_shape(int rows, int W, int num_cu) {
     s.G = 1, s.L = chunks * LP_T;
     s.lds = 0;
   }
-  const int cap = (num_cu > 0 ? num_cu : 256) * (LP_WAVES_PER_CU / (LP_BLOCK / 64));
+  const int cap = resident_blocks(num_cu, LP_WAVES_PER_CU, LP_BLOCK);
   s.blocks = std::max(1, std::min(rows, cap));
   s.ws_doubles = s.staged ? 0 : (size_t)s.blocks * 4 * s.f;
   return s;

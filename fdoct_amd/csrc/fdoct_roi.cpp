@@ -31,22 +31,10 @@ double besseldbinverse(double y) {
 // the displacement of one J0 argument, in the reference's order of operations: x * lambda0 * 1e9 / (4 * pi)
 double x_to_nm(double x, float lambda0) { return x * lambda0 * 1e9 / (4 * kPi); }
 
-bool valid_layout(fdoct_layout l) { return l == FDOCT_LAYOUT_ROWMAJOR_HxD || l == FDOCT_LAYOUT_TRANSPOSED_DxH; }
-bool valid_mem(fdoct_memspace m) { return m == FDOCT_MEM_HOST || m == FDOCT_MEM_DEVICE; }
-
-// The image a kernel reads: the caller's device pointer, or a host batch copied into the handle's workspace.
-int stage_image(fdoct_ctx* h, const float* bscandb, fdoct_memspace mem, fdoct_layout layout, int nbscans, int depths,
-                int ascans, RoiImage* im) {
-  im->nb = nbscans, im->depths = depths, im->ascans = ascans;
-  im->transposed = layout == FDOCT_LAYOUT_TRANSPOSED_DxH;
-  im->db = bscandb;
-  if (mem == FDOCT_MEM_HOST) {
-    const size_t bytes = (size_t)nbscans * depths * ascans * sizeof(float);
-    if (int rc = h->ws_roi_in.reserve(h, bytes)) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->ws_roi_in, bscandb, bytes, hipMemcpyHostToDevice, h->stream));
-    im->db = h->ws_roi_in;
-  }
-  return FDOCT_OK;
+size_t image_bytes(int nbscans, int depths, int ascans) { return (size_t)nbscans * depths * ascans * sizeof(float); }
+// The image a kernel reads once the call's staging plan is reserved: the caller's device pointer, or a host batch's device copy.
+RoiImage image_of(const StagePlan& sp, int item, fdoct_layout layout, int nbscans, int depths, int ascans) {
+  return RoiImage{sp.dev<const float>(item), nbscans, depths, ascans, layout == FDOCT_LAYOUT_TRANSPOSED_DxH};
 }
 
 int check_image(fdoct_ctx* h, const char* fn, const float* bscandb, fdoct_memspace mem, fdoct_layout layout, int nbscans,
@@ -92,22 +80,13 @@ int fdoct_ascan_minmax(fdoct_handle h, const float* bscandb, fdoct_memspace mem,
   if (depths < 5) return fail(h, FDOCT_ERR_INVALID, "fdoct_ascan_minmax: needs depths >= 5 (rows 0-3 read as row 4)");
   if (ascanat < 0 || ascanat >= ascans) return fail(h, FDOCT_ERR_INVALID, "fdoct_ascan_minmax: ascanat outside the image");
   DEVICE_SCOPE(h);
-  RoiImage im;
-  if (int rc = stage_image(h, bscandb, mem, layout, nbscans, depths, ascans, &im)) return rc;
-  float *d_min = out_min, *d_max = out_max;
-  if (out_mem == FDOCT_MEM_HOST || !out_min || !out_max) {  // (the kernel writes both: a missing one goes to the workspace)
-    if (int rc = h->ws_roi_out.reserve(h, (size_t)nbscans * sizeof(double))) return rc;
-    float* w = reinterpret_cast<float*>(static_cast<double*>(h->ws_roi_out));
-    if (out_mem == FDOCT_MEM_HOST || !out_min) d_min = w;
-    if (out_mem == FDOCT_MEM_HOST || !out_max) d_max = w + nbscans;
-  }
-  HIP_TRY(h, launch_roi_ascan_minmax(im, ascanat, d_min, d_max, h->num_cu, h->stream));
-  if (out_mem == FDOCT_MEM_HOST) {
-    if (out_min) HIP_TRY(h, hipMemcpyAsync(out_min, d_min, nbscans * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (out_max) HIP_TRY(h, hipMemcpyAsync(out_max, d_max, nbscans * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  }
-  if (mem == FDOCT_MEM_HOST || out_mem == FDOCT_MEM_HOST) HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return FDOCT_OK;
+  StagePlan sp;
+  const int in = sp.in(bscandb, mem, image_bytes(nbscans, depths, ascans));
+  const int lo = sp.out_or_scratch(out_min, out_mem, nbscans * sizeof(float)), hi = sp.out_or_scratch(out_max, out_mem, nbscans * sizeof(float));
+  if (int rc = stage_begin(h, &sp)) return rc;
+  const RoiImage im = image_of(sp, in, layout, nbscans, depths, ascans);
+  HIP_TRY(h, launch_roi_ascan_minmax(im, ascanat, sp.dev<float>(lo), sp.dev<float>(hi), h->num_cu, h->stream));  // (writes both: a missing one is scratch)
+  return stage_finish(h, sp);
 } FDOCT_CATCH(h)
 
 int fdoct_roi_mean(fdoct_handle h, const float* bscandb, fdoct_memspace mem, fdoct_layout layout, int nbscans, int depths,
@@ -119,18 +98,11 @@ int fdoct_roi_mean(fdoct_handle h, const float* bscandb, fdoct_memspace mem, fdo
     return fail(h, FDOCT_ERR_INVALID, "fdoct_roi_mean: needs ascanat + width < ascans (BscanFFT.cpp:107)");
   if (vertpos < 0 || (long long)vertpos + 3 > depths) return fail(h, FDOCT_ERR_INVALID, "fdoct_roi_mean: the 3 depth rows do not fit");
   DEVICE_SCOPE(h);
-  RoiImage im;
-  if (int rc = stage_image(h, bscandb, mem, layout, nbscans, depths, ascans, &im)) return rc;
-  double* d_out = out_mean;
-  if (out_mem == FDOCT_MEM_HOST) {
-    if (int rc = h->ws_roi_out.reserve(h, (size_t)nbscans * sizeof(double))) return rc;
-    d_out = h->ws_roi_out;
-  }
-  HIP_TRY(h, launch_roi_mean(im, ascanat, vertpos, width, d_out, h->num_cu, h->stream));
-  if (out_mem == FDOCT_MEM_HOST)
-    HIP_TRY(h, hipMemcpyAsync(out_mean, d_out, nbscans * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (mem == FDOCT_MEM_HOST || out_mem == FDOCT_MEM_HOST) HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return FDOCT_OK;
+  StagePlan sp;
+  const int in = sp.in(bscandb, mem, image_bytes(nbscans, depths, ascans)), out = sp.out(out_mean, out_mem, nbscans * sizeof(double));
+  if (int rc = stage_begin(h, &sp)) return rc;
+  HIP_TRY(h, launch_roi_mean(image_of(sp, in, layout, nbscans, depths, ascans), ascanat, vertpos, width, sp.dev<double>(out), h->num_cu, h->stream));
+  return stage_finish(h, sp);
 } FDOCT_CATCH(h)
 
 int fdoct_set_peakhold_roi(fdoct_handle h, int x, int y, int w, int hgt, int ascanat) try {
@@ -158,14 +130,14 @@ int fdoct_peakhold(fdoct_handle h, int slot, const float* bscandb, fdoct_memspac
   if ((long long)r.x + r.w > ascans || (long long)r.y + r.h > depths || r.ascanat >= ascans)
     return fail(h, FDOCT_ERR_INVALID, "fdoct_peakhold: the ROI or ascanat lies outside the image");
   DEVICE_SCOPE(h);
-  RoiImage im;
-  if (int rc = stage_image(h, bscandb, mem, layout, nbscans, depths, ascans, &im)) return rc;
+  StagePlan sp;
+  const int in = sp.in(bscandb, mem, image_bytes(nbscans, depths, ascans));
+  if (int rc = stage_begin(h, &sp)) return rc;
   uint32_t* cols = static_cast<uint32_t*>(h->d_hold_cols) + (size_t)(slot - 1) * r.w;
   uint32_t* scalar = static_cast<uint32_t*>(h->d_hold_scalar) + (slot - 1);
-  HIP_TRY(h, launch_roi_hold(im, r.x, r.y, r.w, r.h, r.ascanat, cols, scalar, h->num_cu, h->stream));
+  HIP_TRY(h, launch_roi_hold(image_of(sp, in, layout, nbscans, depths, ascans), r.x, r.y, r.w, r.h, r.ascanat, cols, scalar, h->num_cu, h->stream));
   h->hold_count[slot - 1] += nbscans;
-  if (mem == FDOCT_MEM_HOST) HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return FDOCT_OK;
+  return stage_finish(h, sp);
 } FDOCT_CATCH(h)
 
 int fdoct_get_peakhold(fdoct_handle h, int slot, float* colmax, float* ascanmax, long long* held_bscans) try {

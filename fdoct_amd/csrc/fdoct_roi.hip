@@ -214,8 +214,6 @@ __global__ __launch_bounds__(ROI_BLOCK) void roi_mean_kernel(const float* __rest
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-int resident_blocks(int num_cu) { return (num_cu > 0 ? num_cu : 256) * (ROI_WAVES_PER_CU / (ROI_BLOCK / 64)); }
-
 }  // namespace
 
 hipError_t launch_roi_hold(const RoiImage& im, int x, int y, int w, int h, int ascanat, uint32_t* cols, uint32_t* scalar,
@@ -239,12 +237,12 @@ hipError_t launch_roi_hold(const RoiImage& im, int x, int y, int w, int h, int a
     lane_work = (long long)im.nb * (a.vec ? ((y + h + 3) >> 2) - (y >> 2) : h) / 64;
   }
   const int per_slice = a.nchunks + a.nruns;
-  const long long waves = (long long)resident_blocks(num_cu) * (ROI_BLOCK / 64);
+  const long long waves = (long long)resident_blocks(num_cu, ROI_WAVES_PER_CU, ROI_BLOCK) * (ROI_BLOCK / 64);
   long long slices = std::max(1LL, waves / per_slice);
   slices = std::min(slices, std::max(1LL, lane_work / kMinLaneLoads));
   a.slices = (int)slices;
   const long long items = (long long)per_slice * slices;
-  const int blocks = (int)std::min<long long>((items + 3) / 4, resident_blocks(num_cu));
+  const int blocks = (int)std::min<long long>((items + 3) / 4, resident_blocks(num_cu, ROI_WAVES_PER_CU, ROI_BLOCK));
   hipLaunchKernelGGL(roi_hold_kernel, dim3(blocks), dim3(ROI_BLOCK), 0, st, a);
   return hipGetLastError();
 }
@@ -252,7 +250,7 @@ hipError_t launch_roi_hold(const RoiImage& im, int x, int y, int w, int h, int a
 hipError_t launch_roi_ascan_minmax(const RoiImage& im, int ascanat, float* out_min, float* out_max, int num_cu, hipStream_t st) {
   const long long bs = (long long)im.depths * im.ascans;
   const int vec = !im.transposed && im.depths % 4 == 0 && aligned16(im.db);
-  const int blocks = std::min((im.nb + 3) / 4, resident_blocks(num_cu));
+  const int blocks = std::min((im.nb + 3) / 4, resident_blocks(num_cu, ROI_WAVES_PER_CU, ROI_BLOCK));
   hipLaunchKernelGGL(roi_minmax_kernel, dim3(blocks), dim3(ROI_BLOCK), 0, st, im.db, bs, im.nb, im.depths, im.ascans,
                      im.transposed, ascanat, vec, out_min, out_max);
   return hipGetLastError();
@@ -260,7 +258,7 @@ hipError_t launch_roi_ascan_minmax(const RoiImage& im, int ascanat, float* out_m
 
 hipError_t launch_roi_mean(const RoiImage& im, int ascanat, int vertpos, int width, double* out, int num_cu, hipStream_t st) {
   const long long bs = (long long)im.depths * im.ascans;
-  const int blocks = std::min(im.nb, resident_blocks(num_cu));
+  const int blocks = std::min(im.nb, resident_blocks(num_cu, ROI_WAVES_PER_CU, ROI_BLOCK));
   hipLaunchKernelGGL(roi_mean_kernel, dim3(blocks), dim3(ROI_BLOCK), 0, st, im.db, bs, im.nb, im.depths, im.ascans,
                      im.transposed, ascanat, vertpos, width, out);
   return hipGetLastError();

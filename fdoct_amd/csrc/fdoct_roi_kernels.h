@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include "fdoct_grid.h"
 
 namespace fdoct {
 

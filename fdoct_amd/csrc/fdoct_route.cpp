@@ -17,10 +17,10 @@ int kernel_dtype(int dt) {
 }
 
 // rows of the front end's workspaces: packed, 16-byte-pitched
-static size_t frontend_pitch(int w, size_t es) { return ((size_t)w * es + 15) & ~(size_t)15; }
+static size_t frontend_pitch(int w, size_t es) { return packed_pitch((size_t)w * es); }
 
 // medianBlur + INTER_AREA binning of device-resident raw frames into a packed, 16-byte-pitched buffer.
-// Returns the binned frames in *out / *out_pitch (library workspace).
+// Returns the binned frames in *out / *out_pitch (library workspace).  d_raw null: the checks and the workspaces only.
 int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_w, int raw_h, size_t raw_pitch, int mediann,
                  int binx, int biny, void** out, size_t* out_pitch) {
   if (kdt != FDOCT_K_U8 && kdt != FDOCT_K_U16) return fail(h, FDOCT_ERR_UNSUPPORTED, "the front end takes 8- or 16-bit camera frames");
@@ -33,16 +33,17 @@ int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_
   hipStream_t st = h->stream;
   const void* src = d_raw;
   size_t src_pitch = raw_pitch;
+  const size_t mp = frontend_pitch(raw_w, es);
+  const int ow = raw_w / binx, oh = raw_h / biny;
+  const size_t op = frontend_pitch(ow, es);
+  if (mediann > 0 && (rc = h->ws_med.reserve(h, mp * (size_t)raw_h * nframes))) return rc;
+  if ((rc = h->ws_front.reserve(h, op * (size_t)oh * nframes))) return rc;
+  if (!d_raw) return FDOCT_OK;
   if (mediann > 0) {
-    const size_t mp = frontend_pitch(raw_w, es);
-    if ((rc = h->ws_med.reserve(h, mp * (size_t)raw_h * nframes))) return rc;
     HIP_TRY(h, launch_median(src, (long long)src_pitch, h->ws_med, (long long)mp, kdt, raw_w, raw_h, mediann, nframes, st));
     src = h->ws_med;
     src_pitch = mp;
   }
-  const int ow = raw_w / binx, oh = raw_h / biny;
-  const size_t op = frontend_pitch(ow, es);
-  if ((rc = h->ws_front.reserve(h, op * (size_t)oh * nframes))) return rc;
   HIP_TRY(h, launch_bin(src, (long long)src_pitch, h->ws_front, (long long)op, kdt, ow, oh, binx, biny, nframes, st));
   *out = h->ws_front;
   *out_pitch = op;
@@ -62,11 +63,11 @@ int colour_check(fdoct_ctx* h, const char* who, int channelnum, fdoct_dtype dtyp
 
 // webcam:1015-1038 and the block behind it.  Sum: one kernel, the binning in it.  Select without a median: likewise, into the
 // front end's output buffer.  Select with a median: the full-resolution channel goes to ws_col and from there through the mono
-// front end as it is (launch_median, launch_bin).
+// front end as it is (launch_median, launch_bin).  d_bgr null: the checks and the workspaces only, like run_frontend.
 int run_colour(fdoct_ctx* h, const void* d_bgr, int nframes, int raw_w, int raw_h, size_t pitch, int channelnum, int mediann, int binx,
                int biny, void** out, size_t* out_pitch) {
   if (int rc = colour_check(h, "colour stage", channelnum, FDOCT_U8, mediann)) return rc;
-  if (!d_bgr || nframes < 1 || raw_w < 1 || raw_h < 1) return fail(h, FDOCT_ERR_INVALID, "colour stage: no frames");
+  if (nframes < 1 || raw_w < 1 || raw_h < 1) return fail(h, FDOCT_ERR_INVALID, "colour stage: no frames");
   if (binx < 1 || biny < 1 || raw_w % binx || raw_h % biny) return fail(h, FDOCT_ERR_INVALID, "frame size must be a multiple of the bin factors");
   if (pitch < 3 * (size_t)raw_w) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a row of B,G,R pixels");
   const bool via_median = mediann > 0;
@@ -89,6 +90,8 @@ int run_colour(fdoct_ctx* h, const void* d_bgr, int nframes, int raw_w, int raw_
     if ((rc = ws.reserve(h, bytes))) return rc;
     a.out = ws;
   }
+  if (via_median && (rc = run_frontend(h, nullptr, FDOCT_K_U8, nframes, raw_w, raw_h, 0, mediann, binx, biny, nullptr, nullptr))) return rc;
+  if (!d_bgr) return FDOCT_OK;
   HIP_TRY(h, launch_colour(a, h->stream));
   if (via_median) return run_frontend(h, a.out, FDOCT_K_U8, nframes, raw_w, raw_h, (size_t)a.out_pitch, mediann, binx, biny, out, out_pitch);
   *out = a.out;

@@ -164,6 +164,27 @@ def test_plan_decisions_match_the_recorded_table(tmp_path):
     assert not diff, "%d decisions differ, first: %s" % (len(diff), diff[0])
 
 
+def test_staging_plan_places_host_memory_arguments(tmp_path):
+    """The staging plan of the side entry points (fdoct_amd/csrc/fdoct_stage.h) is a value without HIP in it:
+    tests/native/stage_check.cpp, built with plain g++ like the two tables above, checks over the plan type alone that every
+    staged item starts at a multiple of 256 bytes, that items do not overlap and the totals cover the last one, that device
+    items keep the caller's pointer and pitch and add nothing to the totals, that an absent output becomes scratch exactly
+    when the kernel writes it anyway, that the in-place pair is one device range, that the 2-D form packs rows to
+    (row + 15) & ~15, that the call synchronises exactly when an item is in host memory, and that sizes which would wrap
+    size_t are FDOCT_ERR_INVALID."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++")
+    if not cxx:
+        pytest.skip("no g++")
+    exe = tmp_path / "stage_check"
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "fdoct_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "native", "stage_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout[-2000:] + out.stderr[-2000:]
+
+
 def test_every_entry_point_catches_at_the_boundary():
     """Each extern "C" definition in fdoct_capi.cpp is a function-try-block that ends in the boundary's catch macro
     (FDOCT_CATCH and its variants), and those definitions are exactly the exported ABI."""
