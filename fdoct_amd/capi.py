@@ -103,6 +103,11 @@ LOWPASS_ABI_SYMBOLS = ["fdoct_set_capture_options", "fdoct_get_capture_options",
 BSCANBIN_ABI_SYMBOLS = ["fdoct_bscanbin_size", "fdoct_bscanbin_taps", "fdoct_bscan_bin"]
 # every symbol include/fdoct_colour.h declares: the webcam's interleaved B,G,R frames (channelnum), likewise on their own
 COLOUR_ABI_SYMBOLS = ["fdoct_set_colour_input", "fdoct_get_colour_input", "fdoct_colour_extract", "fdoct_colour_sum_scale"]
+# every symbol include/fdoct_manualavg.h declares: manual averaging of B-scans (manualaveraging / manualaverages), likewise on its own
+MANUALAVG_ABI_SYMBOLS = ["fdoct_manualavg_plan", "fdoct_manualavg_begin", "fdoct_manualavg_add", "fdoct_manualavg_state",
+                         "fdoct_manualavg_end"]
+# fdoct_manualavg_mode (include/fdoct_manualavg.h)
+MANUALAVG_REFERENCE, MANUALAVG_KEEP_ALL = 0, 1
 # fdoct_ref_role (include/fdoct_capture.h)
 REF_BACKGROUND, REF_PI, REF_DARK, REF_NONE = range(4)
 
@@ -236,6 +241,14 @@ def load_library():
                                          C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.fdoct_colour_sum_scale.argtypes = []
     lib.fdoct_colour_sum_scale.restype = C.c_double
+    # include/fdoct_manualavg.h
+    lib.fdoct_manualavg_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.fdoct_manualavg_begin.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_int]
+    lib.fdoct_manualavg_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.POINTER(C.c_int)]
+    lib.fdoct_manualavg_state.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int), C.c_void_p]
+    lib.fdoct_manualavg_end.argtypes = [C.c_void_p]
     _lib = lib
     return lib
 
@@ -334,6 +347,15 @@ def bscanbin_taps(up):
     if rc:
         raise FdoctError(rc, "fdoct_bscanbin_taps: up must be 1..64")
     return taps, off
+
+
+def manualavg_plan(manualaverages, mode, accumulated, nbscans):
+    """fdoct_manualavg_plan: (emitted, accumulated afterwards) for nbscans more images.  Needs no GPU."""
+    e, a = C.c_int(), C.c_int()
+    rc = load_library().fdoct_manualavg_plan(manualaverages, mode, accumulated, nbscans, C.byref(e), C.byref(a))
+    if rc:
+        raise FdoctError(rc, "fdoct_manualavg_plan: manualaverages < 1, a bad mode, accumulated outside 0..manualaverages or nbscans < 0")
+    return e.value, a.value
 
 
 def _frame_batch(frames):
@@ -775,6 +797,55 @@ class Reconstructor:
                                              binx if upx is None else upx, biny if upy is None else upy,
                                              float(binx * biny) if multiplyfactor is None else float(multiplyfactor),
                                              d_out_bscan_ptr, d_out_db_ptr, MEM_DEVICE))
+
+    # -- manual averaging of B-scans (include/fdoct_manualavg.h): an accumulator of doubles on the device, with state across calls
+    def manualavg_begin(self, manualaverages, count, mode=MANUALAVG_REFERENCE):
+        """manualaccum = zeros, manualaccumcount = 0 (BscanFFT.cpp:933, 567) for images of `count` floats (depths * ascans).
+        MANUALAVG_REFERENCE drops the image that arrives when manualaverages are in, as the reference does; MANUALAVG_KEEP_ALL
+        emits with the last of them."""
+        self._check(self.lib.fdoct_manualavg_begin(self.h, int(manualaverages), int(count), int(mode)))
+
+    def manualavg_state(self, partial=False):
+        """(manualaverages, count, mode, accumulated) and, with partial=True, the running sums as float64[count] as well."""
+        m, n, mode, acc = C.c_int(), C.c_size_t(), C.c_int(), C.c_int()
+        self._check(self.lib.fdoct_manualavg_state(self.h, C.byref(m), C.byref(n), C.byref(mode), C.byref(acc), None))
+        if not partial:
+            return m.value, n.value, mode.value, acc.value
+        sums = np.empty(n.value, np.float64)
+        self._check(self.lib.fdoct_manualavg_state(self.h, None, None, None, None, sums.ctypes.data))
+        return m.value, n.value, mode.value, acc.value, sums
+
+    def manualavg_add(self, bscans, want_mean=True, want_db=True):
+        """BscanFFT.cpp:1399-1444 for host B-scans, in order: float32 (nbscans, ...) images of the accumulator's size, or one
+        such image.  Returns (mean, db) float32, each (emitted,) + the image's shape (None when not requested): mean is
+        manualaccum / manualaverages, db is 20 ln(that) / 2.303."""
+        a = np.ascontiguousarray(bscans, np.float32)
+        m, count, mode, acc = self.manualavg_state()
+        if a.size == count and (a.ndim < 2 or a.shape[0] != 1):
+            a = a[None]
+        n, shape = a.shape[0], a.shape[1:]
+        if a.ndim < 2 or n < 1 or a.size != n * count:
+            raise FdoctError(-1, "manualavg_add takes images of the accumulator's %d floats" % count)
+        e = manualavg_plan(m, mode, acc, n)[0]
+        mean = np.empty((e,) + shape, np.float32) if want_mean else None
+        db = np.empty((e,) + shape, np.float32) if want_db else None
+        got = C.c_int()
+        self._check(self.lib.fdoct_manualavg_add(self.h, a.ctypes.data, MEM_HOST, n, mean.ctypes.data if want_mean and e else None,
+                                                 db.ctypes.data if want_db and e else None, MEM_HOST, e, C.byref(got)))
+        assert got.value == e
+        return mean, db
+
+    def manualavg_add_device(self, d_bscans_ptr, nbscans, d_mean_ptr, d_db_ptr, out_capacity):
+        """... on device-resident B-scans (raw device addresses; either output may be None, both only on a call that emits
+        nothing).  Enqueues on the handle's stream; returns the number of slots the call writes."""
+        got = C.c_int()
+        self._check(self.lib.fdoct_manualavg_add(self.h, d_bscans_ptr, MEM_DEVICE, int(nbscans), d_mean_ptr, d_db_ptr, MEM_DEVICE,
+                                                 int(out_capacity), C.byref(got)))
+        return got.value
+
+    def manualavg_end(self):
+        """Frees the accumulator (close() does so too)."""
+        self._check(self.lib.fdoct_manualavg_end(self.h))
 
     # -- work
     def _out_shape(self, nframes, layout):

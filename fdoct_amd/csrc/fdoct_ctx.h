@@ -9,6 +9,7 @@
 //   fdoct_lowpass.cpp those of include/fdoct_lowpass.h (BscanDark's lpfilter, the capture's options)
 //   fdoct_bscanbin.cpp those of include/fdoct_bscanbin.h (spinjnt's output binning between the linear B-scan and its dB)
 //   fdoct_colour.cpp  those of include/fdoct_colour.h (the webcam's interleaved B,G,R frames: channelnum)
+//   fdoct_manualavg.cpp those of include/fdoct_manualavg.h (manual averaging of B-scans: manualaccum and its counter)
 //   fdoct_stage.h     the staging plan of those side entry points' host-memory arguments (stage_reserve / stage_upload / stage_finish, below, commit it)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
@@ -219,6 +220,11 @@ struct fdoct_ctx {
   int colour = -1;
   DevBuf<unsigned char> ws_col;    // the full-resolution channel on its way to the median (run_colour)
   DevBuf<double> ws_col_sum;       // the (binned) sum frames
+  // manual averaging (fdoct_manualavg.cpp): measurement state like the peak holds, so neither fdoct_export_state nor
+  // fdoct_clone_to_device carries it
+  DevBuf<double> d_mavg;           // manualaccum (BscanFFT.cpp:933): mavg_count running sums
+  size_t mavg_count = 0;
+  int mavg_m = 0, mavg_mode = 0, mavg_accumulated = 0;  // manualaverages (0: no accumulator), fdoct_manualavg_mode, manualaccumcount
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;

@@ -11,7 +11,7 @@
 //                [--rowwisenormalize 0|1] [--donotnormalize 0|1] [--repeat K] [--threshold dB] --out prefix
 //                [--gpus N [--devices d0,d1,...]] [--precise-division | --one-word-division]
 //                [--roi-mean ascanat,vertpos,width] [--capture-background N [--capture-lowpass] [--capture-raw]] [--max-intensity]
-//                [--bscan-bin BX,BY[,BINVALUEX,BINVALUEY]] [--channel N]
+//                [--bscan-bin BX,BY[,BINVALUEX,BINVALUEY]] [--channel N] [--manual-averages M [--manual-keep-all]]
 //
 // --gpus N: one process, N handles (fdoct_clone_to_device), one host thread per handle; the frames are sharded with
 // fdoct_shard_frames (contiguous ranges, averaging groups never split -- the rule of the multi-process path,
@@ -34,6 +34,11 @@
 // interleaved B,G,R frames -- a 3-channel .ocv dump, or raw H x W x 3 bytes -- and the GPU takes channel N (0, 1, 2 = B, G, R) or
 // the scaled sum (3) of every frame (include/fdoct_colour.h) ahead of the capture, the chain and the max-intensity line.  A
 // --background file stays a mono frame or spectrum of --bits samples.
+// --manual-averages M: the ini's manualaveraging with manualaverages = M (BscanFFT.cpp:1399-1444) over the output B-scans, in order,
+// on the GPU (include/fdoct_manualavg.h): every M + 1 B-scans give one averaged image -- the B-scan that arrives when M are in is
+// dropped, as in the reference; with --manual-keep-all every M give one and nothing is dropped.  The emitted images are written
+// as <prefix>_bscanman.f32 (manualaccum / M, what 1440 saves before its log) and <prefix>_bscanman_db.f32 (20 ln / 2.303), D x H
+// each; B-scans left in the accumulator at the end are reported and not written.
 // --max-intensity: the status line's "Max intensity = <floor(max)>" (BscanFFT.cpp:1105-1108) for every reconstructed frame.
 // --frames holds one or more H x W frames back to back (u8 for --bits 8, little-endian u16 for --bits 16).
 // Outputs: <prefix>_bscan.f32 / <prefix>_bscandb.f32 (reference layout D x H per B-scan, main:1220) and
@@ -56,6 +61,7 @@
 #include "../include/fdoct_capture.h"
 #include "../include/fdoct_colour.h"
 #include "../include/fdoct_lowpass.h"
+#include "../include/fdoct_manualavg.h"
 #include "../include/fdoct_roi.h"
 #include "ocv_io.h"
 
@@ -93,6 +99,8 @@ int main(int argc, char** argv) {
   bool max_intensity = false;      // --max-intensity
   int bbin[4] = {0, 0, 1, 1};      // --bscan-bin bscanbinx,bscanbiny[,binvaluex,binvaluey] (0: off)
   int channel = -1;                // --channel channelnum (-1: mono frames)
+  int manual_averages = -1;        // --manual-averages manualaverages (-1: manualaveraging off)
+  int manual_mode = FDOCT_MANUALAVG_REFERENCE;  // --manual-keep-all
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -139,6 +147,14 @@ int main(int argc, char** argv) {
     else if (a == "--capture-raw") capture_raw = 1;
     else if (a == "--max-intensity") max_intensity = true;
     else if (a == "--channel") channel = std::atoi(next());
+    else if (a == "--manual-averages") {
+      manual_averages = std::atoi(next());
+      if (manual_averages < 1) {
+        std::fprintf(stderr, "--manual-averages wants a count of at least 1\n");
+        return 1;
+      }
+    }
+    else if (a == "--manual-keep-all") manual_mode = FDOCT_MANUALAVG_KEEP_ALL;
     else if (a == "--devices") {
       for (const char* p = next(); *p;) {
         devices.push_back(std::atoi(p));
@@ -320,6 +336,28 @@ int main(int argc, char** argv) {
     }
     bscan.swap(lin);
     bscandb.swap(db);
+  }
+
+  if (manual_averages > 0) {
+    // manualaveraging (main:1399-1444) over the B-scans as the loop would hand them over, one call for all of them
+    const size_t px = (size_t)OD * OH;
+    int emitted = 0, left = 0;
+    rc = fdoct_manualavg_plan(manual_averages, manual_mode, 0, G, &emitted, &left);
+    std::vector<float> man((size_t)emitted * px), mandb(man.size());
+    if (!rc) rc = fdoct_manualavg_begin(h, manual_averages, px, manual_mode);
+    if (!rc)
+      rc = fdoct_manualavg_add(h, bscan.data(), FDOCT_MEM_HOST, G, emitted ? man.data() : nullptr, emitted ? mandb.data() : nullptr,
+                               FDOCT_MEM_HOST, emitted, nullptr);
+    if (!rc) rc = fdoct_manualavg_end(h);
+    if (rc) {
+      std::fprintf(stderr, "fdoct_manualavg: %d %s\n", rc, fdoct_last_error(h));
+      return 1;
+    }
+    std::ofstream f(out + "_bscanman.f32", std::ios::binary);
+    f.write(reinterpret_cast<const char*>(man.data()), (std::streamsize)(man.size() * sizeof(float)));
+    std::ofstream g(out + "_bscanman_db.f32", std::ios::binary);
+    g.write(reinterpret_cast<const char*>(mandb.data()), (std::streamsize)(mandb.size() * sizeof(float)));
+    std::printf("manual averaging of %d: %d image(s) written, %d B-scan(s) left in the accumulator\n", manual_averages, emitted, left);
   }
 
   {
