@@ -212,31 +212,37 @@ int fdoct_get_window(fdoct_handle h, double* win, int n) try {
   return FDOCT_OK;
 } FDOCT_CATCH(h)
 
-// The sim variant with averages = S > 1 (sim:936-947): of every S frames the reference keeps the LAST one's magnitudes (copyTo,
-// no accumulate, no division).  Gathers those frames -- frame g S + S - 1 for every group g -- into a packed device buffer
-// with the caller's row pitch (one strided copy on the handle's stream, from host or device memory) and re-points the call
-// at it: nframes becomes the number of groups, the frames device-resident.  (The frame on which the reference EMITS, the
-// (S + 1)-th of its loop, is computed and dropped there, sim:944-947: it never reaches an output, so it is the caller's to
-// skip.)  A no-op for S = 1 and for the main variant.  Host batches worth chunking do not come here: fdoct_process hands the
-// pipeline a frame stride instead (no batch-sized buffer).
-static int sim_last_frames(fdoct_ctx* h, const void** frames, fdoct_memspace* space, fdoct_dtype dtype, int* nframes, size_t pitch_bytes) {
-  const int S = h->sim_group;
-  if (S <= 1) return FDOCT_OK;
-  if (!*frames || *nframes <= 0) return fail(h, FDOCT_ERR_INVALID, "no frames");
-  if (*nframes % S) return fail(h, FDOCT_ERR_INVALID, "nframes must be a multiple of averages");
-  const size_t es = frame_pixel_bytes(h, dtype);  // (a colour handle's frames: rows of B,G,R pixels)
-  if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
-  const size_t pitch = pitch_bytes ? pitch_bytes : es * (size_t)h->W * h->fe_binx;
-  const size_t frame_bytes = pitch * (size_t)h->H * h->fe_biny;  // raw camera rows when a front end is set
-  const int G = *nframes / S;
+// The call as fdoct_hostcall.h sees it: the handle's geometry, the arguments, and -- for host memory on both sides, the only calls
+// whose buffers the pipeline may take as they are -- whether each buffer is pinned.  FDOCT_HOST_CHUNK_MB is read per call.
+static HostCall host_call(const fdoct_ctx* h, const void* frames, fdoct_dtype dtype, fdoct_memspace space, int nframes, size_t pitch_bytes,
+                          const float* out_bscan, const float* out_db, fdoct_memspace out_space) {
+  HostCallInputs in;
+  in.W = h->W, in.H = h->H, in.D = h->D, in.A = h->A, in.sim_group = h->sim_group, in.fe_binx = h->fe_binx, in.fe_biny = h->fe_biny;
+  in.pixel_bytes = frame_pixel_bytes(h, dtype);  // a colour handle's rows hold 3 bytes per pixel: chunks, strides and staging follow
+  in.pitch_bytes = pitch_bytes, in.frames = frames != nullptr, in.nframes = nframes, in.space = space, in.out_space = out_space;
+  in.want_bscan = out_bscan != nullptr, in.want_db = out_db != nullptr;
+  if (frames && space == FDOCT_MEM_HOST && out_space == FDOCT_MEM_HOST) {
+    in.frames_pinned = host_pointer_is_pinned(frames);
+    in.bscan_pinned = !out_bscan || host_pointer_is_pinned(out_bscan);
+    in.db_pinned = !out_db || host_pointer_is_pinned(out_db);
+  }
+  if (const char* e = std::getenv("FDOCT_HOST_CHUNK_MB")) in.chunk_mb = std::atoll(e);  // tuning aid (tools/pcie_chunk.py)
+  return make_host_call(in);
+}
+
+// SimFrames::Gather (fdoct_hostcall.h) carried out: one strided copy on the handle's stream, from host or device memory, packs the
+// last frame of every group into ws_sim with the caller's row pitch and re-points the call at it, device-resident.  (The frame on
+// which the reference EMITS, the (S + 1)-th of its loop, is computed and dropped there, sim:944-947: it never reaches an output,
+// so it is the caller's to skip.)
+static int sim_last_frames(fdoct_ctx* h, const HostCall& call, const void** frames, fdoct_memspace* space) {
+  if (call.sim != SimFrames::Gather) return FDOCT_OK;
+  const size_t frame_bytes = call.pitch * (size_t)call.rows_per_frame;  // raw camera rows when a front end is set
   DEVICE_SCOPE(h);
-  int rc;
-  if ((rc = h->ws_sim.reserve(h, frame_bytes * (size_t)G))) return rc;
-  HIP_TRY(h, hipMemcpy2DAsync(h->ws_sim, frame_bytes, static_cast<const unsigned char*>(*frames) + (size_t)(S - 1) * frame_bytes, (size_t)S * frame_bytes,
-                              frame_bytes, (size_t)G, *space == FDOCT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+  if (int rc = h->ws_sim.reserve(h, frame_bytes * (size_t)call.nframes)) return rc;
+  HIP_TRY(h, hipMemcpy2DAsync(h->ws_sim, frame_bytes, static_cast<const unsigned char*>(*frames) + call.first_byte, call.frame_stride, frame_bytes,
+                              (size_t)call.nframes, *space == FDOCT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
   *frames = h->ws_sim;
   *space = FDOCT_MEM_DEVICE;
-  *nframes = G;
   return FDOCT_OK;
 }
 
@@ -244,11 +250,14 @@ int fdoct_process_async(fdoct_handle h, const void* d_frames, fdoct_dtype dtype,
                         float* d_out_bscan, float* d_out_db, fdoct_layout layout) try {
   if (!h) return FDOCT_ERR_INVALID;
   fdoct_memspace space = FDOCT_MEM_DEVICE;
-  if (h->colour >= 0)  // refused before the gather below enqueues anything
+  if (h->colour >= 0)
     if (int rc = colour_check(h, "colour input", h->colour, dtype, h->fe_median)) return rc;
-  if (int rc = sim_last_frames(h, &d_frames, &space, dtype, &nframes, pitch_bytes)) return rc;
+  const HostCall call = host_call(h, d_frames, dtype, space, nframes, pitch_bytes, d_out_bscan, d_out_db, FDOCT_MEM_DEVICE);
+  if (call.rc) return fail(h, call.rc, call.why);
+  if (int rc = check_call(h, dtype, pitch_bytes, d_out_bscan, d_out_db)) return rc;
+  if (int rc = sim_last_frames(h, call, &d_frames, &space)) return rc;
   h->record_now = h->async_timing;
-  return enqueue(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
+  return enqueue(h, d_frames, dtype, call.nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
 } FDOCT_CATCH(h)
 
 int fdoct_set_timing(fdoct_handle h, int on) try {
@@ -277,172 +286,6 @@ int fdoct_synchronize(fdoct_handle h) try {
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return check_tro_fault(h);
 } FDOCT_CATCH(h)
-
-// Host buffers in, host buffers out, more than one chunk of work: the batch is cut into chunks of whole averaging
-// groups and pipelined over three streams -- chunk c+1 uploads while chunk c computes and chunk c-1 downloads (the
-// two PCIe directions and the kernels overlap when the caller's buffers are pinned, e.g. from fdoct_host_alloc;
-// pageable buffers still work, the runtime then stages them and the host thread serialises the copies).
-static int process_pipelined_impl(fdoct_ctx* h, const unsigned char* frames, fdoct_dtype dtype, int nframes, size_t src_pitch,
-                                  size_t row_bytes, long long rows_per_frame, float* out_bscan, float* out_db, fdoct_layout layout,
-                                  int frames_per_chunk, size_t frame_stride);
-
-// frame_stride: bytes from one frame of the batch to the next in the caller's memory -- rows_per_frame * src_pitch for a packed
-// batch; the sim variant with averages = S reads every S-th frame (the last of each group), S times that.
-static int process_pipelined(fdoct_ctx* h, const unsigned char* frames, fdoct_dtype dtype, int nframes, size_t src_pitch,
-                             size_t row_bytes, long long rows_per_frame, float* out_bscan, float* out_db, fdoct_layout layout,
-                             int frames_per_chunk, size_t frame_stride) {
-  const int rc = process_pipelined_impl(h, frames, dtype, nframes, src_pitch, row_bytes, rows_per_frame, out_bscan, out_db, layout,
-                                        frames_per_chunk, frame_stride);
-  if (rc != FDOCT_OK) drain(h);
-  return rc;
-}
-
-static bool host_staging_enabled(const fdoct_ctx* h) {
-  bool on = h->host_staging != 0;
-  if (const char* e = std::getenv("FDOCT_HOST_STAGING")) on = on && std::atoi(e) != 0;
-  return on;
-}
-
-// Is this host pointer pinned (hipHostMalloc / hipHostRegister), i.e. can a DMA engine reach it without the runtime's bounce
-// buffer?  Pageable memory is "unregistered" to the runtime (an error from hipPointerGetAttributes on older runtimes).
-static bool host_pointer_is_pinned(const void* p) {
-  hipPointerAttribute_t a;
-  std::memset(&a, 0, sizeof a);
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.type == hipMemoryTypeHost;
-}
-
-// The copy threads of a handle (fdoct_hostcopy.h), started with the first batch that needs them.  An explicit count
-// (fdoct_set_host_staging(h, n) or FDOCT_HOST_COPY_THREADS) is taken as given.  Left to the library: half of the hardware
-// threads this process may use, eight at most, the caller's thread among them -- and NO staging below four, because one or two threads
-// copy more slowly than the runtime's own bounce path (MI355X host, 64 frames of 2048 x 1000 u16 per call, result array
-// reused: 3.2-3.4 / 5.9-6.0 / 8.4-8.7 / 8.4-9.4 M A-scans/s with 1 / 2 / 4 / 8 threads against 6.0-6.4 M from the runtime and 10.5 M from pinned
-// buffers; profiles/r06_pcie_rate.txt).
-static int copy_thread_count(const fdoct_ctx* h) {  // 0: pageable buffers are not staged
-  if (!host_staging_enabled(h)) return 0;
-  int n = h->host_staging > 0 ? h->host_staging : 0;
-  if (!n)
-    if (const char* e = std::getenv("FDOCT_HOST_COPY_THREADS")) n = std::atoi(e);
-  if (n <= 0) {
-    n = std::min(8, (int)std::thread::hardware_concurrency() / 2);
-    if (n < 4) return 0;
-  }
-  return std::min(n, 64);
-}
-
-static fdoct_impl::HostCopyPool* copy_pool(fdoct_ctx* h) {
-  const int n = copy_thread_count(h);
-  if (!n) return nullptr;
-  if (!h->copy_pool) h->copy_pool.reset(new (std::nothrow) fdoct_impl::HostCopyPool(n));
-  return h->copy_pool.get();
-}
-
-static int process_pipelined_impl(fdoct_ctx* h, const unsigned char* frames, fdoct_dtype dtype, int nframes, size_t src_pitch,
-                                  size_t row_bytes, long long rows_per_frame, float* out_bscan, float* out_db, fdoct_layout layout,
-                                  int frames_per_chunk, size_t frame_stride) {
-  int rc;
-  const bool packed_batch = frame_stride == (size_t)rows_per_frame * src_pitch;  // one 2-D copy moves a whole chunk
-  // Pageable buffers go through the handle's pinned slots (fdoct_hostcopy.h); pinned ones are the DMA engines' to read and write.
-  fdoct_impl::HostCopyPool* pool = copy_pool(h);
-  bool stage_in = pool && !host_pointer_is_pinned(frames);
-  bool stage_mag = pool && out_bscan && !host_pointer_is_pinned(out_bscan);
-  bool stage_db = pool && out_db && !host_pointer_is_pinned(out_db);
-  struct Landed {  // a chunk whose downloads go to (or sit in) the pinned slots and still have to reach the caller's buffers
-    size_t o0 = 0, elems = 0;
-    bool live = false;
-  } landed[2];
-  auto hand_over = [&](int b) -> int {
-    if (!landed[b].live) return FDOCT_OK;
-    HIP_TRY(h, hipEventSynchronize(h->pe_out[b]));
-    if (stage_mag) pool->copy(out_bscan + landed[b].o0, h->pin_mag[b], landed[b].elems * 4);
-    if (stage_db) pool->copy(out_db + landed[b].o0, h->pin_db[b], landed[b].elems * 4);
-    landed[b].live = false;
-    return FDOCT_OK;
-  };
-  if (!h->s_in) {
-    HIP_TRY(h, hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking));
-    HIP_TRY(h, hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
-    for (int b = 0; b < 2; b++) {
-      HIP_TRY(h, hipEventCreateWithFlags(&h->pe_in[b], hipEventDisableTiming));
-      HIP_TRY(h, hipEventCreateWithFlags(&h->pe_k[b], hipEventDisableTiming));
-      HIP_TRY(h, hipEventCreateWithFlags(&h->pe_out[b], hipEventDisableTiming));
-    }
-  }
-  const size_t packed = (row_bytes + 15) & ~(size_t)15;
-  const size_t out_per_group = (size_t)h->H * h->D;  // output floats per averaging group: chunks are whole groups (H D / A per input
-                                                     // frame is not an integer in general -- 251 lines, 18 bins, 16 averages)
-  const hipStream_t s_k = h->stream;
-  h->record_now = false;
-  {
-    // The pinned slots, sized for the first (the largest) chunk, before anything is enqueued: a host that will not pin that
-    // much memory (a locked-memory limit) gets the runtime's own bounce copies for that buffer, not an error.
-    const int nf0 = std::min(frames_per_chunk, nframes);
-    const size_t in0 = packed * (size_t)nf0 * (size_t)rows_per_frame, out0 = (size_t)(nf0 / h->A) * out_per_group * 4;
-    const std::string err_before = h->err;
-    for (int b = 0; b < 2; b++) {
-      if (stage_in && h->pin_in[b].reserve(h, in0)) stage_in = false;
-      if (stage_mag && h->pin_mag[b].reserve(h, out0)) stage_mag = false;
-      if (stage_db && h->pin_db[b].reserve(h, out0)) stage_db = false;
-    }
-    h->err = err_before;
-  }
-  uint64_t sum_in = 0, sum_out = 0;  // fdoct_get_timing reports the whole batch, not the last chunk
-  for (int f0 = 0, c = 0; f0 < nframes; f0 += frames_per_chunk, c++) {
-    const int b = c & 1;
-    const int nf = std::min(frames_per_chunk, nframes - f0);
-    const size_t in_rows = (size_t)nf * rows_per_frame;
-    const size_t out_elems = (size_t)(nf / h->A) * out_per_group;
-    if ((rc = h->pl_in[b].reserve(h, packed * in_rows))) return rc;
-    if (out_bscan && (rc = h->pl_mag[b].reserve(h, out_elems * 4))) return rc;
-    if (out_db && (rc = h->pl_db[b].reserve(h, out_elems * 4))) return rc;
-    const unsigned char* src = frames + (size_t)f0 * frame_stride;
-    // a packed batch moves as one 2-D copy of the chunk's rows, a strided one frame by frame
-    const int pieces = packed_batch ? 1 : nf;
-    const size_t piece_rows = packed_batch ? in_rows : (size_t)rows_per_frame;
-    if (stage_in) {
-      if (c >= 2) HIP_TRY(h, hipEventSynchronize(h->pe_in[b]));           // chunk c-2's upload has left this pinned slot
-      for (int q = 0; q < pieces; q++)
-        pool->copy2d(static_cast<unsigned char*>(h->pin_in[b]) + (size_t)q * piece_rows * packed, packed, src + (size_t)q * frame_stride, src_pitch,
-                     row_bytes, piece_rows);
-    }
-    if (c >= 2) HIP_TRY(h, hipStreamWaitEvent(h->s_in, h->pe_k[b], 0));   // chunk c-2 has consumed this input slot
-    if (stage_in) {
-      HIP_TRY(h, hipMemcpyAsync(h->pl_in[b], h->pin_in[b], packed * in_rows, hipMemcpyHostToDevice, h->s_in));
-    } else {
-      for (int q = 0; q < pieces; q++)
-        HIP_TRY(h, hipMemcpy2DAsync(static_cast<unsigned char*>(h->pl_in[b]) + (size_t)q * piece_rows * packed, packed, src + (size_t)q * frame_stride,
-                                    src_pitch, row_bytes, piece_rows, hipMemcpyHostToDevice, h->s_in));
-    }
-    HIP_TRY(h, hipEventRecord(h->pe_in[b], h->s_in));
-    HIP_TRY(h, hipStreamWaitEvent(s_k, h->pe_in[b], 0));
-    if (c >= 2) HIP_TRY(h, hipStreamWaitEvent(s_k, h->pe_out[b], 0));     // chunk c-2 has left this output slot
-    if ((rc = enqueue(h, h->pl_in[b], dtype, nf, packed, out_bscan ? h->pl_mag[b] : nullptr, out_db ? h->pl_db[b] : nullptr, layout)))
-      return rc;
-    sum_in += h->timing.bytes_in;
-    sum_out += h->timing.bytes_out;
-    HIP_TRY(h, hipEventRecord(h->pe_k[b], s_k));
-    HIP_TRY(h, hipStreamWaitEvent(h->s_out, h->pe_k[b], 0));
-    const size_t o0 = (size_t)(f0 / h->A) * out_per_group;
-    // chunk c-2's images leave the pinned slots (while chunk c uploads and computes) before chunk c's download may land there
-    if ((rc = hand_over(b))) return rc;
-    if (out_bscan) HIP_TRY(h, hipMemcpyAsync(stage_mag ? h->pin_mag[b] : out_bscan + o0, h->pl_mag[b], out_elems * 4, hipMemcpyDeviceToHost, h->s_out));
-    if (out_db) HIP_TRY(h, hipMemcpyAsync(stage_db ? h->pin_db[b] : out_db + o0, h->pl_db[b], out_elems * 4, hipMemcpyDeviceToHost, h->s_out));
-    HIP_TRY(h, hipEventRecord(h->pe_out[b], h->s_out));
-    landed[b].o0 = o0;
-    landed[b].elems = out_elems;
-    landed[b].live = stage_mag || stage_db;
-  }
-  HIP_TRY(h, hipStreamSynchronize(h->s_out));
-  HIP_TRY(h, hipStreamSynchronize(s_k));
-  for (int b = 0; b < 2; b++)
-    if ((rc = hand_over(b))) return rc;
-  h->timing.bytes_in = sum_in;
-  h->timing.bytes_out = sum_out;
-  return FDOCT_OK;
-}
 
 int fdoct_get_host_staging(fdoct_handle h) try {
   if (!h) return FDOCT_ERR_INVALID;
@@ -474,90 +317,34 @@ int fdoct_process(fdoct_handle h, const void* frames, fdoct_dtype dtype, fdoct_m
                   fdoct_layout layout) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (!frames || nframes <= 0) return fail(h, FDOCT_ERR_INVALID, "no frames");
-  if (h->colour >= 0)  // refused before an upload is enqueued
+  if (h->colour >= 0)
     if (int rc = colour_check(h, "colour input", h->colour, dtype, h->fe_median)) return rc;
-  const size_t es = frame_pixel_bytes(h, dtype);  // a colour handle's rows hold 3 bytes per pixel: chunks, strides and staging follow
-  if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
-  const size_t row_samples = (size_t)h->W * h->fe_binx;
-  size_t d_pitch = pitch_bytes ? pitch_bytes : es * row_samples;
-  const long long rows_per_frame = (long long)h->H * h->fe_biny;      // raw camera rows when a front end is set
-  size_t frame_stride = (size_t)rows_per_frame * d_pitch;
   DEVICE_SCOPE(h);
-  // Host buffers on both sides: the batch is cut into chunks of whole averaging groups and pipelined (process_pipelined).  Chunk
-  // size and the batch that is worth chunking, from tools/pcie_chunk.py (profiles/r06_pcie_chunk.txt, M A-scans/s on C2's frames;
-  // round 5 had 32 MB chunks and two of them as the threshold).  Pinned buffers: 16 MB chunks for batches of ~100 MB and more,
-  // 8 MB below, two chunks are worth it (15 / 31 / 62 / 125 MB in: 7.3 / 8.6 / 9.5 / 10.1 against 6.3 / 6.6 / 8.3 / 9.6).
-  // Pageable buffers (staged by the copy threads): 16 MB chunks, four of them or the single shot (62 / 125 / 250 MB in:
-  // 6.9-7.1 / 8.3 / 8.5-9.1 against 6.2-6.5 / 6.6-7.4 / 8.5-8.7; 8 MB chunks lose to the single shot at 31 MB).
-  const size_t frame_bytes = es * row_samples * (size_t)rows_per_frame;
-  const int S0 = h->sim_group > 1 ? h->sim_group : 1;
-  const bool both_host = space == FDOCT_MEM_HOST && out_space == FDOCT_MEM_HOST;
-  const bool pageable = both_host && (!host_pointer_is_pinned(frames) || (out_bscan && !host_pointer_is_pinned(out_bscan)) ||
-                                      (out_db && !host_pointer_is_pinned(out_db)));
-  size_t chunk_bytes = pageable || frame_bytes * (size_t)(nframes / S0) >= ((size_t)96 << 20) ? (size_t)16 << 20 : (size_t)8 << 20;
-  if (const char* e = std::getenv("FDOCT_HOST_CHUNK_MB"))  // tuning aid (tools/pcie_chunk.py)
-    if (std::atoll(e) > 0) chunk_bytes = (size_t)std::atoll(e) << 20;
-  long long fpc = (long long)(chunk_bytes / (frame_bytes ? frame_bytes : 1));
-  fpc = std::max<long long>(fpc / h->A, 1) * h->A;
-  const int min_chunks = pageable ? 4 : 2;
-  const int S = h->sim_group;
-  if (S > 1 && space == FDOCT_MEM_HOST && out_space == FDOCT_MEM_HOST && nframes % S == 0 && nframes / S >= min_chunks * fpc) {
-    // sim variant, averages = S, a batch worth pipelining: the chunks read the last frame of every group where it lies
-    // (no batch-sized gather buffer, sim_last_frames' fallback below)
-    frames = static_cast<const unsigned char*>(frames) + (size_t)(S - 1) * frame_stride;
-    frame_stride *= (size_t)S;
-    nframes /= S;
-  } else if (int rc0 = sim_last_frames(h, &frames, &space, dtype, &nframes, pitch_bytes)) {
-    return rc0;
-  }
-  if (nframes % h->A) return fail(h, FDOCT_ERR_INVALID, "nframes must be a multiple of averages");
+  const HostCall call = host_call(h, frames, dtype, space, nframes, pitch_bytes, out_bscan, out_db, out_space);
+  if (call.rc) return fail(h, call.rc, call.why);
+  if (int rc = check_call(h, dtype, pitch_bytes, out_bscan, out_db)) return rc;
+  // ---- nothing has been enqueued up to here: everything that can refuse the call without a route has
   int rc;
-  const long long in_rows = (long long)nframes * rows_per_frame;
-  const size_t out_elems = (size_t)(nframes / h->A) * h->H * h->D;
-  const void* d_frames = frames;
-  if (space == FDOCT_MEM_HOST && out_space == FDOCT_MEM_HOST) {
-    if (nframes >= min_chunks * fpc) {
-      const auto t0 = std::chrono::steady_clock::now();
-      rc = process_pipelined(h, static_cast<const unsigned char*>(frames), dtype, nframes, d_pitch, es * row_samples,
-                             rows_per_frame, out_bscan, out_db, layout, (int)fpc, frame_stride);
-      if (rc) return rc;
-      if ((rc = check_tro_fault(h))) return rc;
-      h->timing_pending = false;  // no per-call device events here: report the wall time of the whole pipeline
-      h->timing.last_process_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      h->timing.last_kernel_ms = h->timing.resample_stage_ms = h->timing.fft_stage_ms = 0.0;
-      h->timing.ascans = (uint64_t)in_rows;
-      h->record_now = true;
-      return FDOCT_OK;
-    }
+  if (call.path == HostPath::Pipelined) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = process_pipelined(h, call, frames, dtype, out_bscan, out_db, layout))) return rc;
+    if ((rc = check_tro_fault(h))) return rc;
+    h->timing_pending = false;  // no per-call device events here: report the wall time of the whole pipeline
+    h->timing.last_process_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->timing.last_kernel_ms = h->timing.resample_stage_ms = h->timing.fft_stage_ms = 0.0;
+    h->timing.ascans = (uint64_t)call.in_rows;
+    h->record_now = true;
+    return FDOCT_OK;
   }
-  if (space == FDOCT_MEM_HOST) {
-    // stage into an aligned, packed device buffer (PCIe-inclusive path)
-    const size_t packed = (es * row_samples + 15) & ~(size_t)15;
-    if ((rc = h->ws_in.reserve(h, packed * (size_t)in_rows))) return rc;
-    HIP_TRY(h, hipMemcpy2DAsync(h->ws_in, packed, frames, d_pitch, es * row_samples, (size_t)in_rows, hipMemcpyHostToDevice,
-                                h->stream));
-    d_frames = h->ws_in;
-    d_pitch = packed;
-  }
-  float* d_mag = out_bscan;
-  float* d_db = out_db;
-  if (out_space == FDOCT_MEM_HOST) {
-    if (out_bscan) {
-      if ((rc = h->ws_out0.reserve(h, out_elems * 4))) return rc;
-      d_mag = h->ws_out0;
-    }
-    if (out_db) {
-      if ((rc = h->ws_out1.reserve(h, out_elems * 4))) return rc;
-      d_db = h->ws_out1;
-    }
-  }
+  if ((rc = sim_last_frames(h, call, &frames, &space))) return rc;
+  StagePlan sp;  // host frames go up packed and aligned, host outputs come down (the PCIe-inclusive path)
+  const int in = sp.in(frames, space, call.row_bytes, (size_t)call.in_rows, call.pitch);
+  const int mag = sp.out(out_bscan, out_space, call.out_elems * 4), db = sp.out(out_db, out_space, call.out_elems * 4);
+  sp.sync = true;  // (device-resident arguments too: this is the synchronous call)
+  if ((rc = stage_begin(h, &sp))) return rc;
   h->record_now = true;
-  if ((rc = enqueue(h, d_frames, dtype, nframes, d_pitch, d_mag, d_db, layout))) return rc;
-  if (out_space == FDOCT_MEM_HOST) {
-    if (out_bscan) HIP_TRY(h, hipMemcpyAsync(out_bscan, d_mag, out_elems * 4, hipMemcpyDeviceToHost, h->stream));
-    if (out_db) HIP_TRY(h, hipMemcpyAsync(out_db, d_db, out_elems * 4, hipMemcpyDeviceToHost, h->stream));
-  }
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if ((rc = enqueue(h, sp.dev<const void>(in), dtype, call.nframes, sp.pitch(in), sp.dev<float>(mag), sp.dev<float>(db), layout))) return rc;
+  if ((rc = stage_finish(h, sp))) return rc;
   return check_tro_fault(h);
 } FDOCT_CATCH(h)
 
@@ -709,7 +496,7 @@ int fdoct_set_averages(fdoct_handle h, int averages) try {
   if (!h) return FDOCT_ERR_INVALID;
   if (averages < 1) return fail(h, FDOCT_ERR_INVALID, "averages must be >= 1");
   if (h->cfg.variant == FDOCT_VARIANT_SIM)
-    h->sim_group = averages;  // (sim_last_frames: the last frame of every group is what the reference emits)
+    h->sim_group = averages;  // (fdoct_hostcall.h: the last frame of every group is what the reference emits)
   else
     h->A = averages;  // a launch parameter only: no table depends on it
   h->cfg.averages = averages;

@@ -4,17 +4,18 @@
 //   fdoct_route.cpp   the dispatch: choose_route (with fdoct_launch.h's launch value), the passes in front of the chain, one launcher
 //                     per kernel family, enqueue
 //   fdoct_capi.cpp    the extern "C" entry points of include/fdoct.h
+//   fdoct_hostcall.h  what fdoct_process* decide on the host before anything is enqueued, as a value (make_host_call)
+//   fdoct_pipeline.cpp fdoct_process's three-stream pipeline for host buffers on both sides, and its copy threads
 //   fdoct_roi.cpp     those of include/fdoct_roi.h (the B-scan readouts)
 //   fdoct_capture.cpp those of include/fdoct_capture.h (reference frames captured from camera frames)
 //   fdoct_lowpass.cpp those of include/fdoct_lowpass.h (BscanDark's lpfilter, the capture's options)
 //   fdoct_bscanbin.cpp those of include/fdoct_bscanbin.h (spinjnt's output binning between the linear B-scan and its dB)
 //   fdoct_colour.cpp  those of include/fdoct_colour.h (the webcam's interleaved B,G,R frames: channelnum)
 //   fdoct_manualavg.cpp those of include/fdoct_manualavg.h (manual averaging of B-scans: manualaccum and its counter)
-//   fdoct_stage.h     the staging plan of those side entry points' host-memory arguments (stage_reserve / stage_upload / stage_finish, below, commit it)
+//   fdoct_stage.h     the staging plan of host-memory arguments: the side entry points', fdoct_process's single shot (stage_reserve / stage_upload / stage_finish, below, commit it)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
 #include <hip/hip_runtime.h>
-
 
 #include <dlfcn.h>
 
@@ -35,6 +36,7 @@
 #include "fdoct_host.h"
 #include "fdoct_kernels.h"
 #include "fdoct_launch.h"
+#include "fdoct_hostcall.h"
 #include "fdoct_stage.h"
 #include "fdoct_wave.h"
 #include "fdoct_jit.h"
@@ -139,7 +141,8 @@ struct fdoct_ctx {
   bool precise_div = true;
   // BscanFFTsim.cpp with averages > 1 (sim:936-947): every frame's magnitudes are COPIED over the last one's (the accumulate
   // is commented out) and what is emitted, undivided, is the last copy -- frame averages - 1 of every group.  The chain then
-  // runs with A = 1 on those frames only (sim_last_frames gathers them); sim_group is the group length the caller counts in.
+  // runs with A = 1 on those frames only (fdoct_hostcall.h: read where they lie, or gathered into ws_sim); sim_group is the group
+  // length the caller counts in.
   int sim_group = 1;
   DevBuf<unsigned char> ws_sim;
   DevBuf<uint32_t> d_gidx;
@@ -168,17 +171,15 @@ struct fdoct_ctx {
   DevBuf<float> ws_big_y;
   DevBuf<float2> ws_big_a, ws_big_b;
   // workspaces
-  DevBuf<unsigned char> ws_in;
   DevBuf<float> ws_f32, ws_f32_lo;   // f64 frames as two f32 planes (launch_f64_split)
   DevBuf<float> ws_mov_lo;           // ... and the moving average of the low plane
-  DevBuf<float> ws_out0, ws_out1, ws_tr;
+  DevBuf<float> ws_tr;
   DevBuf<float2> ws_ylin;
   long long ylin_rows = 0;  // A-scans the last staged run left in ws_ylin (0: none)
   DevBuf<float> ws_mov;
   DevBuf<unsigned char> ws_front, ws_med;
-  DevBuf<unsigned char> stage_in, stage_out;  // host-memory arguments of the side entry points on their way up and down (stage_reserve)
+  DevBuf<unsigned char> stage_in, stage_out;  // host-memory arguments on their way up and down (stage_reserve): fdoct_process's single shot, the side entry points
   int fe_median = 0, fe_binx = 1, fe_biny = 1;
-  // display post-chain
   // host-pointer pipeline (fdoct_process with host buffers): copy-in / kernels / copy-out on three streams
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t pe_in[2] = {nullptr, nullptr}, pe_k[2] = {nullptr, nullptr}, pe_out[2] = {nullptr, nullptr};
@@ -439,8 +440,18 @@ int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_
 float chain_eps(const fdoct_ctx* h);  // the epsilon under the chain's log (sim:949 / main:1222)
 int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
                  uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r);
+// What refuses a call without a route and without its frames: no background, no output, a bad dtype, a pitch below a row.  First in
+// enqueue_one; fdoct_process* make it ahead of their own copies.
+int check_call(fdoct_ctx* h, fdoct_dtype dtype, size_t pitch_bytes, const float* out_bscan, const float* out_db);
 int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes,
             float* d_out_bscan, float* d_out_db, fdoct_layout layout);
+
+// ---- fdoct_pipeline.cpp ---------------------------------------------------------------------------------------------------
+bool host_pointer_is_pinned(const void* p);
+int copy_thread_count(const fdoct_ctx* h);  // 0: pageable buffers are not staged
+// HostPath::Pipelined carried out on `batch`, the caller's frames pointer; synchronous.  Drains the handle if it fails.
+int process_pipelined(fdoct_ctx* h, const HostCall& call, const void* batch, fdoct_dtype dtype, float* out_bscan, float* out_db,
+                      fdoct_layout layout);
 
 // ---- fdoct_lowpass.cpp ----------------------------------------------------------------------------------------------------
 // Enqueues lpfilter (BscanDark.cpp:119-167) on device rows of W doubles (d_in == d_out: in place) and reserves the workspace a

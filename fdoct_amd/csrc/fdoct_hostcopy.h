@@ -1,6 +1,6 @@
 // fdoct_hostcopy.h -- the host side of fdoct_process's chunk pipeline when the caller's buffers are PAGEABLE (what cv::Mat
 // owns: the buffers the patch of INTEGRATION.md 1 hands over).  The HIP runtime stages a pageable copy through its own
-// bounce buffer on the calling thread, one direction at a time, so the three-stream pipeline of fdoct_capi.cpp degenerates
+// bounce buffer on the calling thread, one direction at a time, so the three-stream pipeline of fdoct_pipeline.cpp degenerates
 // to upload -> kernels -> download in sequence (round 5: 1.5e6 A-scans/s against 7.8e6 from pinned memory).  Here the
 // library owns pinned staging slots and a few threads move a chunk between them and the caller's memory while the DMA
 // engines and the kernels work on the neighbouring chunks.  Nothing here touches the device.

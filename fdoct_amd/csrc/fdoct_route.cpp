@@ -980,6 +980,15 @@ static int run_passes_in_front(fdoct_ctx* h, const Route& r, Call& c, const void
   return FDOCT_OK;
 }
 
+int check_call(fdoct_ctx* h, fdoct_dtype dtype, size_t pitch_bytes, const float* out_bscan, const float* out_db) {
+  if (!h->yb.rows) return fail(h, FDOCT_ERR_STATE, "no background set (fdoct_set_background)");
+  if (!out_bscan && !out_db) return fail(h, FDOCT_ERR_INVALID, "no output requested");
+  const size_t es = frame_pixel_bytes(h, dtype);
+  if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
+  if (pitch_bytes && pitch_bytes < es * h->W) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a row");  // (0: packed rows)
+  return FDOCT_OK;
+}
+
 // Enqueue the whole path for device-resident frames.  d_out_* are row-major or
 // transposed per `layout`.
 int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes,
@@ -987,12 +996,9 @@ int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nfram
   if (!h) return FDOCT_ERR_INVALID;
   if (!d_frames || nframes <= 0) return fail(h, FDOCT_ERR_INVALID, "no frames");
   if (nframes % h->A) return fail(h, FDOCT_ERR_INVALID, "nframes must be a multiple of averages");
-  if (!h->yb.rows) return fail(h, FDOCT_ERR_STATE, "no background set (fdoct_set_background)");
-  if (!d_out_bscan && !d_out_db) return fail(h, FDOCT_ERR_INVALID, "no output requested");
+  if (int rc = check_call(h, dtype, pitch_bytes, d_out_bscan, d_out_db)) return rc;
   const size_t es = frame_pixel_bytes(h, dtype);
-  if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
   if (pitch_bytes == 0) pitch_bytes = es * h->W * h->fe_binx;
-  if (pitch_bytes < es * h->W) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a row");
   DEVICE_SCOPE(h);
   int rc;
   Route r;

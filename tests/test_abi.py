@@ -185,6 +185,61 @@ def test_staging_plan_places_host_memory_arguments(tmp_path):
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout[-2000:] + out.stderr[-2000:]
 
 
+def test_host_call_decisions_match_the_recorded_table(tmp_path):
+    """make_host_call (fdoct_amd/csrc/fdoct_hostcall.h) decides what fdoct_process / fdoct_process_async decide on the host before
+    anything is enqueued.  tests/native/hostcall_check.cpp, built with plain g++ against the header alone, prints for its grid --
+    2048 x 1000 u16, 1024 x 40 u16, 160 x 120 u8 behind a 2 x 2 front end, 3-byte colour pixels, a frame larger than a chunk;
+    1 / 2 / 3 / 16 averages; the sim variant's groups of 1 and 3; every combination of memory spaces; all buffers pinned and one
+    pageable, wanted or not; FDOCT_HOST_CHUNK_MB of 0 / 1 / 100000; a padded pitch; nframes at the refusals and on both sides of
+    every count at which the decision changes (the legs are listed in the program, not a full cross product) -- every field of
+    the value, or the refusal and its text, exactly as
+    hostcall_check.expected recorded them.  The order was: the arithmetic moved into the header verbatim from fdoct_process and
+    sim_last_frames, the table printed from that and committed, and only then the function restructured.  The rows below are
+    derived by hand from the code as it stood (a C2 frame is 4 096 000 bytes; 96 MiB is 24.6 of them)."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++")
+    if not cxx:
+        pytest.skip("no g++")
+    native = os.path.join(ROOT, "tests", "native")
+    exe = tmp_path / "hostcall_check"
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "fdoct_amd", "csrc"),
+                        os.path.join(native, "hostcall_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got, want = out.stdout.splitlines(), open(os.path.join(native, "hostcall_check.expected")).read().splitlines()
+    assert len(got) == len(want) and len(want) > 600
+    diff = [(w, g) for w, g in zip(want, got) if w != g]
+    assert not diff, "%d decisions differ, first: %s" % (len(diff), diff[0])
+
+    def row(key):
+        (line,) = [l for l in got if l.startswith(key + ": ")]
+        words = line[len(key) + 2:].split()
+        return words[0], words[1], {k: int(v) for k, v in (x.split("=") for x in words[2:])}
+
+    MB = 1 << 20
+    for key, path, chunk, fpc in [("hand: C2 pinned n=3", "single", 8 * MB, 2), ("hand: C2 pinned n=4", "pipelined", 8 * MB, 2),
+                                  ("hand: C2 pinned n=24", "pipelined", 8 * MB, 2), ("hand: C2 pinned n=25", "pipelined", 16 * MB, 4),
+                                  ("hand: C2 one pageable n=15", "single", 16 * MB, 4), ("hand: C2 one pageable n=16", "pipelined", 16 * MB, 4),
+                                  ("hand: C2 A=3 pinned n=3", "single", 8 * MB, 3), ("hand: C2 A=3 pinned n=30", "pipelined", 16 * MB, 3),
+                                  ("hand: C2 A=3 pageable n=3", "single", 16 * MB, 3), ("hand: C2 A=3 pageable n=30", "pipelined", 16 * MB, 3)]:
+        sim, p, f = row(key)
+        assert (sim, p, f["chunk"], f["fpc"]) == ("asis", path, chunk, fpc), key
+        assert f["pageable"] == ("pageable" in key) and f["stride"] == 4096000 and f["first"] == 0, key
+    for A in (1, 2, 3, 16):  # a frame (32 MiB) above the chunk size: one averaging group per chunk, at both chunk sizes
+        for pin in ("pinned", "frames-pageable"):
+            f = row("hand: frame above the chunk A=%d %s n=48" % (A, pin))[2]
+            assert (f["chunk"], f["fpc"]) == (16 * MB, A)
+    for A in (1, 2):  # (two frames are under 96 MiB)
+        f = row("4096x4096u16 A=%d S=1 mb=0 h>h pinned n=2" % A)[2]
+        assert (f["chunk"], f["fpc"]) == (8 * MB, A)
+    sim, p, f = row("hand: sim host>host n=180")
+    assert (sim, p) == ("strided", "pipelined")
+    assert (f["nframes"], f["fpc"], f["first"], f["stride"], f["chunk"]) == (60, 12, 2 * 81920, 3 * 81920, MB)
+    assert row("hand: sim host>device n=180")[:2] == ("gather", "device")
+
+
 def test_every_entry_point_catches_at_the_boundary():
     """Each extern "C" definition in fdoct_capi.cpp is a function-try-block that ends in the boundary's catch macro
     (FDOCT_CATCH and its variants), and those definitions are exactly the exported ABI."""

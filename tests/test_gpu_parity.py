@@ -101,7 +101,7 @@ def test_set_averages_at_run_time():
 def test_sim_variant_with_averages_emits_the_last_frame_of_each_group(where):
     """BscanFFTsim.cpp with averages = A > 1 (sim:936-947): the accumulate is commented out, every frame's magnitudes are copied
     over the previous one's and what the else branch emits -- undivided, + 1e-6 -- is the LAST copy: frame A - 1 of every group
-    of A.  The library runs the chain on those frames only (one strided gather, fdoct_capi.cpp::sim_last_frames, or a frame
+    of A.  The library runs the chain on those frames only (one strided gather, fdoct_capi.cpp::sim_last_frames as fdoct_hostcall.h decides, or a frame
     stride through the host pipeline for a batch worth chunking); against the
     oracle's orc_process_u16_sim, and bit-equal to the same frames handed over one by one with averages = 1; fdoct_set_averages
     changes the grouping at run time."""

@@ -237,3 +237,67 @@ def test_host_memory_calls_share_the_staging_buffers_and_match_device_memory_cal
     fresh.capture_reference(capi.REF_DARK, _frames(5))
     _same(got, fresh.process(frames), "process after the side calls")
     fresh.close()
+
+
+def test_process_single_shot_stages_through_the_plan_and_refuses_before_it_copies():
+    """fdoct_process below the pipeline's threshold stages its host-memory arguments through the same plan (fdoct_stage.h) as the
+    side entry points.  512 x 16 u16 frames, 512 points, 256 depths, 2 averages, 4 frames, called through the C ABI for what
+    Reconstructor.process cannot reach: host frames at a padded pitch (1024 + 16 bytes) into device outputs, device frames into
+    host outputs, host into host with one output wanted -- each, in both layouts, equal bit for bit to process() on the packed
+    host arrays.  Then calls refused before anything is enqueued -- 3 frames with 2 averages, a handle without a background --
+    with the code and text they have always had, after which the next good call still matches."""
+    import torch
+    w, hh, n, d = 512, 16, 512, 256
+    cfg = Config(width=w, height=hh, numfftpoints=n, numdisplaypoints=d, averages=2)
+    frames = synth.make_frames(11, 4, w, hh)
+    padded = np.zeros((4, hh, w + 8), np.uint16)
+    padded[:, :, :w] = frames
+    rec = Reconstructor(cfg)
+    rec.set_background(synth.make_background(w))
+    U16, HOST, DEV = capi.DTYPE_U16, capi.MEM_HOST, capi.MEM_DEVICE
+
+    def call(r, fr, space, nframes, pitch, mag, db, out_space, lay):
+        ptr = lambda a: None if a is None else a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data
+        return r.lib.fdoct_process(r.h, ptr(fr), U16, space, nframes, pitch, ptr(mag), ptr(db), out_space, lay)
+
+    def refused(r, rc, code, text):
+        assert rc == code and r.lib.fdoct_last_error(r.h).decode() == text, (rc, r.lib.fdoct_last_error(r.h))
+
+    for lay in (ROW, TR):
+        want_b, want_d = rec.process(frames, layout=lay)
+        # host frames at a padded pitch into device outputs
+        t_b, t_d = (torch.zeros(want_b.shape, dtype=torch.float32, device="cuda") for _ in range(2))
+        torch.cuda.synchronize()
+        assert call(rec, padded, HOST, 4, 2 * w + 16, t_b, t_d, DEV, lay) == 0
+        _same((t_b.cpu().numpy(), t_d.cpu().numpy()), (want_b, want_d), "padded host frames into device outputs, layout %d" % lay)
+        # device frames into host outputs
+        t_f = torch.from_numpy(frames).cuda()
+        torch.cuda.synchronize()
+        got_b, got_d = np.zeros_like(want_b), np.zeros_like(want_d)
+        assert call(rec, t_f, DEV, 4, 0, got_b, got_d, HOST, lay) == 0
+        _same((got_b, got_d), (want_b, want_d), "device frames into host outputs, layout %d" % lay)
+        # host into host, one output wanted
+        got_d = np.zeros_like(want_d)
+        assert call(rec, frames, HOST, 4, 0, None, got_d, HOST, lay) == 0
+        _same(got_d, want_d, "host into host, dB only, layout %d" % lay)
+        got_b = np.zeros_like(want_b)
+        assert call(rec, padded, HOST, 4, 2 * w + 16, got_b, None, HOST, lay) == 0
+        _same(got_b, want_b, "padded host into host, linear only, layout %d" % lay)
+    # refused calls leave nothing behind
+    want_b, want_d = rec.process(frames)
+    got_b, got_d = np.zeros_like(want_b), np.zeros_like(want_d)
+    refused(rec, call(rec, frames, HOST, 3, 0, got_b, got_d, HOST, ROW), -1, "nframes must be a multiple of averages")
+    refused(rec, call(rec, frames, HOST, 4, 0, None, None, HOST, ROW), -1, "no output requested")
+    refused(rec, call(rec, frames, HOST, 4, 2 * w - 2, got_b, got_d, HOST, ROW), -1, "pitch smaller than a row")
+    assert not got_b.any() and not got_d.any()
+    assert call(rec, frames, HOST, 4, 0, got_b, got_d, HOST, ROW) == 0
+    _same((got_b, got_d), (want_b, want_d), "the good call after the refused ones")
+    rec.close()
+    bare = Reconstructor(cfg)
+    got_b, got_d = np.zeros_like(want_b), np.zeros_like(want_d)
+    refused(bare, call(bare, frames, HOST, 4, 0, got_b, got_d, HOST, ROW), -5, "no background set (fdoct_set_background)")
+    assert not got_b.any()
+    bare.set_background(synth.make_background(w))
+    assert call(bare, frames, HOST, 4, 0, got_b, got_d, HOST, ROW) == 0
+    _same((got_b, got_d), (want_b, want_d), "the good call after the one without a background")
+    bare.close()
