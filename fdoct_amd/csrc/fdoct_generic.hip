@@ -764,6 +764,8 @@ __global__ __launch_bounds__(256) void median_kernel(const T* in, long long in_p
 
 // box mean over binx x biny, rounded to the sample type as cv::resize(INTER_AREA) does for integer
 // factors: (s + 2) >> 2 for 2x2 (the vectorised 8u/16u path), round-half-even of s * (1/area) otherwise.
+// Up to binx * biny = 256 this integer sum and a float32 accumulation of 16-bit samples agree exactly (the sum stays below
+// 2^24); beyond that area they need not (tests/frontend_model.py states the same limit).
 template <typename T>
 __global__ void bin_kernel(const T* in, long long in_pitch, T* out, long long out_pitch, int ow, int oh, int binx, int biny,
                            int nframes) {
@@ -891,11 +893,12 @@ static hipError_t launch_median_t(const void* in, long long in_pitch, void* out,
   if (n == 3 && w % 8 == 0 && in_pitch % 16 == 0 && out_pitch % 16 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0) {
     const long long nrows = (long long)nframes * h;
     const int chunks = w / 8, bx = chunks < 256 ? ((chunks + 63) / 64) * 64 : 256;
+    // (more rows than the cap: tests/test_gpu_frontend_edges.py, MEDIAN3_ROWS)
     const dim3 g((chunks + bx - 1) / bx, (unsigned)(nrows < 32768 ? nrows : 32768));
     hipLaunchKernelGGL((median3_fast_kernel<T>), g, dim3(bx), 0, st, static_cast<const T*>(in), in_pitch, static_cast<T*>(out), out_pitch, w, h, nrows);
     return hipGetLastError();
   }
-  const dim3 g(8192), b(256);
+  const dim3 g(8192), b(256);  // (more pixels than one pass: tests/test_gpu_frontend_edges.py, MEDIAN_PASS)
   const T* i = static_cast<const T*>(in);
   T* o = static_cast<T*>(out);
   switch (n) {
@@ -954,12 +957,14 @@ hipError_t launch_bin(const void* in, long long in_pitch, void* out, long long o
     const long long out_rows = (long long)nframes * oh;
     const auto* i8 = static_cast<const unsigned char*>(in);
     auto* o8 = static_cast<unsigned char*>(out);
+    // (more vectors than one pass: tests/test_gpu_frontend_edges.py, BIN2X2_PASS)
     if (dtype == FDOCT_K_U16)
       hipLaunchKernelGGL(bin2x2_kernel<uint16_t>, dim3(8192), dim3(256), 0, st, i8, in_pitch, o8, out_pitch, vecs, out_rows);
     else
       hipLaunchKernelGGL(bin2x2_kernel<uint8_t>, dim3(8192), dim3(256), 0, st, i8, in_pitch, o8, out_pitch, vecs, out_rows);
     return hipGetLastError();
   }
+  // (more outputs than one pass: tests/test_gpu_frontend_edges.py, BIN_PASS)
   if (dtype == FDOCT_K_U8)
     hipLaunchKernelGGL(bin_kernel<uint8_t>, dim3(4096), dim3(256), 0, st, static_cast<const uint8_t*>(in), in_pitch,
                        static_cast<uint8_t*>(out), out_pitch, ow, oh, binx, biny, nframes);
