@@ -106,6 +106,9 @@ COLOUR_ABI_SYMBOLS = ["fdoct_set_colour_input", "fdoct_get_colour_input", "fdoct
 # every symbol include/fdoct_manualavg.h declares: manual averaging of B-scans (manualaveraging / manualaverages), likewise on its own
 MANUALAVG_ABI_SYMBOLS = ["fdoct_manualavg_plan", "fdoct_manualavg_begin", "fdoct_manualavg_add", "fdoct_manualavg_state",
                          "fdoct_manualavg_end"]
+# every symbol include/fdoct_saveframes.h declares: per-frame saves while averaging (saveframes) and the chain's raw-magnitudes
+# switch, likewise on their own
+SAVEFRAMES_ABI_SYMBOLS = ["fdoct_set_raw_magnitudes", "fdoct_get_raw_magnitudes", "fdoct_saveframes"]
 # fdoct_manualavg_mode (include/fdoct_manualavg.h)
 MANUALAVG_REFERENCE, MANUALAVG_KEEP_ALL = 0, 1
 # fdoct_ref_role (include/fdoct_capture.h)
@@ -249,6 +252,11 @@ def load_library():
     lib.fdoct_manualavg_state.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                           C.POINTER(C.c_int), C.c_void_p]
     lib.fdoct_manualavg_end.argtypes = [C.c_void_p]
+    # include/fdoct_saveframes.h
+    lib.fdoct_set_raw_magnitudes.argtypes = [C.c_void_p, C.c_int]
+    lib.fdoct_get_raw_magnitudes.argtypes = [C.c_void_p]
+    lib.fdoct_saveframes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
     return lib
 
@@ -846,6 +854,43 @@ class Reconstructor:
     def manualavg_end(self):
         """Frees the accumulator (close() does so too)."""
         self._check(self.lib.fdoct_manualavg_end(self.h))
+
+    # -- per-frame saves while averaging (include/fdoct_saveframes.h)
+    def set_raw_magnitudes(self, on=True):
+        """The chain writes a group's mean magnitude without its epsilon (with averages = 1: a frame's own magnitudes, what
+        saveframes() takes); process* then refuse a dB output."""
+        self._check(self.lib.fdoct_set_raw_magnitudes(self.h, int(on)))
+
+    def get_raw_magnitudes(self):
+        rc = self.lib.fdoct_get_raw_magnitudes(self.h)
+        if rc < 0:
+            self._check(rc)
+        return bool(rc)
+
+    def saveframes(self, frames, averages=0, in_layout=LAYOUT_ROWMAJOR, out_layout=LAYOUT_TRANSPOSED, want_gray=True,
+                   want_bscan=True, want_db=True):
+        """BscanFFT.cpp:1197-1240 and 1360-1377 on host magnitudes: float32 (nframes, ascans, depths) in the row-major layout,
+        (nframes, depths, ascans) in the transposed one, or one such image.  Returns (gray, bscan, bscandb): gray uint8
+        (nframes, depths, ascans), every frame's save picture; bscan / bscandb float32, one image per group of `averages`
+        frames in out_layout.  averages = 0: no fold, both are None; so is whatever is not wanted."""
+        a, n, d, h = _db_batch(frames, in_layout)
+        g = n // averages if averages > 0 else 0
+        shp = (g, d, h) if out_layout == LAYOUT_TRANSPOSED else (g, h, d)
+        gray = np.empty((n, d, h), np.uint8) if want_gray else None
+        bscan = np.empty(shp, np.float32) if want_bscan and averages > 0 else None
+        db = np.empty(shp, np.float32) if want_db and averages > 0 else None
+        self._check(self.lib.fdoct_saveframes(self.h, a.ctypes.data, MEM_HOST, in_layout, n, d, h,
+                                              None if gray is None else gray.ctypes.data, int(averages),
+                                              None if bscan is None else bscan.ctypes.data, None if db is None else db.ctypes.data,
+                                              out_layout, MEM_HOST))
+        return gray, bscan, db
+
+    def saveframes_device(self, d_frames_ptr, nframes, depths, ascans, d_gray_ptr, averages=0, d_bscan_ptr=None, d_db_ptr=None,
+                          in_layout=LAYOUT_ROWMAJOR, out_layout=LAYOUT_TRANSPOSED):
+        """... on device-resident magnitudes (raw device addresses; the picture and the fold outputs may each be None, not all
+        of them).  Enqueues on the handle's stream."""
+        self._check(self.lib.fdoct_saveframes(self.h, d_frames_ptr, MEM_DEVICE, in_layout, int(nframes), int(depths), int(ascans),
+                                              d_gray_ptr, int(averages), d_bscan_ptr, d_db_ptr, out_layout, MEM_DEVICE))
 
     # -- work
     def _out_shape(self, nframes, layout):

@@ -610,6 +610,7 @@ int fdoct_clone_to_device(fdoct_handle h, int device, fdoct_handle* out) try {
   c->bandpass = h->bandpass;
   c->jit = h->jit;
   c->precise_div = h->precise_div;
+  c->raw_mag = h->raw_mag;
   c->staged = h->staged;
   c->async_timing = h->async_timing;
   c->host_staging = h->host_staging;  // (the setting: the clone starts its own copy threads)

@@ -12,6 +12,7 @@
 //   fdoct_bscanbin.cpp those of include/fdoct_bscanbin.h (spinjnt's output binning between the linear B-scan and its dB)
 //   fdoct_colour.cpp  those of include/fdoct_colour.h (the webcam's interleaved B,G,R frames: channelnum)
 //   fdoct_manualavg.cpp those of include/fdoct_manualavg.h (manual averaging of B-scans: manualaccum and its counter)
+//   fdoct_saveframes.cpp those of include/fdoct_saveframes.h (per-frame saves while averaging; the raw-magnitudes switch)
 //   fdoct_stage.h     the staging plan of host-memory arguments: the side entry points', fdoct_process's single shot (stage_reserve / stage_upload / stage_finish, below, commit it)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
@@ -226,6 +227,10 @@ struct fdoct_ctx {
   DevBuf<double> d_mavg;           // manualaccum (BscanFFT.cpp:933): mavg_count running sums
   size_t mavg_count = 0;
   int mavg_m = 0, mavg_mode = 0, mavg_accumulated = 0;  // manualaverages (0: no accumulator), fdoct_manualavg_mode, manualaccumcount
+  // per-frame saves (fdoct_saveframes.cpp).  fdoct_set_raw_magnitudes: the chain's kernels get 0 for their epsilon
+  // (kernel_eps) and write no dB.  A run-time setting like `averages`: fdoct_clone_to_device carries it, the state blob does not.
+  bool raw_mag = false;
+  DevBuf<double> d_sf_part;        // partial (min, max) pairs of the pictures' dB values, per image (fdoct_saveframes_kernels.h)
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
@@ -438,6 +443,7 @@ int run_colour(fdoct_ctx* h, const void* d_bgr, int nframes, int raw_w, int raw_
 int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_w, int raw_h, size_t raw_pitch, int mediann,
                  int binx, int biny, void** out, size_t* out_pitch);
 float chain_eps(const fdoct_ctx* h);  // the epsilon under the chain's log (sim:949 / main:1222)
+float kernel_eps(const fdoct_ctx* h);  // what the chain's kernels are handed for it: chain_eps, or 0 with fdoct_set_raw_magnitudes
 int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
                  uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r);
 // What refuses a call without a route and without its frames: no background, no output, a bad dtype, a pitch below a row.  First in

@@ -327,7 +327,7 @@ int run_big(fdoct_ctx* h, const void* kframes, const float* kframes_lo, int kdt,
     a.rowwisenormalize = h->cfg.rowwisenormalize;
     a.dcmask = h->cfg.dc_mask;
     a.inv_A = (float)(1.0 / (double)A);
-    a.eps = (h->cfg.variant == FDOCT_VARIANT_SIM) ? 1e-6f : 1e-5f;
+    a.eps = kernel_eps(h);
     a.db_scale = (float)(20.0 / 2.303 * 0.6931471805599453);
     HIP_TRY(h, big_launch_pre(a, h->ws_big_y, st));
     // Buffer discipline of big_idft with a loader: the first launch reads the loader's source and writes `other`, the next one
@@ -601,6 +601,7 @@ int finish_launch(fdoct_ctx* h, const Route& r, const Call& c, bool staged_timin
 }
 
 float chain_eps(const fdoct_ctx* h) { return (h->cfg.variant == FDOCT_VARIANT_SIM) ? 1e-6f : 1e-5f; }  // sim:949 / main:1222
+float kernel_eps(const fdoct_ctx* h) { return h->raw_mag ? 0.0f : chain_eps(h); }                     // fdoct_set_raw_magnitudes
 constexpr float kDbScale = (float)(20.0 / 2.303 * 0.6931471805599453);                                // main:1236, times ln 2 (the kernels use log2)
 
 int launch_family_wave(fdoct_ctx* h, const Route& r, const Call& c) {
@@ -625,7 +626,7 @@ int launch_family_wave(fdoct_ctx* h, const Route& r, const Call& c) {
   wa.off_tww = h->wave_off[3]; wa.off_twmw = h->wave_off[4]; wa.off_twn = h->wave_off[5];
   wa.dcmask = h->cfg.dc_mask;
   wa.inv_A = (float)(1.0 / (double)A);
-  wa.eps = chain_eps(h);
+  wa.eps = kernel_eps(h);
   wa.db_scale = kDbScale;
   wa.out_mag = c.k_mag;
   wa.out_db = c.k_db;
@@ -749,7 +750,7 @@ int launch_family_generic(fdoct_ctx* h, const Route& r, const Call& c) {
   ga.rowwisenormalize = h->cfg.rowwisenormalize;
   ga.dcmask = h->cfg.dc_mask;
   ga.inv_A = (float)(1.0 / (double)A);
-  ga.eps = chain_eps(h);
+  ga.eps = kernel_eps(h);
   ga.db_scale = kDbScale;
   ga.out_mag = c.k_mag;
   ga.out_db = c.k_db;
@@ -884,7 +885,7 @@ int launch_family_fused(fdoct_ctx* h, const Route& r, const Call& c) {
   a.dcmask = h->cfg.dc_mask;
   a.need_rc = (a.ib2d || a.yp_2d || a.yd_2d || a.minmax || a.frames_lo) ? 1 : 0;
   a.inv_A = (float)(1.0 / (double)A);
-  a.eps = chain_eps(h);
+  a.eps = kernel_eps(h);
   a.db_scale = kDbScale;
   a.out_mag = c.k_mag;
   a.out_db = c.k_db;
@@ -983,6 +984,7 @@ static int run_passes_in_front(fdoct_ctx* h, const Route& r, Call& c, const void
 int check_call(fdoct_ctx* h, fdoct_dtype dtype, size_t pitch_bytes, const float* out_bscan, const float* out_db) {
   if (!h->yb.rows) return fail(h, FDOCT_ERR_STATE, "no background set (fdoct_set_background)");
   if (!out_bscan && !out_db) return fail(h, FDOCT_ERR_INVALID, "no output requested");
+  if (h->raw_mag && out_db) return fail(h, FDOCT_ERR_INVALID, "raw magnitudes are on (fdoct_set_raw_magnitudes): out_db must be NULL");
   const size_t es = frame_pixel_bytes(h, dtype);
   if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
   if (pitch_bytes && pitch_bytes < es * h->W) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a row");  // (0: packed rows)

@@ -11,7 +11,7 @@
 //                [--rowwisenormalize 0|1] [--donotnormalize 0|1] [--repeat K] [--threshold dB] --out prefix
 //                [--gpus N [--devices d0,d1,...]] [--precise-division | --one-word-division]
 //                [--roi-mean ascanat,vertpos,width] [--capture-background N [--capture-lowpass] [--capture-raw]] [--max-intensity]
-//                [--bscan-bin BX,BY[,BINVALUEX,BINVALUEY]] [--channel N] [--manual-averages M [--manual-keep-all]]
+//                [--bscan-bin BX,BY[,BINVALUEX,BINVALUEY]] [--channel N] [--manual-averages M [--manual-keep-all]] [--save-frames]
 //
 // --gpus N: one process, N handles (fdoct_clone_to_device), one host thread per handle; the frames are sharded with
 // fdoct_shard_frames (contiguous ranges, averaging groups never split -- the rule of the multi-process path,
@@ -39,6 +39,11 @@
 // dropped, as in the reference; with --manual-keep-all every M give one and nothing is dropped.  The emitted images are written
 // as <prefix>_bscanman.f32 (manualaccum / M, what 1440 saves before its log) and <prefix>_bscanman_db.f32 (20 ln / 2.303), D x H
 // each; B-scans left in the accumulator at the end are reported and not written.
+// --save-frames: the ini's save_individual_frames_if_averaging (BscanFFT.cpp:1198-1205, 1360-1377; include/fdoct_saveframes.h).
+// The chain then runs once per camera frame -- averages = 1 with raw magnitudes on, so it writes every frame's own magnitudes --
+// and fdoct_saveframes makes from them the averaged B-scans (sums in double, as the reference accumulates) and every frame's
+// save picture, written as <prefix>_bscanNNN-III.pgm (D x H; NNN the B-scan from 001, III the frame of its group from 000, as
+// the reference counts them).  The reference saves the PREVIOUS group's frames on `s`; this writes every group's own.
 // --max-intensity: the status line's "Max intensity = <floor(max)>" (BscanFFT.cpp:1105-1108) for every reconstructed frame.
 // --frames holds one or more H x W frames back to back (u8 for --bits 8, little-endian u16 for --bits 16).
 // Outputs: <prefix>_bscan.f32 / <prefix>_bscandb.f32 (reference layout D x H per B-scan, main:1220) and
@@ -63,6 +68,7 @@
 #include "../include/fdoct_lowpass.h"
 #include "../include/fdoct_manualavg.h"
 #include "../include/fdoct_roi.h"
+#include "../include/fdoct_saveframes.h"
 #include "ocv_io.h"
 
 static bool ends_with(const std::string& s, const std::string& suf) {
@@ -101,6 +107,7 @@ int main(int argc, char** argv) {
   int channel = -1;                // --channel channelnum (-1: mono frames)
   int manual_averages = -1;        // --manual-averages manualaverages (-1: manualaveraging off)
   int manual_mode = FDOCT_MANUALAVG_REFERENCE;  // --manual-keep-all
+  bool save_frames = false;        // --save-frames
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -155,6 +162,7 @@ int main(int argc, char** argv) {
       }
     }
     else if (a == "--manual-keep-all") manual_mode = FDOCT_MANUALAVG_KEEP_ALL;
+    else if (a == "--save-frames") save_frames = true;
     else if (a == "--devices") {
       for (const char* p = next(); *p;) {
         devices.push_back(std::atoi(p));
@@ -178,6 +186,13 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--channel takes 8-bit B,G,R frames: give --bits 8\n");
     return 1;
   }
+  if (save_frames && cfg.variant == FDOCT_VARIANT_SIM) {
+    std::fprintf(stderr, "--save-frames folds the frames of a group: the sim variant copies and does not accumulate\n");
+    return 1;
+  }
+  // --save-frames: the chain's handle takes the frames one by one; `averages` is the fold's
+  const int averages = cfg.averages;
+  if (save_frames) cfg.averages = 1;
   const int frame_channels = channel >= 0 ? 3 : 1;
   const size_t frame_bytes = (size_t)cfg.width * cfg.height * es * frame_channels;
 
@@ -211,7 +226,7 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "%s holds no complete %dx%d frame\n", frames_path.c_str(), cfg.width, cfg.height);
     return 1;
   }
-  const int nframes = nframes_file / cfg.averages * cfg.averages;
+  const int nframes = nframes_file / averages * averages;
   if (nframes < 1) {
     std::fprintf(stderr, "need at least `averages` frames\n");
     return 1;
@@ -259,16 +274,23 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "fdoct_set_precise_division: %s\n", fdoct_last_error(h));
     return 1;
   }
+  if (save_frames && (rc = fdoct_set_raw_magnitudes(h, 1))) {
+    std::fprintf(stderr, "fdoct_set_raw_magnitudes: %s\n", fdoct_last_error(h));
+    return 1;
+  }
   // before the loop: tables, kernel family and any run-time compile, so that the first frame does not stall (an acquisition
   // program would do the same after its 'b' key)
-  const int prepared = fdoct_prepare(h, dt, FDOCT_LAYOUT_TRANSPOSED_DxH);
+  const int prepared = fdoct_prepare(h, dt, save_frames ? FDOCT_LAYOUT_ROWMAJOR_HxD : FDOCT_LAYOUT_TRANSPOSED_DxH);
   if (prepared < 0) {
     std::fprintf(stderr, "fdoct_prepare: %d %s\n", prepared, fdoct_last_error(h));
     return 1;
   }
-  const int G = nframes / cfg.averages;
+  const int G = nframes / averages;
   const size_t out_elems = (size_t)G * cfg.numdisplaypoints * cfg.height;
   std::vector<float> bscan(out_elems), bscandb(out_elems);
+  // --save-frames: every frame's magnitudes (H x D, as the chain writes them) and its picture (D x H)
+  std::vector<float> framemag(save_frames ? (size_t)nframes * cfg.numdisplaypoints * cfg.height : 0);
+  std::vector<unsigned char> framegray(framemag.size());
   // one handle per GPU: clones of the configured handle, each on its own device and host thread
   if (gpus < 1) gpus = 1;
   const int ndev = fdoct_device_count();
@@ -286,12 +308,23 @@ int main(int argc, char** argv) {
   const size_t bscan_elems = (size_t)cfg.numdisplaypoints * cfg.height;
   auto run_shard = [&](int g) {
     int first = 0, count = 0;
-    fdoct_shard_frames(nframes, cfg.averages, g, gpus, &first, &count);
+    fdoct_shard_frames(nframes, averages, g, gpus, &first, &count);
     if (count == 0) return;
-    const size_t o0 = (size_t)(first / cfg.averages) * bscan_elems;
-    for (int k = 0; k < repeat && !rcs[g]; k++)  // the while(1) loop, bounded; sim:842-955 per iteration
-      rcs[g] = fdoct_process(hs[g], live + (size_t)first * frame_bytes, dt, FDOCT_MEM_HOST, count, 0, bscan.data() + o0,
-                             bscandb.data() + o0, FDOCT_MEM_HOST, FDOCT_LAYOUT_TRANSPOSED_DxH);
+    const size_t o0 = (size_t)(first / averages) * bscan_elems;
+    for (int k = 0; k < repeat && !rcs[g]; k++) {  // the while(1) loop, bounded; sim:842-955 per iteration
+      if (!save_frames) {
+        rcs[g] = fdoct_process(hs[g], live + (size_t)first * frame_bytes, dt, FDOCT_MEM_HOST, count, 0, bscan.data() + o0,
+                               bscandb.data() + o0, FDOCT_MEM_HOST, FDOCT_LAYOUT_TRANSPOSED_DxH);
+        continue;
+      }
+      float* mag = framemag.data() + (size_t)first * bscan_elems;
+      rcs[g] = fdoct_process(hs[g], live + (size_t)first * frame_bytes, dt, FDOCT_MEM_HOST, count, 0, mag, nullptr, FDOCT_MEM_HOST,
+                             FDOCT_LAYOUT_ROWMAJOR_HxD);
+      if (!rcs[g])
+        rcs[g] = fdoct_saveframes(hs[g], mag, FDOCT_MEM_HOST, FDOCT_LAYOUT_ROWMAJOR_HxD, count, cfg.numdisplaypoints, cfg.height,
+                                  framegray.data() + (size_t)first * bscan_elems, averages, bscan.data() + o0, bscandb.data() + o0,
+                                  FDOCT_LAYOUT_TRANSPOSED_DxH, FDOCT_MEM_HOST);
+    }
   };
   const auto t0 = std::chrono::steady_clock::now();
   if (gpus == 1) {
@@ -303,7 +336,7 @@ int main(int argc, char** argv) {
   }
   for (int g = 0; g < gpus; g++)
     if (rcs[g]) {
-      std::fprintf(stderr, "fdoct_process (handle %d): %d %s\n", g, rcs[g], fdoct_last_error(hs[g]));
+      std::fprintf(stderr, "%s (handle %d): %d %s\n", save_frames ? "fdoct_process / fdoct_saveframes" : "fdoct_process", g, rcs[g], fdoct_last_error(hs[g]));
       return 1;
     }
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -316,6 +349,18 @@ int main(int argc, char** argv) {
               fdoct_version(), nframes, repeat, gpus, G, cfg.numdisplaypoints, cfg.height,
               (double)nframes * cfg.height * repeat / sec, tm.last_process_ms, tm.last_kernel_ms,
               fam >= 0 && fam < 8 ? family[fam] : "?", *fdoct_jit_note(h) ? "; " : "", fdoct_jit_note(h));
+
+  if (save_frames) {
+    // main:1375-1376: one picture per frame, named after its B-scan and its place in the group
+    for (int f = 0; f < nframes; f++) {
+      char name[64];
+      std::snprintf(name, sizeof name, "_bscan%03d-%03d.pgm", f / averages + 1, f % averages);
+      std::ofstream pg(out + name, std::ios::binary);
+      pg << "P5\n" << cfg.height << " " << cfg.numdisplaypoints << "\n255\n";
+      pg.write(reinterpret_cast<const char*>(framegray.data() + (size_t)f * bscan_elems), (std::streamsize)bscan_elems);
+    }
+    std::printf("save frames: %d picture(s) of %d B-scan(s) written\n", nframes, G);
+  }
 
   // spinjnt's output stage (BscanFFTspinjnt.cpp:1856-1874): the averaged linear B-scan is binned and resized back, and the dB
   // (with the DC mask) is taken of the result; everything below sees these images, as in the reference

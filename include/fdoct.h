@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define FDOCT_VERSION_MAJOR 0
-#define FDOCT_VERSION_MINOR 4   /* 0.4: fdoct_set_host_staging, fdoct_get_host_staging (additions only) */
+#define FDOCT_VERSION_MINOR 5   /* 0.5: the raw-magnitudes switch and the per-frame saves of fdoct_saveframes.h (additions only) */
 
 typedef struct fdoct_ctx* fdoct_handle;
 
