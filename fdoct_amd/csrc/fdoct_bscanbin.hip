@@ -235,6 +235,7 @@ void bscanbin_plan(BscanBinArgs* a, int num_cu) {
   a->lds_stride = ncc | 1;  // odd: the rows of a column of cells start in different banks
   a->lds_bytes = ((size_t)kBinTapStride * (a->upr + a->upc) + (size_t)ncr * a->lds_stride) * sizeof(double);
   const long long ntiles = (long long)a->tiles_r * a->tiles_c * a->nb;
+  // (more tiles than the cap: tests/test_gpu_stage_grids.py, test_binning_more_tiles_than_workgroups)
   const long long resident = resident_blocks(num_cu, BIN_WAVES_PER_CU, BIN_BLOCK);
   a->blocks = (int)std::min(ntiles, resident);
 }

@@ -221,6 +221,7 @@ hipError_t launch_capture_accumulate(const CaptureFrames& in, int movavgn, bool 
   a.zero_start = zero_start;
   a.out = out;
   const long long items = runs_of(in, sample_bytes(in.dt));
+  // (more runs than the capped grid has threads: tests/test_gpu_stage_grids.py, test_capture_beyond_one_pass_of_the_grid)
   const int blocks = (int)std::min<long long>((items + CAP_BLOCK - 1) / CAP_BLOCK, resident_blocks(num_cu, CAP_WAVES_PER_CU, CAP_BLOCK));
   switch (in.dt) {
     case FDOCT_U8: hipLaunchKernelGGL(capture_accumulate_kernel<uint8_t>, dim3(blocks), dim3(CAP_BLOCK), 0, st, a); break;
@@ -248,6 +249,8 @@ hipError_t launch_frame_minmax(const CaptureFrames& in, double* partials, double
   a.nframes = in.nframes, a.H = in.H, a.W = in.W;
   a.vec = vec_ok(in);
   a.partials = partials;
+  // (more than 64 partials a frame, and more frames than workgroups: tests/test_gpu_stage_grids.py,
+  // test_one_large_frame_takes_the_folds_second_stride, test_more_frames_than_workgroups)
   const int nblk = frame_minmax_blocks(in, num_cu);
   const dim3 grid(nblk, in.nframes);
   switch (in.dt) {

@@ -187,6 +187,7 @@ hipError_t launch_colour(const ColourArgs& a, hipStream_t st) {
       a.pitch < 3LL * a.ow * a.binx || reinterpret_cast<uintptr_t>(a.out) % 16 || a.out_pitch % 16 ||
       a.out_pitch < (long long)a.ow * (a.channelnum == 3 ? 8 : 1))
     return hipErrorInvalidValue;
+  // (more items than 8192 workgroups take in one pass, either kernel: tests/test_gpu_stage_grids.py, test_colour_*_beyond_one_pass)
   int x0 = 0;
   if (colour_vectorised(a)) {
     const long long items = a.out_rows * (a.ow / 16);

@@ -158,6 +158,8 @@ LowpassShape lowpass_shape(int rows, int W, int num_cu) {
     s.G = 1, s.L = chunks * LP_T;
     s.lds = 0;
   }
+  // (more rows than the cap, more than 256 staged bins, the last staged width 5849 and every slice count:
+  // tests/test_gpu_stage_grids.py, test_lowpass_*; the formulas restated in tests/stage_grid_sizes.py)
   const int cap = resident_blocks(num_cu, LP_WAVES_PER_CU, LP_BLOCK);
   s.blocks = std::max(1, std::min(rows, cap));
   s.ws_doubles = s.staged ? 0 : (size_t)s.blocks * 4 * s.f;

@@ -242,6 +242,7 @@ hipError_t launch_roi_hold(const RoiImage& im, int x, int y, int w, int h, int a
   slices = std::min(slices, std::max(1LL, lane_work / kMinLaneLoads));
   a.slices = (int)slices;
   const long long items = (long long)per_slice * slices;
+  // (more runs than waves, and the quad masks against poisoned surroundings: tests/test_gpu_stage_grids.py, test_hold_*)
   const int blocks = (int)std::min<long long>((items + 3) / 4, resident_blocks(num_cu, ROI_WAVES_PER_CU, ROI_BLOCK));
   hipLaunchKernelGGL(roi_hold_kernel, dim3(blocks), dim3(ROI_BLOCK), 0, st, a);
   return hipGetLastError();
@@ -250,6 +251,7 @@ hipError_t launch_roi_hold(const RoiImage& im, int x, int y, int w, int h, int a
 hipError_t launch_roi_ascan_minmax(const RoiImage& im, int ascanat, float* out_min, float* out_max, int num_cu, hipStream_t st) {
   const long long bs = (long long)im.depths * im.ascans;
   const int vec = !im.transposed && im.depths % 4 == 0 && aligned16(im.db);
+  // (more B-scans than waves: tests/test_gpu_stage_grids.py, test_ascan_minmax_of_more_bscans_than_waves)
   const int blocks = std::min((im.nb + 3) / 4, resident_blocks(num_cu, ROI_WAVES_PER_CU, ROI_BLOCK));
   hipLaunchKernelGGL(roi_minmax_kernel, dim3(blocks), dim3(ROI_BLOCK), 0, st, im.db, bs, im.nb, im.depths, im.ascans,
                      im.transposed, ascanat, vec, out_min, out_max);
@@ -258,6 +260,7 @@ hipError_t launch_roi_ascan_minmax(const RoiImage& im, int ascanat, float* out_m
 
 hipError_t launch_roi_mean(const RoiImage& im, int ascanat, int vertpos, int width, double* out, int num_cu, hipStream_t st) {
   const long long bs = (long long)im.depths * im.ascans;
+  // (more B-scans than workgroups: tests/test_gpu_stage_grids.py, test_roi_mean_of_more_bscans_than_workgroups)
   const int blocks = std::min(im.nb, resident_blocks(num_cu, ROI_WAVES_PER_CU, ROI_BLOCK));
   hipLaunchKernelGGL(roi_mean_kernel, dim3(blocks), dim3(ROI_BLOCK), 0, st, im.db, bs, im.nb, im.depths, im.ascans,
                      im.transposed, ascanat, vertpos, width, out);

@@ -315,7 +315,11 @@ def test_frame_minmax_is_exact(dt, device_out):
 
 
 def test_c2_sized_capture_and_minmax_on_device_frames():
-    """2048 x 1000 u16, 16 device-resident frames: the grid-stride loops of both kernels on a frame that fills the chip."""
+    """2048 x 1000 u16, 16 device-resident frames: a frame that fills the chip.  Its 256 000 runs of 8 samples stay below the
+    262 144 threads of a 256-CU card's capped grid, so capture_accumulate_kernel's loop body runs once per thread here, and with
+    16 frames the min / max fold reads exactly one 64-lane stride of partials.  The second strides are taken by
+    tests/test_gpu_stage_grids.py: test_capture_beyond_one_pass_of_the_grid, test_one_large_frame_takes_the_folds_second_stride
+    and test_more_frames_than_workgroups."""
     W, H, n = 2048, 1000, 16
     rng = np.random.default_rng(77)
     frames = rng.integers(0, 65536, (n, H, W), dtype=np.uint16)
