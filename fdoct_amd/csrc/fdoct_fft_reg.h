@@ -182,6 +182,20 @@ __device__ __forceinline__ v2f twc(v2f v) {
   }
 }
 
+// The 4-point DFT whose input 2 is still owed a quarter turn (the twiddle exp(+-2*pi*i/4) of the stage before: +i for INV,
+// -i forward): v[0] +- (+-i)*v[2] are packed adds with the turn on their modifiers, where the turn on its own is a v_xor and
+// a v_mov.  x + (-y) and x - y are the same operation, so the values are those of fft_reg<4> on the turned input, bit for bit.
+template <bool INV>
+__device__ __forceinline__ void fft_reg4_turn2(v2f* v) {
+  const v2f t0 = INV ? sub_mulmi(v[0], v[2]) : add_mulmi(v[0], v[2]);
+  const v2f t1 = INV ? add_mulmi(v[0], v[2]) : sub_mulmi(v[0], v[2]);
+  const v2f t2 = v[1] + v[3], d = v[1] - v[3];
+  v[0] = t0 + t2;
+  v[1] = INV ? sub_mulmi(t1, d) : add_mulmi(t1, d);
+  v[2] = t0 - t2;
+  v[3] = INV ? add_mulmi(t1, d) : sub_mulmi(t1, d);
+}
+
 // In-register R-point DFT, natural order in and out.  R in {1,2,4,8,16,32}.
 template <int R, bool INV>
 __device__ __forceinline__ void fft_reg(v2f* v) {
@@ -205,12 +219,19 @@ __device__ __forceinline__ void fft_reg(v2f* v) {
       fft_reg<4, INV>(t);
       static_for<0, 4>([&](auto k1c) {
         constexpr int k1 = decltype(k1c)::value;
-        v[k1 * Rb + n2] = twc<k1 * n2, R, INV>(t[k1]);
+        // (R = 16: the one quarter turn, k1 = n2 = 2, is left to the second stage)
+        if constexpr (R == 16 && k1 == 2 && n2 == 2)
+          v[k1 * Rb + n2] = t[k1];
+        else
+          v[k1 * Rb + n2] = twc<k1 * n2, R, INV>(t[k1]);
       });
     });
     static_for<0, 4>([&](auto k1c) {
       constexpr int k1 = decltype(k1c)::value;
-      fft_reg<Rb, INV>(v + k1 * Rb);
+      if constexpr (R == 16 && k1 == 2)
+        fft_reg4_turn2<INV>(v + k1 * Rb);
+      else
+        fft_reg<Rb, INV>(v + k1 * Rb);
     });
     v2f o[R];
     static_for<0, R>([&](auto ic) {

@@ -2013,17 +2013,21 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
           const v2f Xa2 = Xa * Xa, Xb2 = Xb * Xb;
           const float lo_mag = fast_sqrt(Xa2.x + Xa2.y);
           acc[m] = AVG ? acc[m] + lo_mag : lo_mag;
-          float hi = fast_sqrt(Xb2.x + Xb2.y);
+          float hi2 = Xb2.x + Xb2.y;
           if constexpr (m == 0) {
-            // bin NC/2: Z[NC/2] is its own partner; only lane 0 keeps the result
-            const v2f zc = z[PH];
-            const v2f Ac = add_conj(zc, zc), Bc = sub_conj(zc, zc);
-            const v2f qc = cmul(twc<PH, 2 * P, true>(utw_row), Bc);
-            const v2f Xc = add_mulmi(Ac, qc);
+            // bin NC/2: Z[NC/2] = zc is its own partner and only lane 0 keeps the result, so only lane 0's phasor counts:
+            // utw = (1, +-0) there (exp of 0) and the PH/(2P) turn is an exact quarter turn.  Run through the general formula
+            // that gives  A = zc + conj(zc) = (2x, +0),  B = zc - conj(zc) = (+0, 2y),  q = i*utw*B = (-2y, +0) and
+            // X = A - i*q = (2x + 0, 0 + 2y): every step is exact (doubling is; x - x and the products with 0 are zeros,
+            // and adding a zero changes at most the sign of a zero), so X is zc + zc up to the sign of a zero component.
+            // The square discards that sign (both give +0), hence |X|^2 below has the bits the general formula had for
+            // every finite zc, zeros of either sign included -- and one square root serves both selections.
+            const v2f Xc = z[PH] + z[PH];
             const v2f Xc2 = Xc * Xc;
-            const float mid = fast_sqrt(Xc2.x + Xc2.y);
-            hi = (l == 0) ? mid : hi;
+            const float mid2 = Xc2.x + Xc2.y;
+            hi2 = (l == 0) ? mid2 : hi2;
           }
+          const float hi = fast_sqrt(hi2);
           acc[PH + m] = AVG ? acc[PH + m] + hi : hi;
         });
       }
@@ -2110,11 +2114,23 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     const int D = a.D;
     const bool upper_slots = !CPLX || D > NC / 2;  // complex path, half-depth output: slots >= P/2 are never stored
     float outv[P];
+    // (without averaging the epsilon add goes two slots to a packed add: each half rounds like the single add)
+    auto add_eps = [&](auto lo_c, auto hi_c) {
+      if constexpr (AVG) {
 #pragma unroll
-    for (int m = 0; m < P / 2; m++) outv[m] = AVG ? fmaf(acc[m], a.inv_A, a.eps) : (acc[m] + a.eps);
+        for (int m = decltype(lo_c)::value; m < decltype(hi_c)::value; m++) outv[m] = fmaf(acc[m], a.inv_A, a.eps);
+      } else {
+#pragma unroll
+        for (int m = decltype(lo_c)::value; m < decltype(hi_c)::value; m += 2) {
+          const v2f o = mk(acc[m], acc[m + 1]) + mk(a.eps, a.eps);
+          outv[m] = o.x;
+          outv[m + 1] = o.y;
+        }
+      }
+    };
+    add_eps(IC<0>{}, IC<P / 2>{});
     if (upper_slots) {
-#pragma unroll
-      for (int m = P / 2; m < P; m++) outv[m] = AVG ? fmaf(acc[m], a.inv_A, a.eps) : (acc[m] + a.eps);
+      add_eps(IC<P / 2>{}, IC<P>{});
     } else {
 #pragma unroll
       for (int m = P / 2; m < P; m++) outv[m] = 1.f;
