@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fdoct_big_plan.h"
 #include "fdoct_kernels.h"
 
 namespace fdoct {
@@ -39,8 +40,7 @@ hipError_t big_launch_fft_pass(const float2* src, float2* dst, long long rows, i
 // The first group may read its input through a loader (the elementwise step in front of the transform fused into it), the
 // last one may crop its output.
 enum { BIG_LOAD_CPLX = 0, BIG_LOAD_REAL = 1, BIG_LOAD_PAD = 2, BIG_LOAD_RESAMPLE = 3 };
-constexpr int BIG_GROUP_MAX_PASSES = 6;
-constexpr int BIG_GROUP_TILE_VALUES = 2048;  // values of one workgroup's tile (sub-problems x local length): 8 per thread in registers during a pass
+// (BIG_GROUP_MAX_PASSES, BIG_GROUP_TILE_VALUES and the plan of the groups: fdoct_big_plan.h)
 struct BigGroup {
   const float2* src;         // BIG_LOAD_CPLX: rows of n complex values; BIG_LOAD_PAD: the W-point spectra (rows of W)
   float2* dst;               // rows of n

@@ -440,7 +440,7 @@ hipError_t big_launch_fft_pass(const float2* src, float2* dst, long long rows, i
   }
   return hipGetLastError();
 }
-size_t big_group_lds_bytes(const BigGroup& g) { return (size_t)g.Q * ((1u << g.log2ts) + 1) * sizeof(float2); }
+size_t big_group_lds_bytes(const BigGroup& g) { return big_group_lds_bytes(g.Q, g.log2ts); }
 hipError_t big_launch_fft_group(const BigGroup& g, hipStream_t st) {
   const int S = g.P * g.F, TS = 1 << g.log2ts;
   const long long tiles = g.rows * ((S + TS - 1) / TS);

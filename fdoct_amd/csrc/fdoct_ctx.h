@@ -157,10 +157,7 @@ struct fdoct_ctx {
   int wave_tw_count = 0, wave_off[6] = {0, 0, 0, 0, 0, 0};
   DevBuf<float2> d_twg_n, d_twg_nh, d_twg_w, d_twg_mw, d_twg_wh, d_twg_mwh;
   // long-row path (fdoct_big.hip): rows in HBM, one DFT plan per length
-  struct BigGroupPlan {        // one launch: a group of the transform's passes with the data in LDS (fdoct_big.h)
-    int P = 1, Q = 1, F = 1, log2ts = 0;
-    std::vector<int> rad;
-  };
+  using BigGroupPlan = fdoct::BigGroupPlan;  // one launch: a group of the transform's passes with the data in LDS (fdoct_big_plan.h)
   struct BigPlan {
     std::vector<int> rad;      // Stockham radices of the length itself, or (Bluestein) of mb: the one-launch-per-pass form
     std::vector<BigGroupPlan> groups;  // the same transform as a few launches of several passes each (empty: not available)

@@ -100,60 +100,7 @@ int run_colour(fdoct_ctx* h, const void* d_bgr, int nframes, int raw_w, int raw_
 }
 
 // ---- long-row path (fdoct_big.hip) ----------------------------------------------------------------------------------
-// The passes of an n-point transform (n = 2^a 3^b 5^c) as a few groups, each one launch with its data in LDS: the prime
-// factors are dealt to G groups so that the groups' lengths come out as equal as they can (16384 = 128 x 128, 4096 = 64 x 64),
-// G the smallest count that keeps every length within what a workgroup's tile holds.
-bool big_plan_groups(int n, std::vector<fdoct_ctx::BigGroupPlan>& groups) {
-  groups.clear();
-  std::vector<int> primes;
-  int m = n;
-  for (int p : {5, 3, 2})
-    while (m % p == 0) { primes.push_back(p); m /= p; }
-  if (m != 1 || n < 2) return false;
-  constexpr int kQmax = BIG_GROUP_TILE_VALUES / 8;   // 8 sub-problems of this many points fill the tile (64 contiguous bytes per element index)
-  int G = 1;
-  for (double cap = kQmax; cap < (double)n; cap *= kQmax) G++;
-  for (; G <= 4; G++) {
-    std::vector<long long> prod(G, 1);
-    std::vector<std::vector<int>> fac(G);
-    for (int p : primes) {  // largest factors first, each to the group that is shortest so far
-      int best = 0;
-      for (int g = 1; g < G; g++)
-        if (prod[g] < prod[best]) best = g;
-      prod[best] *= p;
-      fac[best].push_back(p);
-    }
-    bool ok = true;
-    for (int g = 0; g < G; g++) ok = ok && prod[g] <= BIG_GROUP_TILE_VALUES / 4;
-    if (!ok) continue;
-    long long P = 1;
-    for (int g = 0; g < G; g++) {
-      fdoct_ctx::BigGroupPlan gp;
-      gp.P = (int)P;
-      gp.Q = (int)prod[g];
-      gp.F = (int)(n / (P * prod[g]));
-      int twos = 0;
-      for (int p : fac[g]) {
-        if (p == 2) twos++;
-        else gp.rad.push_back(p);
-      }
-      for (; twos >= 3; twos -= 3) gp.rad.push_back(8);
-      if (twos == 2) gp.rad.push_back(4);
-      if (twos == 1) gp.rad.push_back(2);
-      if ((int)gp.rad.size() > BIG_GROUP_MAX_PASSES || gp.rad.empty()) { ok = false; break; }
-      const long long S = (long long)gp.P * gp.F;
-      int l2 = 4;
-      while (l2 > 0 && (((long long)gp.Q << l2) > BIG_GROUP_TILE_VALUES || (1LL << l2) > S)) l2--;
-      gp.log2ts = l2;
-      groups.push_back(gp);
-      P *= prod[g];
-    }
-    if (ok) return true;
-    groups.clear();
-  }
-  return false;
-}
-
+// (the plans of its transforms and the chunks of a batch are values: fdoct_big_plan.h)
 // DFT plan of one length: Stockham radices when it factors into 2, 3, 5, else Bluestein around a power of two >= 2n - 1.
 int big_plan_get(fdoct_ctx* h, int n, fdoct_ctx::BigPlan** out) {
   auto it = h->big_plans.find(n);
@@ -162,30 +109,19 @@ int big_plan_get(fdoct_ctx* h, int n, fdoct_ctx::BigPlan** out) {
     return FDOCT_OK;
   }
   fdoct_ctx::BigPlan p;
-  auto radices = [](int len, std::vector<int>& rad) {  // 5s and 3s first, then 8s, then what is left of the power of two
-    rad.clear();
-    while (len % 5 == 0) { rad.push_back(5); len /= 5; }
-    while (len % 3 == 0) { rad.push_back(3); len /= 3; }
-    while (len % 8 == 0) { rad.push_back(8); len /= 8; }
-    if (len % 4 == 0) { rad.push_back(4); len /= 4; }
-    if (len % 2 == 0) { rad.push_back(2); len /= 2; }
-    return len == 1;
-  };
-  int tn = n;
-  if (!radices(n, p.rad)) {
-    int mb = 1;
-    while (mb < 2 * n - 1) mb <<= 1;
-    p.mb = mb;
-    radices(mb, p.rad);
-    tn = mb;
+  static const bool per_pass = [] { const char* e = std::getenv("FDOCT_BIG_PER_PASS"); return e && std::atoi(e) != 0; }();  // measurement: round 3's form
+  BigTransform t = make_big_transform(n, per_pass);
+  p.rad = std::move(t.rad);
+  p.groups = std::move(t.groups);
+  p.mb = t.mb;
+  const int tn = t.tn;
+  if (p.mb) {
     std::vector<float2> chirp, bhat;
-    build_bluestein_tables(n, mb, chirp, bhat);
+    build_bluestein_tables(n, p.mb, chirp, bhat);
     int rc;
     if ((rc = upload(h, p.d_chirp, chirp))) return rc;
     if ((rc = upload(h, p.d_bhat, bhat))) return rc;
   }
-  static const bool per_pass = [] { const char* e = std::getenv("FDOCT_BIG_PER_PASS"); return e && std::atoi(e) != 0; }();  // measurement: round 3's form
-  if (!per_pass) big_plan_groups(tn, p.groups);
   std::vector<float2> tw(tn);
   for (int j = 0; j < tn; j++) {
     const double a = 2.0 * kPi * (double)j / (double)tn;
@@ -298,12 +234,12 @@ int run_big(fdoct_ctx* h, const void* kframes, const float* kframes_lo, int kdt,
     if ((rc = big_plan_get(h, n, &p))) return rc;
     lmax = std::max(lmax, (size_t)std::max(n, p->mb));
   }
-  const size_t per_group = (size_t)A * H * ((size_t)W * 4 + 2 * lmax * sizeof(float2));
-  long long cg = (long long)(((size_t)2 << 30) / per_group);
   const int G = nframes / A;
-  if (cg < 1) cg = 1;
-  if (cg > G) cg = G;
-  const size_t crow = (size_t)cg * A * H;
+  long long chunk_mb = 0;
+  if (const char* e = std::getenv("FDOCT_BIG_CHUNK_MB")) chunk_mb = std::atoll(e);  // read per call, like FDOCT_HOST_CHUNK_MB: the tests cut small batches with it
+  const BigChunks ch = make_big_chunks(W, H, A, G, lmax, big_chunk_budget(chunk_mb));
+  const long long cg = ch.cg;
+  const size_t crow = ch.rows;
   if ((rc = h->ws_big_y.reserve(h, crow * W * 4))) return rc;
   if ((rc = h->ws_big_a.reserve(h, crow * lmax * sizeof(float2)))) return rc;
   if ((rc = h->ws_big_b.reserve(h, crow * lmax * sizeof(float2)))) return rc;

@@ -164,6 +164,22 @@ def test_plan_decisions_match_the_recorded_table(tmp_path):
     assert not diff, "%d decisions differ, first: %s" % (len(diff), diff[0])
 
 
+def test_long_row_plans_and_chunks_match_the_recorded_table(tmp_path):
+    """The long-row path's host-side decisions (fdoct_amd/csrc/fdoct_big_plan.h) are values without HIP in them.
+    tests/native/bigplan_check.cpp asserts their invariants for every length 2^a 3^b 5^c from 2 to 2^24 -- a grouped plan exists,
+    the groups' lengths multiply to n and P Q F = n in each, every tile and its LDS fit, the radices multiply to Q, the group
+    count is 1 up to 256 points, 2 up to 65 536 and 3 beyond (4 only where three groups cannot hold the factors) -- and for the
+    chunks of a batch over a grid of geometries and budgets: 1 <= cg <= G, the chunks cover G exactly, the buffers hold cg A H
+    rows; a failed invariant is a non-zero exit status.  Its table -- the plan of every transform length that
+    tests/test_gpu_long_rows.py runs and the chunk sequences of its batches -- must equal bigplan_check.expected, recorded from
+    big_plan_groups, big_plan_get's radix split and run_big's chunk arithmetic as they were moved out of fdoct_route.cpp."""
+    got, want = _native_table(tmp_path, "bigplan_check")
+    assert len(got) == len(want) and len(want) > 30
+    diff = [(w, g) for w, g in zip(want, got) if w != g]
+    assert not diff, "%d rows differ, first: %s" % (len(diff), diff[0])
+    assert got[0] == "lengths 2^a 3^b 5^c from 2 to 2^24 checked: 835"
+
+
 def test_staging_plan_places_host_memory_arguments(tmp_path):
     """The staging plan of the side entry points (fdoct_amd/csrc/fdoct_stage.h) is a value without HIP in it:
     tests/native/stage_check.cpp, built with plain g++ like the two tables above, checks over the plan type alone that every
