@@ -504,18 +504,41 @@ template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_add_f32(float v) {
   return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true));
 }
+// The two cross-row steps of that sum, one v_add_f32_dpp each: row_bcast:15 into rows 1 and 3, then row_bcast:31 into rows 2
+// and 3.  The destination is tied to v, so rows outside a mask keep v.  (Written with the builtin above, each step is three
+// instructions -- a zero, a v_mov_b32_dpp into it, an add: the compiler does not fold a partial row mask into a float add,
+// because the rows left out would hold v where the source says v + 0, and those differ for v = -0.)  That difference cannot
+// reach group_sum_f32's result, which is lane 63 alone: lane 63 is in both masks, so it is added to in both steps; what it
+// adds is lane 47 as the row shifts left it (a DPP step reads its sources before any lane is written) and then lane 31, which
+// is in row 1 and so was itself added to in the first step.  No lane that a mask leaves out is read again.
+// The compiler does not see a DPP read inside an asm statement, so the two wait states that a VALU write of v needs before
+// a DPP read of it are in the statement itself.  The five that a VALU write of EXEC (v_cmpx) needs before a DPP operation are
+// not: the callers run this at the top level of a row, with every lane on (which the broadcasts assume as well: no bound_ctrl),
+// and the compiler writes EXEC from the scalar unit there.  A caller under a v_cmpx would have to wait them out itself.
+__device__ __forceinline__ float dpp_add_cross_rows_f32(float v) {
+  asm("s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
+      : "+v"(v));
+  return v;
+}
 
 // Sum over the T lanes of a row group in f32, returned to every lane of the group (T == 64: the DPP chain of
-// group_sum, one v_add_f32_dpp per step).
-template <int T>
+// group_sum; ONE_EACH: one v_add_f32_dpp per step, the cross-row steps included -- the same bits either way).
+template <int T, bool ONE_EACH>
 __device__ __forceinline__ float group_sum_f32(float v) {
   if constexpr (T == 64) {
     v = dpp_add_f32<0x111, 0xf>(v);
     v = dpp_add_f32<0x112, 0xf>(v);
     v = dpp_add_f32<0x114, 0xf>(v);
     v = dpp_add_f32<0x118, 0xf>(v);
-    v = dpp_add_f32<0x142, 0xa>(v);
-    v = dpp_add_f32<0x143, 0xc>(v);
+    if constexpr (ONE_EACH) {
+      v = dpp_add_cross_rows_f32(v);
+    } else {
+      v = dpp_add_f32<0x142, 0xa>(v);
+      v = dpp_add_f32<0x143, 0xc>(v);
+    }
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
   } else {
 #pragma unroll
@@ -531,10 +554,10 @@ __device__ __forceinline__ float group_sum_f32(float v) {
 // q = p - base (values and partial sums of fringe size), whose rounding errors are those of any f32 arithmetic on
 // the fringe signal itself.  mean = base / SPL + sum(q) / W; inv_spl and inv_w are exact reciprocals (powers of two
 // on the compiled plans).
-template <int T>
+template <int T, bool ONE_EACH>
 __device__ __forceinline__ void group_mean_f32(float p, float inv_t, float inv_spl, float inv_w, float& mh, float& ml) {
-  const float base = group_sum_f32<T>(p) * inv_t;
-  const float qs = group_sum_f32<T>(p - base);
+  const float base = group_sum_f32<T, ONE_EACH>(p) * inv_t;
+  const float qs = group_sum_f32<T, ONE_EACH>(p - base);
   const float m1 = base * inv_spl, m2 = qs * inv_w;
   mh = m1 + m2;  // two-sum: mh + ml == m1 + m2 exactly
   const float bb = mh - m1;
@@ -627,6 +650,11 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   static_assert(!(PRECT && !LEAN), "the any-option kernel always multiplies by both words");
   static_assert(!(PRECT && IB2D && !IL16), "a full-frame background on the fast path: the second word is prefetched as half floats");
 
+  // The row loop's trims (one v_add_f32_dpp per cross-row step of the wave sums; the row ticket as a plain ds_add_rtn_u32): the
+  // same results bit for bit, taken where they are measured to pay -- the 1024-point one-exchange plan writing rows.  The
+  // transposed-store kernels are at 256 VGPRs with scratch and allocate worse with either; with the ticket's wait fixed inside
+  // an asm statement the plans with four rows per wave lose what the compiler gains by placing it (EXPERIMENTS.md section 7).
+  constexpr bool TRIM = KIND == 1 && !TRO;
   __shared__ unsigned int row_ticket;  // next unclaimed row slot of this workgroup
   __shared__ unsigned int tr_arrived[4];  // TRO: rows of tile (q mod 4) in the ring
   // TRO: tiles q = i (mod 4) that have completed so far.  Tiles need not complete in order -- with a 4-row last tile of a
@@ -1130,9 +1158,20 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   // the FFT-stage kernel, which prefetches at the row top -- one whole row ahead (EARLY).
   constexpr bool EARLY = STAGE == 2;
   auto slot_row = [&](unsigned s) { return ((long long)s * gridDim.x + blockIdx.x) * RPW; };
+  // TRIM kernels: the add is written out as the instruction, with its wait.  As an atomic builtin inside `if (lane == 0)` the
+  // compiler's atomic optimiser elects a lane a second time (v_mbcnt twice, a compare, a count of exec, a second exec mask and
+  // branch, a v_readfirstlane and an add of the lane's rank) for a wave that has one lane left.  The other kernels keep the
+  // builtin, where the compiler is free to place the wait (see TRIM).
   auto claim = [&]() -> unsigned {
     unsigned t = 0;
-    if (lane == 0) t = __hip_atomic_fetch_add(&row_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if constexpr (!TRIM) {
+      if (lane == 0) t = __hip_atomic_fetch_add(&row_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    } else if (lane == 0) {
+      const unsigned at = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned*)&row_ticket;
+      asm volatile("ds_add_rtn_u32 %0, %1, %2\n\t"
+                   "s_waitcnt lgkmcnt(0)"
+                   : "=&v"(t) : "v"(at), "v"(1u) : "memory");
+    }
     return t;
   };
   // (An asm ds_add_rtn_u32 whose result stays in flight until it is needed would save the LDS round trip the compiler
@@ -1570,7 +1609,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             for (int p = 0; p < 4; p++) s4[p] = pk_fma(v[4 * c + p], ibv[4 * c + p], s4[p]);
           }
           const v2f part = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-          group_mean_f32<T>(part.x + part.y, 1.f / (float)T, 1.f / (float)(8 * WCH), 1.f / (float)WC, mh, ml);
+          group_mean_f32<T, TRIM>(part.x + part.y, 1.f / (float)T, 1.f / (float)(8 * WCH), 1.f / (float)WC, mh, ml);
 #else
           // Row mean without any DC-sized sum: c0, the average of one x = v / yb per lane, is a wave-uniform estimate
           // of the mean; d = fma(v, 1/yb, -c0) is the exact product minus c0 rounded at the size of the DEVIATION from it
@@ -1584,7 +1623,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
           // workgroup's LDS plane (there is no register left to keep them resident), read at the row top (ilx).
           // (the 64 samples 8 l of the first chunk.  The middle chunk was tried in round 6 -- it is what the any-option kernel below
           // takes its single-chunk estimate from -- and left C2's flat 1e-3 dB pass rate at 0.9999 instead of 1: kept as it was.)
-          const float c0 = group_sum_f32<T>((NPREC ? (v[0].x - nmn) * nsc : v[0].x) * ibv[0].x) * (1.f / (float)T);
+          const float c0 = group_sum_f32<T, TRIM>((NPREC ? (v[0].x - nmn) * nsc : v[0].x) * ibv[0].x) * (1.f / (float)T);
           // IL16: what the first word leaves out, v * il = (v * ib) * rho = (c0 + d) * rho with rho = il / ib (|rho| <= 2^-24), is
           // c0 * rho up to d * rho -- below the rounding of d.  rho * 2^38 comes as half floats (ten bits of a correction that is
           // 8 x the tolerance at fringes of 1e-3 of the DC level), v_fma_mix_f32 converts them inside the fma.
@@ -1628,7 +1667,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             for (int p = 0; p < 4; p++) s4[p] += v[4 * c + p];
           }
           const v2f part = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-          mh = group_sum_f32<T>(part.x + part.y) * (1.f / (float)WC);  // mean of d (W == WC on this path)
+          mh = group_sum_f32<T, TRIM>(part.x + part.y) * (1.f / (float)WC);  // mean of d (W == WC on this path)
 #endif
           if constexpr (RESC) {
 #pragma unroll
@@ -1695,7 +1734,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
               }
             }
             if constexpr (CMEAN) {
-              if (c == 0) c0 = group_sum_f32<T>(v[0].x * ibv[0].x) * (1.f / (float)T);
+              if (c == 0) c0 = group_sum_f32<T, TRIM>(v[0].x * ibv[0].x) * (1.f / (float)T);
               if constexpr (IL16R) {   // what the first word leaves out is c0 * rho up to d * rho (see the fast path above)
                 const float c0s = c0 * 3.637978807091713e-12f;  // 2^-38 (kPrec16Shift)
                 const uint32_t hq[4] = {r_il16r[c].x, r_il16r[c].y, r_il16r[c].z, r_il16r[c].w};
@@ -1769,8 +1808,8 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
                 }
               }
               if (!have_c0 && (LEAN || 8 * T * c < W)) {
-                const float cnt = group_sum_f32<T>(in_row ? 1.f : 0.f);
-                c0 = group_sum_f32<T>(in_row ? v[4 * c].x * ibv[4 * c].x : 0.f) / cnt;   // (cnt >= 1: the chunk's first lane is in the row)
+                const float cnt = group_sum_f32<T, TRIM>(in_row ? 1.f : 0.f);
+                c0 = group_sum_f32<T, TRIM>(in_row ? v[4 * c].x * ibv[4 * c].x : 0.f) / cnt;   // (cnt >= 1: the chunk's first lane is in the row)
                 have_c0 = true;
               }
 #pragma unroll
@@ -1789,7 +1828,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
           // ---------------- A3: DC removal (mean in double; CMEAN: mean of the deviations from c0, in float)
           if constexpr (CMEAN) {
             const v2f part = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-            mh = group_sum_f32<T>(part.x + part.y) * (1.f / (float)WC);
+            mh = group_sum_f32<T, TRIM>(part.x + part.y) * (1.f / (float)WC);
             ml = 0.f;
           } else {
             sum = group_sum<T>(sum);
