@@ -135,7 +135,7 @@ struct fdoct_ctx {
   // device state
   DevBuf<float> d_ib, d_ib2d, d_ib2d_f, d_yp, d_yd, d_yp_lo, d_yd_lo, d_win, d_g;
   DevBuf<float> d_il, d_il2d, d_il2d_f, d_il_p;  // d_il_p: d_il in the order of the fused kernels' LDS planes  // low words of the reciprocal background, laid out like d_ib / d_ib2d / d_ib2d_f
-  DevBuf<uint32_t> d_il16, d_il16_2d;  // the second word as the fast path reads it: il / ib * 2^38 as half-float pairs (fdoct_kernels.h: FDOCT_PREC16)
+  DevBuf<uint32_t> d_il16, d_il16_2d;  // the second word as the fast path reads it: il / ib * 2^38 as half-float pairs (fdoct_fused_rules.h: fused_il_half)
   // fdoct_set_precise_division.  ON by default (round 5): main:1132 divides in double, and one f32 reciprocal leaves a fixed
   // pattern of 6e-8 of the DC level -- 8 x the tolerance on fringes of 1e-3 of it.  Off (or FDOCT_PRECISE_DIVISION=0) is the
   // opt-out for callers who know their fringes exceed ~1 % of the DC level.

@@ -4,9 +4,8 @@
 #pragma once
 #include <cstddef>
 
-#ifndef FDOCT_MAX_BLOCK
-#define FDOCT_MAX_BLOCK 768
-#endif
+// Largest workgroup any fused kernel is compiled for (fdoct_capi.cpp checks a caller's geometry against it).
+constexpr int FDOCT_MAX_BLOCK = 768;
 
 namespace fdoct {
 
@@ -17,9 +16,6 @@ namespace fdoct {
 // fast-path row-swap plan (kind 1) keeps its row-invariant tables in registers: all of these trade
 // occupancy for registers instead of spilling.
 constexpr int fused_max_block(int nc, int T, bool lean, int kind) {
-#ifdef FDOCT_X_BLOCK  // tuning: threads per workgroup of the fast-path row-swap plan (768 = 3 waves per SIMD, <= 168 VGPRs)
-  if (lean && kind == 1) return FDOCT_X_BLOCK;
-#endif
   return (nc / T >= 32 || !lean || kind == 1) ? 512 : FDOCT_MAX_BLOCK;  // nc/T = FFT points held per lane
 }
 
@@ -27,9 +23,6 @@ constexpr int fused_max_block(int nc, int T, bool lean, int kind) {
 // registers; the host then leaves those three planes out of the workgroup's LDS (FusedArgs::lds_planes = 0), which is
 // what lets the 2048-point plans run 7 instead of 5 waves per CU.  One definition for kernel and host.
 constexpr bool fused_resident_consts(int kind, bool lean, bool avg, int wch, int stage) {
-#ifdef FDOCT_X_NO_RESC  // tuning: constant planes from LDS on the 1024-point plan
-  if (kind == 1) return false;
-#endif
   return lean && (kind == 1 || (kind == 2 && !avg)) && wch <= 4 && stage != 2;
 }
 
@@ -39,40 +32,22 @@ enum { FDOCT_K_U8 = 0, FDOCT_K_U16 = 1, FDOCT_K_F32 = 2 };
 // (fdoct_capi.cpp::reciprocal_words; fdoct_set_precise_division).  The any-option kernel always uses both.
 // FDOCT_PREC_T2: how many of the 12 step-3 twiddles of the 1024-point plan stay in registers in the kernels that can
 // multiply by both words (the rest come from LDS every row: the low words' 32 registers are in flight at the row top).
-#ifndef FDOCT_PREC_T2
-#define FDOCT_PREC_T2 6
-#endif
-// FDOCT_PREC16: the form of the second word on the fast-path kernels with at most 32 samples per lane (fused_kernel's ILX).
+constexpr int FDOCT_PREC_T2 = 6;
+// The form of the second word on the fast-path kernels with at most 32 samples per lane (fused_kernel's IL16; fused_il_half).
 // The missing part of the quotient, v * il, is (v * ib) * (il / ib) = (c0 + d) * rho with rho = il / ib, |rho| <= 2^-24, and
 // d * rho lies below the rounding of d itself: the correction is c0 * rho_i -- a row-dependent scalar times a column-dependent
-// pattern that needs no more than ~10 bits.  1: the pattern is a plane of HALF floats (rho * 2^38: 2 W bytes of LDS, 16
+// pattern that needs no more than ~10 bits.  The pattern is a plane of HALF floats (rho * 2^38: 2 W bytes of LDS, 16
 // registers in flight instead of 32, every step-3 twiddle resident again) applied by v_fma_mix_f32, which converts its f16
-// operand inside the fma.  0: round 4's form, il as floats multiplied by the samples.
-#ifndef FDOCT_PREC16
-#define FDOCT_PREC16 1
-#endif
-#ifndef FDOCT_PREC16_T2
-#define FDOCT_PREC16_T2 10       // step-3 twiddles resident in the half-float form (16 registers in flight at the row top): 516 M A-scans/s with 10 or 8, 513 with 12
-#endif
-#ifndef FDOCT_PREC16_T2_IB2D
-#define FDOCT_PREC16_T2_IB2D 0   // ... with a full-frame background (16 more registers hold the next row's pattern): 443 against 422 M A-scans/s with 4
-#endif
-#ifndef FDOCT_PREC16_T2_DMA
-#define FDOCT_PREC16_T2_DMA 8    // ... with a full-frame background whose pattern row is prefetched into LDS (FDOCT_IL16_DMA): 478 M A-scans/s against 438 with 12 (spills) and 442 with the pattern row in registers
-#endif
-#ifndef FDOCT_IL16_RESIDENT
-#define FDOCT_IL16_RESIDENT 1    // 1: the averaging kernels with more than 32 samples per lane keep the half-float pattern in registers
-#endif
-#ifndef FDOCT_IL16_DMA
-#define FDOCT_IL16_DMA 1         // 1: a full-frame background's pattern row is prefetched into LDS by global_load_lds_dwordx4 (no registers)
-#endif
+// operand inside the fma.  (Round 4's form, il as floats multiplied by the samples, is what the kernels with wider rows keep.)
+constexpr int FDOCT_PREC16_T2 = 10;      // step-3 twiddles resident in the half-float form (16 registers in flight at the row top): 516 M A-scans/s with 10 or 8, 513 with 12
+constexpr int FDOCT_PREC16_T2_IB2D = 0;  // ... with a full-frame background (16 more registers hold the next row's pattern): 443 against 422 M A-scans/s with 4
+constexpr int FDOCT_PREC16_T2_DMA = 8;   // ... with a full-frame background whose pattern row is prefetched into LDS (fused_il16_dma_bytes): 478 M A-scans/s against 438 with 12 (spills) and 442 with the pattern row in registers
+// The averaging kernels with more than 32 samples per lane keep the half-float pattern in registers (fused_kernel, IL16R).  A
+// full-frame background's pattern row is prefetched into LDS by global_load_lds_dwordx4 (no registers; fused_kernel, ILDMA):
 // LDS bytes per computing wave of that prefetch slot (one definition for kernel and host)
-constexpr size_t fused_il16_dma_bytes(bool ib2d, bool both_words_half, bool tro, int wc) { return (FDOCT_IL16_DMA && ib2d && both_words_half && !tro) ? (size_t)2 * wc : 0; }
-#ifndef FDOCT_TRO_IB2D_RES3
-#define FDOCT_TRO_IB2D_RES3 0    // 1: the transposed-store variant of that kernel keeps its 15 step-5 twiddles in registers (spills)
-#endif
+constexpr size_t fused_il16_dma_bytes(bool ib2d, bool both_words_half, bool tro, int wc) { return (ib2d && both_words_half && !tro) ? (size_t)2 * wc : 0; }
 constexpr int kPrec16Shift = 38;  // rho * 2^38: at most 2^14 in magnitude
-constexpr bool fused_il_half(bool lean, int wch) { return FDOCT_PREC16 != 0 && lean && wch <= 4; }
+constexpr bool fused_il_half(bool lean, int wch) { return lean && wch <= 4; }
 // The averaging fast-path kernels with more than 32 samples per lane keep their planes in LDS and are bound by its capacity (a
 // fourth plane would cost C4 a wave per CU): they read the low words from a global plane in the same order (FusedArgs::prec = 3).
 // (round 6: so do ALL fast-path kernels of the 512-point plan -- C1, 16 lanes per row, four rows per wave -- averaging or not, row-major
@@ -82,23 +57,13 @@ constexpr bool fused_il_global(bool lean, bool avg, int wch, int T = 64) { retur
 
 // Rows per tile of the fused transposed store: a workgroup owns FUSED_TR_ROWS consecutive A-scans of one B-scan at a time, so
 // the depth-major output is written in segments of FUSED_TR_ROWS * 4 bytes.
-#ifndef FUSED_TR_ROWS
-#define FUSED_TR_ROWS 16
-#endif
+constexpr int FUSED_TR_ROWS = 16;
 // Slots of the LDS ring of finished rows (FUSED_TR_ROWS < slots <= 2 FUSED_TR_ROWS): what 160 KB of LDS hold of 1024-bin
 // rows next to seven computing waves' buffers.
-#ifndef FUSED_TR_RING
-#define FUSED_TR_RING 20
-#endif
-// Who writes a complete tile out: 1 = every wave takes steps of it at its hand-over points (all waves compute); 2 = the wave
-// whose row completes it, all steps at once (all waves compute; one LDS round trip per row); 0 = the last wave of the
-// workgroup does nothing else (one wave less computes).  Measured (profiles/r03_tro_final_probe.txt): at 1024
-// depth bins 1 is 0-4 % ahead of 2, up to 512 bins (40-slot ring) 2 is 4 % ahead of 1; 1 ships because the reference's
-// configurations display 1024 bins.
-#ifndef FDOCT_TRO_DW
-#define FDOCT_TRO_DW 1
-#endif
-constexpr int fused_tro_writer_waves() { return FDOCT_TRO_DW ? 0 : 1; }
+constexpr int FUSED_TR_RING = 20;
+// Who writes a complete tile out: every wave takes steps of it at its hand-over points, and all waves compute.  (Measured against
+// the wave whose row completes the tile writing it out at once, and against a wave set aside for it: DESIGN.md 3.1a,
+// profiles/r03_tro_final_probe.txt.)
 // Ring slots for numdisplaypoints = d: up to 512 depth bins a second tile fits (rows of the next tile go in while a tile is
 // written out: + 7 %), above that FUSED_TR_RING is what the LDS holds.  One definition for kernel and host.
 constexpr unsigned fused_tro_ring_slots(int d) { return d <= 512 ? 2u * FUSED_TR_RING : (unsigned)FUSED_TR_RING; }
@@ -120,38 +85,24 @@ constexpr unsigned fused_tro_ring_pick(size_t lds_left, int d, int rpw = 1) {
   return best;
 }
 // Which tables a fused kernel stages in LDS (one rule for kernel and host).  tw3: the step-5 table of the 1024-point row-swap plan.
-// (ib2d_both_words: the variant with a full-frame background and both words re-reads its step-5 twiddles every row: FDOCT_TRO_IB2D_RES3)
+// (ib2d_both_words: the variant with a full-frame background and both words re-reads its step-5 twiddles every row; keeping
+// them in registers there spills)
 constexpr bool fused_tw3_in_lds(int kind, bool lean, int stage, bool tro, bool ib2d_both_words) {
-  return !(tro && lean && kind == 1 && stage != 1 && !(ib2d_both_words && !FDOCT_TRO_IB2D_RES3));
+  return !(tro && lean && kind == 1 && stage != 1 && !ib2d_both_words);
 }
-// Transposed store, row-swap plan, 16-bit samples, no per-row prefetch besides the samples (one-spectrum background, no frame
-// normalisation): the samples are prefetched TWO rows ahead (fused_kernel, PF2) -- a wave's vector-memory operations return in
-// order, so with one row of distance the prefetched samples wait behind the write-out stores issued a row earlier, and those take
-// 2-8 us to be acknowledged (EXPERIMENTS.md section 5).  The second set of sample registers takes the place of the resident gather
-// addresses: the gather table goes back to LDS in this variant.
-#ifndef FDOCT_TRO_PF2
-#define FDOCT_TRO_PF2 0
-#endif
-constexpr bool fused_tro_pf2(int kind, bool lean, int stage, bool cplx, bool avg, bool tro, bool ib2d, int norm, int sample_bytes) {
-  return FDOCT_TRO_PF2 && tro && lean && stage == 0 && kind == 1 && !cplx && !avg && !ib2d && norm == 0 && sample_bytes == 2;
+constexpr bool fused_gi_in_lds(int kind, bool lean, int stage, bool cplx, bool avg, bool tro) {
+  return !(tro && lean && stage != 2 && kind == 1 && !cplx && !avg);
 }
-constexpr bool fused_gi_in_lds(int kind, bool lean, int stage, bool cplx, bool avg, bool tro, bool pf2 = false) {
-  return pf2 || !(tro && lean && stage != 2 && kind == 1 && !cplx && !avg);
-}
-#ifndef FDOCT_TRO_SPIN_LIMIT
-#define FDOCT_TRO_SPIN_LIMIT (1u << 21)  // x s_sleep(8) = 512 cycles each: about half a second
-#endif
+constexpr unsigned FDOCT_TRO_SPIN_LIMIT = 1u << 21;  // x s_sleep(8) = 512 cycles each: about half a second
 // Depth bins one iteration of the tile write-out covers (numdisplaypoints must be a multiple of it).
 // Four rows per wave (the 512-point plan's in-place tiles): waves per group = rows per tile / 4.  Groups of EIGHT waves own tiles of
 // 32 rows and write the D x H image in 128-byte segments -- whole cache lines, which the memory system takes at its row-major rate
 // where 64-byte segments stop at 3.7 TB/s (profiles/r06_rw_mix.txt) -- at no cost in LDS (the rows lie in the waves' own buffers).
 // Built and measured (round 6, profiles/r06_c1_group_ab.txt, bit-identical results): 790 against 855 M A-scans/s on C1 -- a workgroup
 // that is ONE group meets twice per tile with all of its waves, and what they idle there outweighs the segments.  Four it stays.
-#ifndef FDOCT_TRO_GROUP_WAVES
-#define FDOCT_TRO_GROUP_WAVES 4
-#endif
-constexpr int fused_tro_group_waves() { return FDOCT_TRO_GROUP_WAVES; }
-constexpr int fused_tro_tile_rows(int rpw) { return rpw == 4 ? 4 * FDOCT_TRO_GROUP_WAVES : FUSED_TR_ROWS; }
+constexpr int kTroGroupWaves = 4;
+constexpr int fused_tro_group_waves() { return kTroGroupWaves; }
+constexpr int fused_tro_tile_rows(int rpw) { return rpw == 4 ? 4 * kTroGroupWaves : FUSED_TR_ROWS; }
 constexpr int fused_tro_step_bins(int rpw = 1) { return 4 * (64 / (fused_tro_tile_rows(rpw) / 4)); }
 // Which plans have the fused transposed store compiled (the fast-path row-swap 1024-point plan, one row per wave).
 // Round 6: also the 512-point Stockham plan (C1: 1024 samples -> numfftpoints 1024; 16 lanes per row, FOUR rows per wave) --

@@ -48,23 +48,7 @@
 // soffset followed directly by a VALU write of its first data register stores the NEW value in the last four lanes of each
 // 16-lane row when the memory pipeline is busy (the compiler's hazard recogniser only covers the immediate-offset form of
 // this store-data hazard); one wait state cures it, two are used.
-#ifndef FDOCT_TRO_X
-#define FDOCT_TRO_X 0
-#endif
-#ifndef FDOCT_TRO_NOP
-#define FDOCT_TRO_NOP 2
-#endif
-// Cache policy of the write-out stores: 0 = write-back.  The two 64-byte halves of a 128-byte line of the B-scan come from
-// neighbouring tiles, which tro_tile hands to workgroups of the same XCD: with write-back stores they meet in that L2 and
-// leave it as one line.  Measured (C2, M A-scans/s): nt 277, write-back 329, sc1 357-376; with the tile pairing sc1 367-380,
-// write-back 395-406.
-#ifndef FDOCT_TRO_OUT_AUX
-#define FDOCT_TRO_OUT_AUX 0
-#endif
-// 1: the write-out is shared by all (computing) waves of the workgroup; 0: the last wave only writes out (fdoct_kernels.h)
-#ifndef FDOCT_TRO_DW_STEPS
-#define FDOCT_TRO_DW_STEPS 1  // write-out steps a wave may take after putting a row into the ring (1: 400, 2: 392, 4: 385 M A-scans/s)
-#endif
+constexpr int FDOCT_TRO_NOP = 2;
 
 namespace fdoct {
 
@@ -547,23 +531,6 @@ __device__ __forceinline__ float group_sum_f32(float v) {
   }
 }
 
-// Row mean (main:1138) of a fast-path row from the per-lane f32 sums p (every lane holds the same number of samples),
-// as an unevaluated two-float sum mh + ml, without f64 arithmetic.  The lane sums are all close to SPL * mean, and what
-// distinguishes them (the fringes) is small next to that, so a plain f32 reduction would round at the size of the
-// total.  Instead: a first, sloppy reduction gives the average lane sum `base`; the second reduction runs on
-// q = p - base (values and partial sums of fringe size), whose rounding errors are those of any f32 arithmetic on
-// the fringe signal itself.  mean = base / SPL + sum(q) / W; inv_spl and inv_w are exact reciprocals (powers of two
-// on the compiled plans).
-template <int T, bool ONE_EACH>
-__device__ __forceinline__ void group_mean_f32(float p, float inv_t, float inv_spl, float inv_w, float& mh, float& ml) {
-  const float base = group_sum_f32<T, ONE_EACH>(p) * inv_t;
-  const float qs = group_sum_f32<T, ONE_EACH>(p - base);
-  const float m1 = base * inv_spl, m2 = qs * inv_w;
-  mh = m1 + m2;  // two-sum: mh + ml == m1 + m2 exactly
-  const float bb = mh - m1;
-  ml = (m1 - (mh - bb)) + (m2 - bb);
-}
-
 // fma with a half-float second operand (the low / high half of hp), converted inside the instruction: a * f16(hp) + c.
 __device__ __forceinline__ float fma_mix_lo(float a, uint32_t hp, float c) {
   float r;
@@ -619,8 +586,7 @@ __device__ __forceinline__ void load_consts(const float* plane_lane, int c, v2f*
 //   bscandb are asked for, the ring holds bscan and the step takes the logarithm (the same instruction on the same value as
 //   the epilogue would).  The steps are claimed one at a time (compare-and-swap on an LDS counter) by whichever wave passes
 //   a hand-over point: after putting a row into the ring, while waiting for a ring slot, and -- its rows done -- until the
-//   workgroup's last tile is out (FDOCT_TRO_DW = 0 keeps the first form instead: the last wave of the workgroup computes
-//   nothing and writes every tile out; 4-8 % slower).  No workgroup barrier, and nothing of it crosses HBM or L2: per A-scan
+//   workgroup's last tile is out.  No workgroup barrier, and nothing of it crosses HBM or L2: per A-scan
 //   only the camera samples are read and the images written.  The ring is a quarter larger than a tile, so the waves run on
 //   into the next tile while one is written out; a wave waits only when the slot it needs still holds a row of a tile that
 //   has not been written out, and takes write-out steps itself while it waits.  Nobody waits in a cycle: a row is counted
@@ -645,7 +611,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   // 1/background as two floats (fdoct_capi.cpp::reciprocal_words): always on the any-option kernel; the fast path has both
   // instantiations (PRECT: fdoct_set_precise_division)
   constexpr bool PREC = !LEAN || PRECT;
-  // the second word's form on the fast-path kernels with at most 32 samples per lane: a plane of half floats (fdoct_kernels.h)
+  // the second word's form on the fast-path kernels with at most 32 samples per lane: a plane of half floats (fdoct_fused_rules.h)
   constexpr bool IL16 = PRECT && fused_il_half(LEAN, WCH);
   static_assert(!(PRECT && !LEAN), "the any-option kernel always multiplies by both words");
   static_assert(!(PRECT && IB2D && !IL16), "a full-frame background on the fast path: the second word is prefetched as half floats");
@@ -662,13 +628,8 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   // q + 4 needs tile q + 1 written out, which the in-order counters below allow only after tile q), so these only grow and
   // "tile q is complete" is tr_done[q & 3] > q / 4.  tro_publish() turns them into the in-order counter everything else reads.
   __shared__ unsigned int tr_done[4];
-#if FDOCT_TRO_DW != 1
-  __shared__ unsigned int tr_released;    // TRO, write-out by one wave per tile: tiles 0 .. tr_released - 1 are written out
-#endif
-#if FDOCT_TRO_DW == 1
   __shared__ unsigned int tr_ready, tr_wo_next, tr_wo_done;  // TRO, write-out by all waves: complete tiles; next step to claim; steps done (cumulative)
-#endif
-  // TRO with FOUR rows per wave (the 512-point plan, round 6): no ring.  A GROUP of four waves (GW, fdoct_kernels.h) owns a tile of 16 rows; a finished
+  // TRO with FOUR rows per wave (the 512-point plan, round 6): no ring.  A GROUP of four waves (GW, fdoct_fused_rules.h) owns a tile of 16 rows; a finished
   // row is deposited in the wave's OWN row buffer (free between the untangle and the next row's staging), the group meets, writes
   // the tile out together, meets again, and goes on -- all eight waves compute (the ring cost two of them their LDS).
   __shared__ unsigned int grp_tile[4][2];   // the tile a group's leader has claimed, by sequence parity
@@ -686,10 +647,8 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   const int cwl = (a.prec == 1 && STAGE != 2) ? (IL16 ? WC / 2 : WC) : 0;  // floats (the FFT-stage kernel reads no samples); IL16: 2 WC bytes
   v2f* c_tw = reinterpret_cast<v2f*>(c_il + cwl);  // twiddle tables, a.tw_count entries
   // (transposed-store kernels leave out of LDS what they read once into registers, so that the ring of finished rows can be
-  // larger: fdoct_kernels.h, fused_tw3_in_lds / fused_gi_in_lds)
-  // (PF2: the transposed store's samples prefetched two rows ahead -- fdoct_kernels.h, fused_tro_pf2, and the row loop below)
-  constexpr bool PF2 = fused_tro_pf2(KIND, LEAN, STAGE, CPLX, AVG, TRO, IB2D, NORM, (int)sizeof(IN_T));
-  constexpr bool TW3_LDS = fused_tw3_in_lds(KIND, LEAN, STAGE, TRO, IB2D && IL16), GI_LDS = fused_gi_in_lds(KIND, LEAN, STAGE, CPLX, AVG, TRO, PF2);
+  // larger: fdoct_fused_rules.h, fused_tw3_in_lds / fused_gi_in_lds)
+  constexpr bool TW3_LDS = fused_tw3_in_lds(KIND, LEAN, STAGE, TRO, IB2D && IL16), GI_LDS = fused_gi_in_lds(KIND, LEAN, STAGE, CPLX, AVG, TRO);
   const int tw_lds = TW3_LDS ? a.tw_count : (R2 - 1) * R1;   // entries staged: all, or the step-3 table only
   v2f* c_ph = c_tw + tw_lds;                     // [NC] phase (CPLX only)
   uint32_t* c_gi = reinterpret_cast<uint32_t*>(c_ph + (CPLX ? NC : 0));  // [NC] packed gather offsets
@@ -734,14 +693,10 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   }
   constexpr bool TRO_INPLACE = TRO && RPW == 4;
   constexpr unsigned GW = (unsigned)fused_tro_group_waves();   // waves of a group (TRO_INPLACE): a tile is 4 GW rows
-  if (tid == 0) row_ticket = TRO_INPLACE ? (blockDim.x >> 6) / GW : (blockDim.x >> 6) - ((TRO && !FDOCT_TRO_DW) ? 1u : 0u);  // slots 0 .. nwaves-1 are the (computing) waves' first rows (groups' first tiles)
+  if (tid == 0) row_ticket = TRO_INPLACE ? (blockDim.x >> 6) / GW : (blockDim.x >> 6);  // slots 0 .. nwaves-1 are the (computing) waves' first rows (groups' first tiles)
   if (TRO && tid < 4) tr_arrived[tid] = tr_done[tid] = 0u;
   if (TRO_INPLACE && tid < 4) grp_pub[tid] = grp_arrived[tid] = grp_done[tid] = 0u;
-#if FDOCT_TRO_DW == 1
   if (TRO && tid == 0) tr_ready = tr_wo_next = tr_wo_done = 0u;
-#else
-  if (TRO && tid == 0) tr_released = 0u;
-#endif
   // gather table: entry n = ln + T*m is stored at [(m/4)][ln][m%4] so a lane's P entries are P/4
   // b128 reads with a 16-byte lane stride (re-read every row: cheaper than P resident VGPRs)
   if constexpr (GI_LDS) {
@@ -756,16 +711,12 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   // (the last tile of a B-scan may be short).  Wave-uniform, scalar unit.
   constexpr unsigned TR = TRO_INPLACE ? 4u * GW : (unsigned)FUSED_TR_ROWS;
   auto tro_tile = [&](unsigned tq, unsigned& g, unsigned& r0, unsigned& nrows) -> bool {  // false: past the end of the batch
-#ifndef FDOCT_TRO_NO_XCDPAIR
     // workgroups b, b + 8, b + 16 .. run on the same XCD (round-robin dispatch) at about the same time: they get a run of
     // NEIGHBOURING tiles, so that the two 64-byte halves of every 128-byte line of the B-scan meet in one L2 (a
     // performance matter only: any bijection of the workgroups is correct)
     const unsigned nx = gridDim.x >> 3;
     const unsigned bperm = (gridDim.x & 7u) ? blockIdx.x : (blockIdx.x & 7u) * nx + (blockIdx.x >> 3);
     const unsigned gt = tq * gridDim.x + bperm;
-#else
-    const unsigned gt = tq * gridDim.x + blockIdx.x;
-#endif
     if (gt >= a.tr_total_tiles) return false;
     g = __umulhi(gt, a.tr_tpf_magic);  // gt / tiles-per-frame: floor(2^32 / tpf) under-estimates by at most one
     unsigned tf = gt - g * a.tr_tpf;
@@ -796,36 +747,24 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       default: return x % 20u;
     }
   };
-  constexpr int TRO_WRITERS = FDOCT_TRO_DW ? 0 : 1;  // waves of the workgroup that only write out
-  // the ring lies behind the computing waves' row buffers; a slot is D + 4 floats (the pad moves consecutive rows 4 banks apart)
-  float* const tro_ring = reinterpret_cast<float*>(scratch0 + (size_t)((blockDim.x >> 6) - TRO_WRITERS) * RPW * a.scratch_bytes);
+  // the ring lies behind the waves' row buffers; a slot is D + 4 floats (the pad moves consecutive rows 4 banks apart)
+  float* const tro_ring = reinterpret_cast<float*>(scratch0 + (size_t)(blockDim.x >> 6) * RPW * a.scratch_bytes);
   const int tro_slot = a.D + 4;
   // One write-out step: bins s0 .. s0 + SB - 1 of tile tq, all its rows.  Lane (dg, rq) takes rows 4 rq .. 4 rq + 3 and bins
   // 4 dg .. 4 dg + 3: four ds_read_b128 (one per row), four 16-byte stores (one per bin: the lanes of a row-quad group cover
   // TR * 4 contiguous bytes of the B-scan).  When both images are asked for the ring holds bscan and the logarithm is taken
   // here (the same instruction on the same value as the epilogue's).
   constexpr int TRO_RQ = TR / 4, TRO_DGN = 64 / TRO_RQ, TRO_SB = 4 * TRO_DGN;
-  // PF2: store INSTRUCTIONS this wave has issued since its last wait for samples (wave-uniform; an instruction counts whatever
-  // its lanes' masks): the wait names how many younger operations may still be outstanding
-  [[maybe_unused]] unsigned pf2_stores = 0u;
   auto tro_step = [&](unsigned tq, unsigned g, unsigned r0, unsigned nrows, int s0) {
-    if constexpr (PF2) pf2_stores += (a.out_mag && a.out_db) ? 8u : 4u;
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
     typedef float f4 __attribute__((ext_vector_type(4)));
     const int rq = lane % TRO_RQ, dg = lane / TRO_RQ;
     const int Dn = a.D, Hn = a.H;
-#if FDOCT_TRO_X == 2   // measurement builds (tools/tro_cost_probe.sh): 2 = no write-out work at all, 1 = the LDS reads without the stores
-    return;
-#endif
     if (4 * rq >= (int)nrows) return;
     const bool both = a.out_mag && a.out_db;
     const bool mask = both && a.dcmask && Dn > 4;  // dB bins 0, 1 <- bin 4 (main:1237-1238); alone, dB arrives masked
     float* const out0 = a.out_mag ? a.out_mag : a.out_db;
-#if FDOCT_TRO_X == 3   // measurement build: every tile's stores land in the same 64 KB (16 "rows" per depth bin): same instruction
-    const int Hs = 16;  // stream, L2-resident targets -- do the waves wait for the stores' COMPLETION (EXPERIMENTS.md section 5)?  Results are wrong.
-#else
     const int Hs = Hn;
-#endif
     const int vout = (4 * dg * Hs + 4 * rq) * 4;
     const float* rowp[4];
     if constexpr (TRO_INPLACE) {
@@ -842,23 +781,19 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         rowp[i] = tro_ring + sl * tro_slot + 4 * dg + s0;
       }
     }
-#if FDOCT_TRO_X == 3
-    const size_t goff = 0;
-#else
     const size_t goff = ((size_t)g * Dn) * Hn + r0;
-#endif
     __amdgpu_buffer_rsrc_t rout0 = __builtin_amdgcn_make_buffer_rsrc(out0 + goff, 0, 0x7ffffff0, 0x00020000);
     f4 v[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) v[i] = *reinterpret_cast<const f4*>(rowp[i]);
+    // Cache policy of the stores (the last argument): 0 = write-back.  The two 64-byte halves of a 128-byte line of the B-scan
+    // come from neighbouring tiles, which tro_tile hands to workgroups of the same XCD: with write-back stores they meet in that
+    // L2 and leave it as one line.  Measured (C2, M A-scans/s): nt 277, write-back 329, sc1 357-376; with the tile pairing sc1
+    // 367-380, write-back 395-406.
 #pragma unroll
     for (int bb = 0; bb < 4; bb++) {
       const f4 w = {v[0][bb], v[1][bb], v[2][bb], v[3][bb]};
-#if FDOCT_TRO_X == 1
-      asm volatile("" ::"v"(w));
-      if (Dn < 0)
-#endif
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, w), rout0, vout, ((s0 + bb) * Hs) * 4, FDOCT_TRO_OUT_AUX);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, w), rout0, vout, ((s0 + bb) * Hs) * 4, 0);
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("s_nop %0" ::"n"(FDOCT_TRO_NOP - 1));
       __builtin_amdgcn_sched_barrier(0);
@@ -876,15 +811,14 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         if (mask && bb < 2 && s0 == 0 && dg == 0) w = v4;
 #pragma unroll
         for (int k = 0; k < 4; k++) w[k] = a.db_scale * fast_log2(w[k]);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, w), rout1, vout, ((s0 + bb) * Hs) * 4, FDOCT_TRO_OUT_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, w), rout1, vout, ((s0 + bb) * Hs) * 4, 0);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_nop %0" ::"n"(FDOCT_TRO_NOP - 1));
         __builtin_amdgcn_sched_barrier(0);
       }
     }
   };
-#if FDOCT_TRO_DW != 0
-  // Tile tq of this workgroup has just completed (FDOCT_TRO_DW = 1: all its rows are in the ring; 2: it is written out).
+  // Tile tq of this workgroup has just completed (all its rows are in the ring).
   // Tiles need not complete in order (see tr_done), but everything that waits or claims counts tiles IN ORDER: the tile is
   // counted in tr_done, then the in-order counter *inorder is advanced over every tile that is complete by now -- by this
   // wave or by whichever wave's compare-and-swap wins; a wave that completes tile q + 1 before tile q leaves the counter
@@ -911,17 +845,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     }
     return r;
   };
-#endif
-#if FDOCT_TRO_DW == 2
-  // Write-out by the wave whose row completes the tile: all SPT steps in one go, the LDS reads of a step issued ahead of the
-  // stores of the step before it.  tr_released counts the tiles written out, in order (tro_publish).
-  auto tro_tile_out = [&](unsigned tq, unsigned g, unsigned r0, unsigned nrows) {
-    for (int s0 = 0; s0 < a.D; s0 += TRO_SB) tro_step(tq, g, r0, nrows, s0);
-    asm volatile("" ::: "memory");  // every LDS read has returned (its data fed a store that has been issued)
-    (void)tro_publish(tq, &tr_released);
-  };
-  unsigned tro_rel_seen = 0u;  // tiles written out, as last read (the counter only grows: a valid lower bound)
-#elif FDOCT_TRO_DW == 1
   // Distributed write-out: no wave is set aside.  The wave whose row completes a tile publishes it (tr_ready counts the
   // complete tiles IN ORDER, tro_publish: tile q's steps exist once tiles 0 .. q are all complete); its SPT = D / SB steps are
   // then claimed one at a time (compare-and-swap on tr_wo_next, so a step is never claimed before it exists) by whichever
@@ -959,38 +882,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     return did;
   };
   unsigned tro_done_seen = 0u;  // steps written out, as last read (the counter only grows: a valid lower bound)
-#else  // FDOCT_TRO_DW == 0
-  if constexpr (TRO) {
-    // The LAST wave of the workgroup is the write-out wave: it computes nothing.
-    if (wave == (int)(blockDim.x >> 6) - 1) {
-      for (unsigned tq = 0;; tq++) {
-        unsigned g, r0, nrows;
-        if (!tro_tile(tq, g, r0, nrows)) break;
-        // every row of the tile in the ring?  (The rows arrive whatever this wave does; the bound is the exit condition a
-        // spinning wave must have all the same -- about half a second -- and is reported through a.tr_fault.)
-        for (unsigned spin = 0;; spin++) {
-          const unsigned have = (unsigned)__builtin_amdgcn_readfirstlane(
-              (int)__hip_atomic_load(&tr_arrived[tq & 3u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-          if (have >= nrows) break;
-          if (spin >= FDOCT_TRO_SPIN_LIMIT) {
-            if (lane == 0) __hip_atomic_store(a.tr_fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-        asm volatile("" ::: "memory");
-        for (int s0 = 0; s0 < a.D; s0 += TRO_SB) tro_step(tq, g, r0, nrows, s0);
-        // every LDS read above has returned (its data fed a store that has been issued): the slots may be overwritten
-        asm volatile("" ::: "memory");
-        if (lane == 0) {
-          __hip_atomic_store(&tr_arrived[tq & 3u], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_store(&tr_released, tq + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      }
-      return;
-    }
-  }
-#endif
 
   unsigned char* scr = scratch0 + (size_t)(wave * RPW + sub) * a.scratch_bytes;
   float* stg = reinterpret_cast<float*>(scr);
@@ -1010,11 +901,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   // SIMD, 256 VGPRs), which removes half of the LDS traffic per row.  Every other instantiation re-reads
   // them from LDS each row.
   constexpr bool RES = fused_resident_consts(KIND, LEAN, AVG, WCH, STAGE);
-#ifdef FDOCT_X_NO_GRES
-  constexpr bool GRES = false;
-#else
-  constexpr bool GRES = LEAN && STAGE != 2 && KIND == 1 && !CPLX && !AVG && !PF2;  // (with averaging the accumulators need those registers; PF2: the second sample set does)
-#endif
+  constexpr bool GRES = LEAN && STAGE != 2 && KIND == 1 && !CPLX && !AVG;  // (with averaging the accumulators need those registers)
   uint32_t gaddr[GRES ? 2 * P : 1];
   if constexpr (GRES) {  // 2 LDS byte addresses per FFT point
     const uint4* gl4 = reinterpret_cast<const uint4*>(c_gi) + l;
@@ -1035,28 +922,14 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     }
   }
 
-#ifdef FDOCT_X_NO_RESTW
-  constexpr bool RESTW = false;
-#else
   constexpr bool RESTW = LEAN && KIND == 1 && STAGE != 1;
-#endif
-  constexpr bool ILDMA_ = IB2D && IL16 && !TRO && FDOCT_IL16_DMA;  // (= ILDMA, defined with the prefetch buffers below)
-#ifdef FDOCT_X_RES_T3_ONLY  // tuning: only the 15 step-5 twiddles stay in registers
-  constexpr int RES2 = 0;
-  constexpr bool RES3 = LEAN && KIND == 1 && STAGE != 1;
-#else
-#ifdef FDOCT_TRO_RES2  // tuning: keep the step-3 twiddles resident in the transposed-store variant too (spills 7 registers)
-  constexpr int RES2 = RESTW ? 12 : 0;
-  constexpr bool RES3 = RESTW;
-#else
+  constexpr bool ILDMA_ = IB2D && IL16 && !TRO;  // (= ILDMA, defined with the prefetch buffers below)
   // (the transposed-store variant, and every variant that multiplies by both words of the reciprocal background, is a
   // few registers over the budget with everything resident: their 12 step-3 twiddles come from LDS every row)
   constexpr int RES2 = !RESTW ? 0 : (TRO ? 0 : (PREC ? (IL16 ? ((IB2D && !ILDMA_) ? FDOCT_PREC16_T2_IB2D : (ILDMA_ ? FDOCT_PREC16_T2_DMA : FDOCT_PREC16_T2)) : FDOCT_PREC_T2) : 12));
   // (the transposed store with a full-frame background and both words holds 48 prefetch registers: its step-5 twiddles come
   // from LDS too, or the row loop spills)
-  constexpr bool RES3 = RESTW && !(TRO && IB2D && IL16 && !FDOCT_TRO_IB2D_RES3);
-#endif
-#endif
+  constexpr bool RES3 = RESTW && !(TRO && IB2D && IL16);
   v2f r_t2[RES2 ? RES2 : 1], r_t3[RES3 ? 15 : 1];
   if constexpr (RES2 > 0 || RES3) {
     v2f t2tmp[12], t3tmp[15];
@@ -1090,14 +963,14 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   // IB2D + both words: the half-float pattern of the same background row is prefetched with it -- into a per-wave LDS slot by
   // the global -> LDS loads of gfx950 (global_load_lds_dwordx4: no registers held through the transform; ILDMA), or, where the
   // LDS belongs to the ring of the transposed store, into 16 registers
-  constexpr bool ILDMA = IB2D && IL16 && !TRO && FDOCT_IL16_DMA;
+  constexpr bool ILDMA = IB2D && IL16 && !TRO;
   uint4 r_il16[(IB2D && IL16 && !ILDMA) ? WCH : 1];
   // (the slots lie behind the waves' row buffers: 2 WC bytes each)
   unsigned char* const il_dma = scratch0 + (size_t)(blockDim.x >> 6) * RPW * a.scratch_bytes + (size_t)wave * (2 * WC);
   // The averaging fast-path kernels with more than 32 samples per lane (C4): the half-float pattern of the second word stays
   // RESIDENT -- 4 registers per chunk, loaded once per wave (the kernel has them to spare since the low words' source became a
   // compile-time property) -- instead of sixteen 16-byte loads of the float low words per input A-scan from the global plane.
-  constexpr bool IL16R = LEAN && PRECT && fused_il_global(LEAN, AVG, WCH, T) && FDOCT_IL16_RESIDENT && STAGE != 2;
+  constexpr bool IL16R = LEAN && PRECT && fused_il_global(LEAN, AVG, WCH, T) && STAGE != 2;
   uint4 r_il16r[IL16R ? WCH : 1];
   if constexpr (IL16R) {
     const uint4* h4 = reinterpret_cast<const uint4*>(a.il16) + l;
@@ -1289,50 +1162,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   const int c0l = 4 * l;  // this lane's slot inside a constant plane (see the staging loop above)
 
   RawChunk<IN_T> raw[WCH];
-  // PF2 (fdoct_kernels.h, fused_tro_pf2): TWO sets of sample registers.  Row r's samples live in set r & 1; they are asked for
-  // in the middle of row r - 2 -- into the set row r - 2 unpacked at its top -- by loads the COMPILER DOES NOT TRACK (inline asm),
-  // because the wait they need is one it cannot express: in front of row r - 1's write-out, for the samples of row r only, with
-  // the stores of row r - 2's write-out and the loads of row r + 1 -- all younger -- still outstanding: s_waitcnt vmcnt(N) with
-  // N = the number of those younger instructions, counted as they are issued (pf2_stores + WCH; a smaller N is always safe).
-  // A wave's vector-memory operations return in order: with N exact, the wait covers the stores issued TWO rows ago and older,
-  // which have had 10 us to be acknowledged (EXPERIMENTS.md section 5), instead of one row's 5 us.
-  typedef unsigned pf2_u4 __attribute__((ext_vector_type(4)));
-  [[maybe_unused]] pf2_u4 pf2_s0[PF2 ? WCH : 1], pf2_s1[PF2 ? WCH : 1];
-  [[maybe_unused]] bool pf2_ph = false;   // the set the CURRENT row's samples were unpacked from (wave-uniform)
-  // One asm statement per set, executed on EVERY row with the branch INSIDE it: a conditional around an asm that writes the set
-  // makes the register allocator merge two versions of the set behind it -- with copies of registers whose loads are in flight
-  // (seen in the first build: v_mov of the whole set right behind the loads).  `skip` != 0: the statement does nothing.
-  auto pf2_load = [&](pf2_u4* set, const void* row, unsigned skip) {
-    static_assert(!PF2 || (T == 64 && WCH == 4 && sizeof(IN_T) == 2), "PF2: 16 bytes per lane and chunk, four chunks 1 KB apart");
-    const unsigned voff = 16u * (unsigned)l;
-    constexpr int C1 = WCH > 1 ? 1 : 0, C2 = WCH > 2 ? 2 : 0, C3 = WCH > 3 ? 3 : 0;
-    asm volatile(
-        "s_cmp_lg_u32 %[skip], 0\n\t"
-        "s_cbranch_scc1 .Lpf2_skip_%=\n\t"
-        "global_load_dwordx4 %[a], %[off], %[base] nt\n\t"
-        "global_load_dwordx4 %[b], %[off], %[base] offset:1024 nt\n\t"
-        "global_load_dwordx4 %[c], %[off], %[base] offset:2048 nt\n\t"
-        "global_load_dwordx4 %[d], %[off], %[base] offset:3072 nt\n"
-        ".Lpf2_skip_%=:"
-        : [a] "+v"(set[0]), [b] "+v"(set[C1]), [c] "+v"(set[C2]), [d] "+v"(set[C3])
-        : [off] "v"(voff), [base] "s"(row), [skip] "s"(skip)
-        : "scc");
-  };
-  // wait until at most n of this wave's vector-memory operations are outstanding (n wave-uniform; the ladder rounds it DOWN)
-  auto pf2_wait = [&](unsigned n) {
-    if (n >= 36u) asm volatile("s_waitcnt vmcnt(36)");
-    else if (n >= 28u) asm volatile("s_waitcnt vmcnt(28)");
-    else if (n >= 20u) asm volatile("s_waitcnt vmcnt(20)");
-    else if (n >= 16u) asm volatile("s_waitcnt vmcnt(16)");
-    else if (n >= 12u) asm volatile("s_waitcnt vmcnt(12)");
-    else if (n >= 8u) asm volatile("s_waitcnt vmcnt(8)");
-    else if (n >= 4u) asm volatile("s_waitcnt vmcnt(4)");
-    else asm volatile("s_waitcnt vmcnt(0)");
-  };
-  auto pf2_pin = [&](pf2_u4* set) {   // (the registers of a set that has landed: nothing that reads them moves above this)
-#pragma unroll
-    for (int c = 0; c < (PF2 ? WCH : 1); c++) asm volatile("" : "+v"(set[c]));
-  };
   auto issue_loads = [&](long long o, int avg_i) {
     const bool valid = o < total;
     long long in_row = valid ? o : 0;
@@ -1343,12 +1172,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       }
     }
     const void* row = frames + uni64(in_row) * a.pitch_bytes;
-    if constexpr (PF2) {   // into the set the current row has unpacked (its loop-top copy is done)
-      const unsigned into1 = (unsigned)__builtin_amdgcn_readfirstlane(pf2_ph ? 1 : 0);
-      pf2_load(pf2_s0, row, into1);
-      pf2_load(pf2_s1, row, into1 ^ 1u);
-      return;
-    }
 #pragma unroll
     for (int c = 0; c < WCH; c++) {
       const int i0 = i0l + 8 * T * c;
@@ -1389,8 +1212,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   static_assert(!IL16 || ILX, "half-float second word: the kernels that read the row's low words at its top");
   v2f ilx[(ILX && !IL16) ? NPR : 1];
   uint4 ilh[IL16 ? WCH : 1];  // IL16: chunk c's four half-float pairs (pair q = dword q), 16 registers instead of 32
-  [[maybe_unused]] long long pf2_o1 = total, pf2_o2 = total;   // PF2: the rows after the current one (tro_next, tro_n2)
-  [[maybe_unused]] TroRow tro_n2{};
   if (o_wave < total) {
     // (the first row like every later one: the full-frame background's rows -- and the global -> LDS load of its half-float
     // pattern -- are issued BEFORE the samples, so that a wait for the samples covers them: loads return in order)
@@ -1400,15 +1221,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     else
       issue_loads(o_wave + sub, 0);
     frame_scale(o_wave + sub, 0);
-    if constexpr (PF2) {   // the wave's second row, into the other set; both have landed before the loop
-      pf2_o1 = tro_take(ticket_value(claim()), tro_next);
-      pf2_ph = true;
-      issue_loads(pf2_o1 + sub, 0);
-      pf2_ph = false;
-      asm volatile("s_waitcnt vmcnt(0)");
-      pf2_pin(pf2_s0);
-      pf2_pin(pf2_s1);
-    }
   }
 
 
@@ -1477,15 +1289,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         for (int c = 0; c < WCH; c++) load_consts<T>(c_il + c0l, c, ilx + 4 * c);
       }
       v2f v[NPR];  // sample pairs: v[4c+q] = samples 8*(l+T*c) + chunk_pair_offset(q), +2
-      if constexpr (PF2) {   // this row's samples: landed before the previous row's write-out (the wait in front of it)
-        if constexpr (sizeof(IN_T) == 2) {
-#pragma unroll
-          for (int c = 0; c < WCH; c++) {
-            const pf2_u4 t = pf2_ph ? pf2_s1[c] : pf2_s0[c];
-            raw[c].v = make_uint4(t.x, t.y, t.z, t.w);
-          }
-        }
-      }
 #pragma unroll
       for (int c = 0; c < WCH; c++) raw[c].unpack(v + 4 * c);
       // Fast-path normalisations.  With the two-word division (PREC) the normalised sample p = (v - min) * scale is carried as two
@@ -1589,7 +1392,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         }
         // fast path with at most 32 samples per lane: 1/background stays in registers through the sum and the
         // subtraction (resident, or read once from the LDS plane), so x is never formed -- the row sum is accumulated
-        // by fma (four chains), t = fma(v, 1/yb, -mh) - ml rounds once, and the mean needs no f64 (group_mean_f32)
+        // by fma (four chains), t = fma(v, 1/yb, -mh) - ml rounds once, and the mean needs no f64
         constexpr bool FMAX = LEAN && WCH <= 4;
         if constexpr (FMAX) {
           if constexpr (RESC) {
@@ -1601,16 +1404,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
 #pragma unroll
             for (int c = 0; c < WCH; c++) load_consts<T>(c_win + c0l, c, av + 4 * c);
           }
-#ifdef FDOCT_X_OLD_MEAN  // tuning: round 2's form (lane sums of the DC-sized products, two-float mean)
-          v2f s4[4] = {mk(0.f, 0.f), mk(0.f, 0.f), mk(0.f, 0.f), mk(0.f, 0.f)};
-#pragma unroll
-          for (int c = 0; c < WCH; c++) {
-#pragma unroll
-            for (int p = 0; p < 4; p++) s4[p] = pk_fma(v[4 * c + p], ibv[4 * c + p], s4[p]);
-          }
-          const v2f part = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-          group_mean_f32<T, TRIM>(part.x + part.y, 1.f / (float)T, 1.f / (float)(8 * WCH), 1.f / (float)WC, mh, ml);
-#else
           // Row mean without any DC-sized sum: c0, the average of one x = v / yb per lane, is a wave-uniform estimate
           // of the mean; d = fma(v, 1/yb, -c0) is the exact product minus c0 rounded at the size of the DEVIATION from it
           // (fringes, residual envelope), so are the sums of d, and x - mean = d - mean(d).  Same operation count as summing
@@ -1668,7 +1461,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
           }
           const v2f part = (s4[0] + s4[1]) + (s4[2] + s4[3]);
           mh = group_sum_f32<T, TRIM>(part.x + part.y) * (1.f / (float)WC);  // mean of d (W == WC on this path)
-#endif
           if constexpr (RESC) {
 #pragma unroll
             for (int i = 0; i < NPR; i++) {
@@ -1679,13 +1471,8 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
 #pragma unroll
             for (int c = 0; c < WCH; c++) load_consts<T>(c_g + c0l, c, bv + 4 * c);
           }
-#ifdef FDOCT_X_OLD_MEAN
-#pragma unroll
-          for (int i = 0; i < NPR; i++) v[i] = pk_fma(v[i], ibv[i], mk(-mh, -mh)) - mk(ml, ml);
-#else
 #pragma unroll
           for (int i = 0; i < NPR; i++) v[i] -= mk(mh, mh);
-#endif
         } else {
           // WCH <= 4: all reciprocal-background reads are issued up front (one LDS wait); wider rows read
           // them chunk by chunk to stay inside the register budget
@@ -1694,11 +1481,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             for (int c = 0; c < WCH; c++) load_consts<T>(c_ib + c0l, c, ibv + 4 * c);
           }
           double sum = 0.0;
-#ifndef FDOCT_X_OLD_MEAN
           constexpr bool CMEAN = LEAN;  // the fast-path rows that are too wide for the block above (C4, C1): the same mean, see there
-#else
-          constexpr bool CMEAN = false;
-#endif
           float c0 = 0.f;
           [[maybe_unused]] bool have_c0 = false;
           v2f s4[4] = {mk(0.f, 0.f), mk(0.f, 0.f), mk(0.f, 0.f), mk(0.f, 0.f)};
@@ -1906,16 +1689,13 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         int na = ai + 1;
         if (na == A) {
           na = 0;
-          if constexpr (PF2) {   // the row after next; the next one's samples have been on their way since the previous row
-            pf2_o2 = tro_take(ticket_value(ticket), tro_n2);
-            o_next = pf2_o1;
-          } else if constexpr (TRO_INPLACE)
+          if constexpr (TRO_INPLACE)
             o_next = grp_rows(grp_next_tile(ticket), tro_next);
           else if constexpr (TRO)
             o_next = tro_take(ticket_value(ticket), tro_next);
           else
             o_next = slot_row(ticket_value(ticket));
-          no = (PF2 ? pf2_o2 : o_next) + sub;
+          no = o_next + sub;
           issue_ib2d(no);  // r_ib was consumed at the top of this pass
         }
         issue_loads(no, na);
@@ -2077,17 +1857,8 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
 #pragma unroll
         for (int m = 0; m < P; m++) asm volatile("" : "+v"(znext[m]));
       } else {
-        if constexpr (PF2) {
-          // the NEXT row's samples (the other set), asked for a row and a half ago: younger than they are the write-out stores this
-          // wave has issued since the last wait here and the loads of the row after next
-          pf2_wait(pf2_stores + (unsigned)WCH);
-          pf2_stores = 0u;
-          pf2_pin(pf2_s0);   // (both sets, unconditionally: see pf2_load)
-          pf2_pin(pf2_s1);
-        } else {
 #pragma unroll
-          for (int c = 0; c < WCH; c++) raw[c].pin();
-        }
+        for (int c = 0; c < WCH; c++) raw[c].pin();
         if constexpr (IB2D) {
 #pragma unroll
           for (int i = 0; i < NPR; i++) asm volatile("" : "+v"(r_ib[i]));
@@ -2106,19 +1877,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     if constexpr (TRO && !TRO_INPLACE) {
       // the ring slot of this row (ticket mod RS) last held the row of ticket - RS: its tile must have been written out
       const unsigned need = tro_cur.t >= RS ? (tro_cur.t - RS) / TR + 1u : 0u;
-#if FDOCT_TRO_DW == 2
-      // (the write-out this waits for is done by the wave that completes that tile, at once and without a wait of its own;
-      // the bound is the exit condition a spinning wave must have all the same and is reported through a.tr_fault)
-      for (unsigned spin = 0; tro_rel_seen < need; spin++) {
-        tro_rel_seen = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&tr_released, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        if (tro_rel_seen >= need) break;
-        if (spin >= FDOCT_TRO_SPIN_LIMIT) {
-          if (lane == 0) __hip_atomic_store(a.tr_fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-#elif FDOCT_TRO_DW == 1
       const unsigned need_steps = need * ((unsigned)a.D / (unsigned)TRO_SB);
       // (the write-out this waits for may be this wave's own to do; the bound is the exit condition a spinning wave must
       // have all the same and is reported through a.tr_fault)
@@ -2131,23 +1889,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         }
         if (!tro_writeout(1)) __builtin_amdgcn_s_sleep(2);
       }
-#else
-      if (need) {
-        unsigned seen = (unsigned)__builtin_amdgcn_readfirstlane(
-            (int)__hip_atomic_load(&tr_released, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        // (the write-out this waits for depends on no wait of its own; the bound is the exit condition a spinning wave must
-        // have all the same and is reported through a.tr_fault)
-        for (unsigned spin = 0; seen < need; spin++) {
-          if (spin >= FDOCT_TRO_SPIN_LIMIT) {
-            if (lane == 0) __hip_atomic_store(a.tr_fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            break;
-          }
-          __builtin_amdgcn_s_sleep(2);
-          seen = (unsigned)__builtin_amdgcn_readfirstlane(
-              (int)__hip_atomic_load(&tr_released, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        }
-      }
-#endif
     }
     // ---------------- A9/A10: average, epsilon, dB, DC mask, store
     const int D = a.D;
@@ -2184,24 +1925,9 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     // 64-bit VGPR address (+1.6 % on C2: fewer address registers read per store).  num_records = the floats of the
     // wave's valid rows: the hardware drops the rows past the end of the batch and, with one row per wave, whatever lies
     // past the crop.
-    float* const stg_row = stg;  // (FDOCT_X_LDS_STORE) the wave's own LDS buffer, free between the untangle and the next row's staging
     auto store_row = [&](float* obase, const float* val) {
       constexpr int NLO = CPLX ? P : P / 2;
-#ifdef FDOCT_X_PLAIN_STORE  // tuning: ordinary (write-back) global stores
-      constexpr bool BUF = false;
-      auto stg = [](float* p, float v) { *p = v; };
-#elif defined(FDOCT_X_GLOBAL_STORE)  // tuning: non-temporal global stores
-      constexpr bool BUF = false;
-      auto stg = [](float* p, float v) { __builtin_nontemporal_store(v, p); };
-#else
-#ifdef FDOCT_X_LDS_STORE  // tuning experiment: the row goes through the wave's own (free) LDS buffer and leaves as 16-byte stores
-      constexpr bool LSX = LEAN && KIND == 1 && !TRO && RPW == 1;
-#else
-      constexpr bool LSX = false;
-#endif
-      constexpr bool BUF = !TRO && !LSX;
-      auto stg = [](float* p, float v) { __builtin_nontemporal_store(v, p); };
-#endif
+      constexpr bool BUF = !TRO;  // (the transposed store's rows go into LDS: plain ds_write_b32)
       // o_wave is wave-uniform by construction (slot_row of a wave-uniform ticket); say so for RPW > 1 too, or the
       // descriptor would be built per lane and the stores wrapped in a waterfall loop
       const long long ow = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(o_wave >> 32)) << 32) |
@@ -2216,8 +1942,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         orow = reinterpret_cast<float*>(scratch0 + (size_t)(wave * RPW + sub) * a.scratch_bytes);   // the row's own buffer, free since the untangle
       else if constexpr (TRO)
         orow = tro_ring + (ring_mod(tro_cur.t) + (unsigned)sub) * tro_slot;
-      float* const grow = orow;  // (LSX) where the row goes in global memory
-      if constexpr (LSX) orow = stg_row;
       __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(BUF ? wbase : nullptr, 0, BUF ? nrows * D * 4 : 0, 0x00020000);
       // bin index -> store; lo(m) = bin l + T*m, hi(m) = bin NC - l - T*m, hi0 = slot P/2 (lane 0: bin NC/2)
       float* plo = orow + l;
@@ -2230,26 +1954,20 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       auto st_lo = [&](int m, float v) {
         if constexpr (BUF)
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, vlo + 4 * T * m, 0, 2);  // aux 2 = nt
-        else if constexpr (TRO || LSX)
-          plo[T * m] = v;
         else
-          stg(plo + T * m, v);
+          plo[T * m] = v;
       };
       auto st_hi = [&](int m, float v) {
         if constexpr (BUF)
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, vhi + 4 * T * (P / 2 - 1 - m), 0, 2);
-        else if constexpr (TRO || LSX)
-          phi[-T * m] = v;
         else
-          stg(phi - T * m, v);
+          phi[-T * m] = v;
       };
       auto st_hi0 = [&](float v) {  // slot P/2 of lane 0 is bin NC/2
         if constexpr (BUF)
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, vrow + 4 * ((l == 0) ? NC / 2 : NC - l), 0, 2);
-        else if constexpr (TRO || LSX)
-          *((l == 0) ? orow + NC / 2 : phi) = v;
         else
-          stg((l == 0) ? orow + NC / 2 : phi, v);
+          *((l == 0) ? orow + NC / 2 : phi) = v;
       };
       if (D == NC || (BUF && RPW == 1 && (D % T) != 0)) {  // full depth: nothing to crop; ragged crop of a wave-per-row plan: the hardware drops bins >= D
 #pragma unroll
@@ -2289,21 +2007,10 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             if (NC - l - T * m < D) st_hi(m, val[NLO + m]);
         }
       }
-      if constexpr (LSX) {
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        wave_lds_sync();
-        const int nq = D >> 8;  // 256 bins per instruction (D a multiple of 256 here: host)
-        for (int k = 0; k < nq; k++) {
-          const f4 v = *reinterpret_cast<const f4*>(orow + 4 * l + 256 * k);
-          __builtin_nontemporal_store(v, reinterpret_cast<f4*>(grow + 4 * l + 256 * k));
-        }
-        asm volatile("s_nop 1");
-        wave_lds_sync();
-      }
     };
     const bool deposit = valid && !(TRO_INPLACE && tro_cur.dummy);   // (a wave without rows in a short tile stores nothing)
     if (deposit && a.out_mag && !FDOCT_ABL(128)) store_row(a.out_mag, outv);
-    // (transposed store with both images asked for: the ring holds bscan, the write-out wave takes the logarithm)
+    // (transposed store with both images asked for: the ring holds bscan, the write-out step takes the logarithm)
     if (a.out_db && !(TRO && a.out_mag)) {
       float db[P];
 #pragma unroll
@@ -2344,13 +2051,8 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       grp_seq++;
       tro_cur = tro_next;
     } else if constexpr (TRO) {
-      // the row is in the ring (a wave's LDS operations execute in order): count it for the write-out wave
+      // the row is in the ring (a wave's LDS operations execute in order): count it for the write-out
       wave_lds_sync();
-#if FDOCT_TRO_DW == 2
-      unsigned cnt = 0u;
-      if (lane == 0) cnt = __hip_atomic_fetch_add(&tr_arrived[tro_cur.tq & 3u], (unsigned)RPW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if ((unsigned)__builtin_amdgcn_readfirstlane((int)cnt) + (unsigned)RPW == tro_cur.nrows) tro_tile_out(tro_cur.tq, tro_cur.g, tro_cur.r0, tro_cur.nrows);
-#elif FDOCT_TRO_DW == 1
       // count the row, and read the write-out state in the same LDS round trip
       unsigned cnt = 0u;
       if (lane == 0) cnt = __hip_atomic_fetch_add(&tr_arrived[tro_cur.tq & 3u], (unsigned)RPW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2359,19 +2061,11 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       unsigned ready = (unsigned)__builtin_amdgcn_readfirstlane((int)r_l);
       if ((unsigned)__builtin_amdgcn_readfirstlane((int)cnt) + (unsigned)RPW == tro_cur.nrows)  // the tile is complete: publish it
         ready = tro_publish(tro_cur.tq, &tr_ready);
-      if (tro_try_step((unsigned)__builtin_amdgcn_readfirstlane((int)s_l), ready) && FDOCT_TRO_DW_STEPS > 1) (void)tro_writeout(FDOCT_TRO_DW_STEPS - 1);
-#else
-      if (lane == 0) __hip_atomic_fetch_add(&tr_arrived[tro_cur.tq & 3u], (unsigned)RPW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
+      // (one write-out step per row put into the ring: 400 M A-scans/s on C2 against 392 with two and 385 with four)
+      (void)tro_try_step((unsigned)__builtin_amdgcn_readfirstlane((int)s_l), ready);
       tro_cur = tro_next;
-      if constexpr (PF2) {
-        tro_next = tro_n2;
-        pf2_o1 = pf2_o2;
-        pf2_ph = !pf2_ph;
-      }
     }
   }
-#if FDOCT_TRO_DW == 1
   if constexpr (TRO && !TRO_INPLACE) {
     // all rows of this wave are done: help until the workgroup's last tile is out (it completes when its last row is in the
     // ring, which needs no help from here; the bound is the exit condition a spinning wave must have all the same)
@@ -2392,7 +2086,6 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       __builtin_amdgcn_s_sleep(2);
     }
   }
-#endif
 #ifdef FDOCT_FUSED_PROBE
   if (a.phase_probe && lane == 0 && blockIdx.x < 4 && wave < 16) {
     for (int i = 0; i < FUSED_PROBE_PHASES; i++) a.phase_probe[(blockIdx.x * 16 + wave) * FUSED_PROBE_PHASES + i] = pr.acc[i];

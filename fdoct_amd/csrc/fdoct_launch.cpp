@@ -26,8 +26,7 @@ static size_t tro_const_lds_bytes(const Plan& pl, const FusedLaunchInputs& in) {
   const bool planes = !fused_resident_consts(p.kind, true, in.A > 1, p.WCH, 0);
   const bool il_plane = both && !ib2d && !fused_il_global(true, in.A > 1, p.WCH, p.T);
   return const_lds_bytes(pl, planes, il_plane, half, fused_tw3_in_lds(p.kind, true, 0, true, ib2d && both && half),
-                         fused_gi_in_lds(p.kind, true, 0, false, in.A > 1, true,
-                                         fused_tro_pf2(p.kind, true, 0, false, in.A > 1, true, ib2d, in.minmax ? 1 : 0, in.kdt == FDOCT_K_U8 ? 1 : 2)));
+                         fused_gi_in_lds(p.kind, true, 0, false, in.A > 1, true));
 }
 
 // Can the chain write the reference's D x H layout itself (fused_kernel's TRO instantiations), as far as handle and geometry say?
@@ -51,17 +50,16 @@ static bool tro_configured(const Plan& pl, const FusedLaunchInputs& in) {
 }
 
 // The transposed store's launch (block, LDS, grid, ring and tiles into *l), or none where no group of waves / no ring fits the
-// LDS: computing waves + the write-out wave; LDS: constants, one row buffer per computing wave, the ring of finished rows.  As
-// many computing waves as the register budget allows, then the largest ring that fits (round 5: the store is bound by how much
+// LDS, which holds the constants, one row buffer per wave and the ring of finished rows (every wave computes; they share the write-out).  As
+// many waves as the register budget allows, then the largest ring that fits (round 5: the store is bound by how much
 // of the next tile fits into the ring while a tile drains, so the kernel keeps its once-read tables out of LDS); a wave is given
 // up only where not even the smallest ring fits next to them.
 static void tro_launch(const Plan& pl, const FusedLaunchInputs& in, int max_waves, size_t lds_max, FusedLaunch* l) {
   const FusedPlan& p = *pl.fused;
   const int rpw = 64 / p.T;
   const size_t tro_const = tro_const_lds_bytes(pl, in), per_wave = (size_t)pl.scratch_bytes * rpw;
-  const int ww = fused_tro_writer_waves();
-  int cw = max_waves - ww;
-  if (in.block_override && in.block_override / 64 - ww >= 1 && in.block_override / 64 - ww < cw) cw = in.block_override / 64 - ww;
+  int cw = max_waves;
+  if (in.block_override && in.block_override / 64 >= 1 && in.block_override / 64 < cw) cw = in.block_override / 64;
   FusedTroLaunch t;
   if (rpw == 4) {
     // whole groups of four waves, as many as registers and LDS allow; no ring (the rows wait in the waves' own buffers)
@@ -77,7 +75,7 @@ static void tro_launch(const Plan& pl, const FusedLaunchInputs& in, int max_wave
       if (used < lds_max && (t.ring = fused_tro_ring_pick(std::min(lds_max - used, cap), in.D, rpw))) break;
     }
   }
-  l->block = (cw + ww) * 64;
+  l->block = cw * 64;
   l->lds = tro_const + cw * per_wave + (size_t)t.ring * (size_t)(in.D + 4) * 4;
   const unsigned tile_rows = (unsigned)fused_tro_tile_rows(rpw);
   t.tpf = (unsigned)((in.H + tile_rows - 1) / tile_rows);

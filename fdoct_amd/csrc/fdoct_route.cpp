@@ -387,7 +387,7 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
                        (r->need_minmax ? FDOCT_WAVE_OPT_FRAMENORM : 0) | (!h->phase.empty() ? FDOCT_WAVE_OPT_CPLX : 0) |
                        (h->phase.empty() && D > h->N / 2 ? FDOCT_WAVE_OPT_DEEP : 0);
   // The wave-per-row kernel's launch, where its tables leave room for at least one wave's buffers: as many waves as LDS and
-  // the shape's register budget allow (two rows per wave on the short zero-padded shapes), at most one workgroup per CU.
+  // the shape's register budget allow, at most one workgroup per CU.
   auto wave_fits = [&](int opt) {
     const size_t shared = wave_shared_lds_bytes(h->wave_tw_count, W, h->M, h->N, h->yb.rows > 1, opt);
     const size_t priv = wave_private_lds_bytes(W, h->M, h->N, opt);
@@ -395,10 +395,9 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
     int waves = (int)((160 * 1024 - 64 - shared) / priv);
     if (waves > wave_max_waves(W, h->M, h->N, opt)) waves = wave_max_waves(W, h->M, h->N, opt);
     if (h->block_override && h->block_override / 64 >= 1 && h->block_override / 64 <= waves) waves = h->block_override / 64;
-    const long long rows = (long long)waves * wave_rows_per_wave(W, h->M, h->N, opt);
     r->waves = waves;
     r->lds = shared + (size_t)waves * priv;
-    r->grid = std::min<long long>(h->grid_override > 0 ? h->grid_override : h->num_cu, (out_rows + rows - 1) / rows);
+    r->grid = std::min<long long>(h->grid_override > 0 ? h->grid_override : h->num_cu, (out_rows + waves - 1) / waves);   // (a wave takes one row at a time)
     return true;
   };
   // 2 x 2 binning with nothing else in front of the chain, on a configuration the wave-per-row kernel takes: the kernel compiled

@@ -91,7 +91,7 @@ uint16_t half_bits(float f) {
   return (uint16_t)(sign | r);
 }
 
-// The second word as the fast-path kernels with at most 32 samples per lane apply it (fdoct_kernels.h: FDOCT_PREC16): what
+// The second word as the fast-path kernels with at most 32 samples per lane apply it (fdoct_fused_rules.h: fused_il_half): what
 // v * ib leaves out of v / yb is (v * ib) * rho, rho = (1/yb - ib) / ib, |rho| <= 2^-24; the kernel adds c0 * rho (c0: its
 // estimate of the row mean of v / yb).  rho * 2^38 as half floats, in the order the lanes read them: the lane's 8-sample group
 // of chunk c is 16 bytes at ((c T + lane) * 16), dword q = samples chunk_pair_offset(q), + 2 (the RawChunk pair order).

@@ -460,7 +460,7 @@ def test_weak_fringes_on_a_strong_background(family):
     multiplies by the reciprocal as TWO floats (fdoct_capi.cpp::reciprocal_words): d = fma(v, ib, -c0) with a uniform mean
     estimate c0, d = fma(v, il, d), x - mean = d - mean(d) -- nothing rounds at the size of the DC level.
     The fused kernel's fast path does so by default since round 5 (fdoct_set_precise_division(h, 0) is the opt-out), in the
-    half-float form of fdoct_kernels.h (FDOCT_PREC16: the correction c0 * (il / ib)) where a lane holds at most 32 samples;
+    half-float form of fdoct_fused_rules.h (fused_il_half: the correction c0 * (il / ib)) where a lane holds at most 32 samples;
     every other kernel always.
     (Rounds 2 and 3: lane sums of DC-sized products left 1e-8 of the DC level in the mean, 1.2 x the tolerance at 2 % fringes;
     the single f32 reciprocal a fixed pattern of <= 6e-8 of it per sample, 1.9 x the tolerance at 0.5 %, 6 x at 0.1 %.)
