@@ -1,6 +1,6 @@
 // fdoct_generic.hip -- the any-configuration kernels of the FD-OCT path (gfx950).
 //
-// fdoct_kernels.hip holds the specialised kernels (power-of-two N, M = 1, row widths that are a multiple
+// fdoct_kernels.hip (with the fdoct_fused_*.h it includes) holds the specialised kernels (power-of-two N, M = 1, row widths that are a multiple
 // of 8, D <= N/2).  Everything else the reference's block accepts runs here: any N = 2^a 3^b 5^c (the
 // shipped ini uses 2560), the zero-pad spectral upsampling `zeropadrowwise` (increasefftpointsmultiplier
 // M > 1, BscanFFT.cpp:180-245), any row width, numdisplaypoints up to N, every input type.  One workgroup

@@ -27,6 +27,14 @@
 // arithmetic is written on 2-element vectors that lower to v_pk_add/mul/fma_f32 (two
 // flops per lane per instruction) and quarter turns ride on instruction modifiers.
 // MFMA is not used: the path is elementwise + FFT work, not a dense contraction.
+//
+// This file is the translation unit: fused_kernel (workgroup set-up and the row loop) and the dispatch.  In headers:
+//   fdoct_fused_traits.h    FusedTraits: every size and compile-time switch an instantiation derives from its parameters
+//   fdoct_fused_dev.h       shared device helpers: measurement switches, wave_lds_sync, RawChunk, group reductions, load_consts
+//   fdoct_fused_fft.h       the LDS transforms: Stockham passes, the 1024- and 2048-point row-swap plans
+//   fdoct_fused_tro.h       the transposed store's geometry: tiles, ring slots, one write-out step, ticket -> row
+//   fdoct_fused_row.h       row slots and tickets, the real-path untangle, issue_ib2d, load_plane, second_word
+//   fdoct_prepass_kernels.inc, fdoct_prepass_launch.inc   the small pre-pass kernels (min / max, transpose, f64 split) and their launchers
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -44,516 +52,13 @@
 #endif
 #endif
 
-// Wait states after each 16-byte store of the tile write-out.  Measured on gfx950: a buffer_store_dwordx4 with an SGPR
-// soffset followed directly by a VALU write of its first data register stores the NEW value in the last four lanes of each
-// 16-lane row when the memory pipeline is busy (the compiler's hazard recogniser only covers the immediate-offset form of
-// this store-data hazard); one wait state cures it, two are used.
-constexpr int FDOCT_TRO_NOP = 2;
+#include "fdoct_fused_traits.h"
+#include "fdoct_fused_dev.h"
+#include "fdoct_fused_fft.h"
+#include "fdoct_fused_tro.h"
+#include "fdoct_fused_row.h"
 
 namespace fdoct {
-
-// Stage-skipping profiling aid (tools/ablate.sh): only in builds with -DFDOCT_RUNTIME_ABLATE.
-#ifdef FDOCT_RUNTIME_ABLATE
-#define FDOCT_ABL(bit) ((a.ablate & (bit)) != 0)
-#elif defined(FDOCT_CT_ABLATE)  // compile-time mask: the skipped stage costs nothing at all (one build per mask)
-#define FDOCT_ABL(bit) (((FDOCT_CT_ABLATE) & (bit)) != 0)
-#else
-#define FDOCT_ABL(bit) false
-#endif
-
-// Orders this wave's LDS traffic: a wave's DS operations execute in program
-// order, so a compiler-level fence is all a same-wave write->read hand-off needs.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Where a row's cycles go (measurement builds, -DFDOCT_FUSED_PROBE; tools/mkvariant.sh): the cycle counter is read at the phase
-// boundaries of the row loop and the differences summed per phase over a wave's rows.  (Each read waits for the wave's
-// outstanding LDS / scalar-memory operations -- s_memtime returns through the same counter -- so a phase is charged with the
-// latency of what it issued; the build is for attribution, its rate is a few per cent below the shipped kernel's.)
-#ifdef FDOCT_FUSED_PROBE
-struct FusedProbe {
-  unsigned long long acc[FUSED_PROBE_PHASES] = {}, t = 0;
-  __device__ __forceinline__ void start() { t = __builtin_readcyclecounter(); }
-  __device__ __forceinline__ void mark(int i) {
-    // (scheduling barriers either side: without them the compiler moves a phase's arithmetic across the read -- the first
-    // build of this probe showed 0.1 % for the radix-16 step)
-    __builtin_amdgcn_sched_barrier(0);
-    const unsigned long long n = __builtin_readcyclecounter();
-    __builtin_amdgcn_sched_barrier(0);
-    acc[i] += n - t;
-    t = n;
-  }
-};
-#define FDOCT_FPR(p, i) (p).mark(i)
-#else
-struct FusedProbe {};
-#define FDOCT_FPR(p, i) do {} while (0)
-#endif
-
-// Exchange-buffer layout: element e lives at slot e + (e >> LP) (one pad slot per
-// 2^LP elements, LP = log2 of the first radix).  Unlike an XOR swizzle this is
-// additive, so every LDS access below is <one per-lane base VGPR> + <immediate>;
-// writes are conflict free for every compiled plan and read-backs are conflict
-// free when the first radix is 32 (tests/kernel_model.py checks the banking).
-template <int LP>
-__device__ __forceinline__ constexpr int padded(int e) {
-  return e + (e >> LP);
-}
-
-// One Stockham pass over the T-lane group, in three pieces so that the kernel can issue the
-// (row-invariant) twiddle reads of a pass behind the previous pass's exchange writes and have a
-// single wait cover both:  z[m] = element (l + T*m).
-//   pass_twiddles : LDS -> registers, (R-1) twiddles per butterfly
-//   pass_compute  : twiddle multiply, radix-R butterflies, exchange writes (or registers if LAST)
-//   pass_readback : natural-order read-back of the exchange buffer
-template <int NC, int T, int R, int NS>
-__device__ __forceinline__ void pass_twiddles(v2f* twr, int l, const v2f* tw) {
-  constexpr int P = NC / T;
-  constexpr int NB = P / R;
-  static_for<0, NB>([&](auto tc) {
-    constexpr int t = decltype(tc)::value;
-    const v2f* twk = tw + ((l + T * t) & (NS - 1));
-    static_for<1, R>([&](auto rc) {
-      constexpr int r = decltype(rc)::value;
-      twr[t * (R - 1) + (r - 1)] = twk[(r - 1) * NS];
-    });
-  });
-}
-
-template <int NC, int T, int R, int NS, bool LAST, int LP, bool INV>
-__device__ __forceinline__ void pass_compute(v2f* z, int l, v2f* xch, const v2f* twr) {
-  constexpr int P = NC / T;
-  constexpr int NB = P / R;  // butterflies per lane
-  static_assert(P % R == 0, "radix must divide the per-lane point count");
-  static_assert(NS == 1 || NS >= (1 << LP), "later passes must keep pad-aligned strides");
-  static_for<0, NB>([&](auto tc) {
-    constexpr int t = decltype(tc)::value;
-    const int j = l + T * t;
-    const int k = j & (NS - 1);
-    v2f v[R];
-    static_for<0, R>([&](auto rc) {
-      constexpr int r = decltype(rc)::value;
-      v[r] = z[t + r * NB];
-    });
-    if constexpr (NS > 1) {
-      static_for<1, R>([&](auto rc) {
-        constexpr int r = decltype(rc)::value;
-        v[r] = cmul(v[r], twr[t * (R - 1) + (r - 1)]);
-      });
-    }
-    fft_reg<R, INV>(v);
-    if constexpr (LAST) {
-      static_for<0, R>([&](auto rc) {
-        constexpr int r = decltype(rc)::value;
-        z[t + r * NB] = v[r];
-      });
-    } else {
-      const int e0 = (j / NS) * (NS * R) + k;
-      v2f* dst = xch + (e0 + (e0 >> LP));
-      static_for<0, R>([&](auto rc) {
-        constexpr int r = decltype(rc)::value;
-        dst[padded<LP>(r * NS)] = v[r];  // (e0 + r*NS) >> LP == (e0 >> LP) + ((r*NS) >> LP) here
-      });
-    }
-  });
-}
-
-template <int NC, int T, int LP>
-__device__ __forceinline__ void pass_readback(v2f* z, int l, const v2f* xch) {
-  constexpr int P = NC / T;
-  if constexpr (T >= (1 << LP)) {
-    const v2f* src = xch + (l + (l >> LP));
-    static_for<0, P>([&](auto mc) {
-      constexpr int m = decltype(mc)::value;
-      z[m] = src[padded<LP>(T * m)];
-    });
-  } else {
-    const v2f* src = xch + l;  // l < T < 2^LP: the pad term depends on m only
-    static_for<0, P>([&](auto mc) {
-      constexpr int m = decltype(mc)::value;
-      z[m] = src[T * m + ((T * m) >> LP)];
-    });
-  }
-}
-
-// 1024-point inverse DFT on a full wave with ONE LDS exchange (plan "16 | row swap | 4 | LDS | 16").
-// Index split n = 64*m + 16*a + b (m: register, a: 16-lane row, b: lane in row), output
-// k = k1 + 16*k2 + 64*k3:
-//   1. radix-16 over m in registers                      -> A[k1][a][b], k1 in the register index
-//   2. 4x4 transpose between the lane row a and the low two bits of k1, done with
-//      v_permlane32_swap / v_permlane16_swap on register quads (no LDS)
-//   3. twiddle W_64^(a*k1), radix-4 over a               -> B[k1][k2][b]
-//   4. LDS exchange b <-> (k1,k2): element (b, l') at slot 65*b + l', l' = k1 + 16*k2
-//      (stride 65: conflict-free writes; reads are contiguous)
-//   5. twiddle W_1024^(b*l'), radix-16 over b            -> X[l' + 64*k3] in register k3 (natural)
-// tw2[(3*c + i-1)*4 + j] = W_64^(i*(4c+j)), tw3[(b-1)*64 + l'] = W_1024^(b*l')  (host tables).
-// tests/kernel_model.py::fft1024_rowswap_model is the index-for-index numpy model.
-__device__ __forceinline__ void swap_rows32(float& x, float& y) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-  x = __uint_as_float(r[0]);
-  y = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void swap_rows16(float& x, float& y) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-  x = __uint_as_float(r[0]);
-  y = __uint_as_float(r[1]);
-}
-
-// RESTW: the caller keeps the 12 + 15 row-invariant twiddles in registers (rt2 / rt3, loaded with
-// fft1024_rowswap_twiddles) instead of re-reading them from LDS for every row.
-__device__ __forceinline__ void fft1024_rowswap_twiddles(int lane, const v2f* tw2, const v2f* tw3, v2f* rt2, v2f* rt3) {
-  const int j = lane >> 4;
-  static_for<0, 12>([&](auto ec) {
-    constexpr int e = decltype(ec)::value;
-    rt2[e] = tw2[e * 4 + j];
-  });
-  static_for<1, 16>([&](auto bc) {
-    constexpr int bb = decltype(bc)::value;
-    rt3[bb - 1] = tw3[(bb - 1) * 64 + lane];
-  });
-}
-
-template <int RES2, bool RES3>  // RES2: how many of the 12 step-3 twiddles the caller keeps in registers (the first RES2)
-__device__ __forceinline__ void fft1024_rowswap(v2f* z, int lane, v2f* xch, const v2f* tw2, const v2f* tw3, const v2f* rt2,
-                                                const v2f* rt3, FusedProbe& pr) {
-  const int j = lane >> 4, b = lane & 15;
-  // 1. radix-16 over the register index
-  fft_reg<16, true>(z);
-  FDOCT_FPR(pr, 3);
-  // Steps 2-4 one register quad at a time (the transposition stays inside a quad).  The quad's three step-3 twiddles come
-  // from the caller's registers (the first RES2 of the twelve) or from LDS, read one quad ahead: six registers in flight
-  // instead of twenty-four.
-  auto quad_twiddles = [&](auto cc, v2f* t) {
-    constexpr int c = decltype(cc)::value;
-    static_for<0, 3>([&](auto ic) {
-      constexpr int e = 3 * c + decltype(ic)::value;
-      if constexpr (e < RES2)
-        t[e - 3 * c] = rt2[e];
-      else
-        t[e - 3 * c] = tw2[e * 4 + j];
-    });
-  };
-  v2f* dst = xch + (65 * b + j);
-  v2f tnext[3];
-  quad_twiddles(IC<0>{}, tnext);
-  static_for<0, 4>([&](auto cc) {
-    constexpr int c = decltype(cc)::value;
-    const v2f t2[3] = {tnext[0], tnext[1], tnext[2]};
-    if constexpr (c < 3) quad_twiddles(IC<c + 1>{}, tnext);
-    // 2. transpose (row a) <-> (k1 & 3) inside the register quad
-    float x0 = z[4 * c].x, y0 = z[4 * c].y, x1 = z[4 * c + 1].x, y1 = z[4 * c + 1].y;
-    float x2 = z[4 * c + 2].x, y2 = z[4 * c + 2].y, x3 = z[4 * c + 3].x, y3 = z[4 * c + 3].y;
-    swap_rows32(x0, x2);
-    swap_rows32(y0, y2);
-    swap_rows32(x1, x3);
-    swap_rows32(y1, y3);
-    swap_rows16(x0, x1);
-    swap_rows16(y0, y1);
-    swap_rows16(x2, x3);
-    swap_rows16(y2, y3);
-    // 3. register 4c+i of lane (j,b) now holds A[k1 = 4c+j][a = i][b]
-    v2f v[4] = {mk(x0, y0), cmul(mk(x1, y1), t2[0]), cmul(mk(x2, y2), t2[1]), cmul(mk(x3, y3), t2[2])};
-    fft_reg<4, true>(v);
-    // 4. B[k1 = 4c+j][k2][b] -> slot 65*b + (4c + j) + 16*k2
-    static_for<0, 4>([&](auto kc) {
-      constexpr int k2 = decltype(kc)::value;
-      dst[4 * c + 16 * k2] = v[k2];
-    });
-  });
-  // step-5 twiddles queue behind the exchange writes so one wait covers both
-  v2f t3[15];
-  static_for<1, 16>([&](auto bc) {
-    constexpr int bb = decltype(bc)::value;
-    if constexpr (RES3)
-      t3[bb - 1] = rt3[bb - 1];
-    else
-      t3[bb - 1] = tw3[(bb - 1) * 64 + lane];
-  });
-  wave_lds_sync();
-  FDOCT_FPR(pr, 5);   // (the 1024-point plan does the row swap quad by quad inside steps 3 / 4: phase 4 stays empty)
-  const v2f* src = xch + lane;
-  static_for<0, 16>([&](auto bc) {
-    constexpr int bb = decltype(bc)::value;
-    z[bb] = src[65 * bb];
-  });
-  wave_lds_sync();
-  FDOCT_FPR(pr, 6);
-  // 5. twiddle and radix-16 over b
-  static_for<1, 16>([&](auto bc) {
-    constexpr int bb = decltype(bc)::value;
-    z[bb] = cmul(z[bb], t3[bb - 1]);
-  });
-  fft_reg<16, true>(z);
-  FDOCT_FPR(pr, 7);
-}
-
-// 2048-point version of the same plan ("32 | row swap | 4 | LDS | 16 x2"): n = 64*m + 16*a + b with 32 registers m,
-// output k = k1 + 32*k2 + 128*k3.  Steps 1-4 as above with radix 32 and eight register quads (twiddle W_128^(a*k1),
-// exchange slot 129*b + l', l' = k1 + 32*k2 < 128); in step 5 every lane takes TWO columns l' = lane + 64*s, s = 0, 1
-// (twiddle W_2048^(b*l'), radix-16 over b) and leaves X[lane + 64*(s + 2*k3)] in register s + 2*k3 -- the natural slot
-// order.  tw2[(3*c + i-1)*4 + j] = W_128^(i*(4c+j)) (c < 8), tw3[l'] = W_2048^(l'), l' < 128.
-// tests/kernel_model.py::fft2048_rowswap_model is the index-for-index numpy model.
-__device__ __forceinline__ void fft2048_rowswap(v2f* z, int lane, v2f* xch, const v2f* tw2, const v2f* tw3, FusedProbe& pr) {
-  const int j = lane >> 4, b = lane & 15;
-  fft_reg<32, true>(z);  // 1.
-  FDOCT_FPR(pr, 3);
-  static_for<0, 8>([&](auto cc) {  // 2.
-    constexpr int c = decltype(cc)::value;
-    float x0 = z[4 * c].x, y0 = z[4 * c].y, x1 = z[4 * c + 1].x, y1 = z[4 * c + 1].y;
-    float x2 = z[4 * c + 2].x, y2 = z[4 * c + 2].y, x3 = z[4 * c + 3].x, y3 = z[4 * c + 3].y;
-    swap_rows32(x0, x2);
-    swap_rows32(y0, y2);
-    swap_rows32(x1, x3);
-    swap_rows32(y1, y3);
-    swap_rows16(x0, x1);
-    swap_rows16(y0, y1);
-    swap_rows16(x2, x3);
-    swap_rows16(y2, y3);
-    z[4 * c] = mk(x0, y0);
-    z[4 * c + 1] = mk(x1, y1);
-    z[4 * c + 2] = mk(x2, y2);
-    z[4 * c + 3] = mk(x3, y3);
-  });
-  FDOCT_FPR(pr, 4);
-  // 3. + 4.: register 4c+i of lane (j,b) holds A[k1 = 4c+j][a = i][b]
-  v2f* dst = xch + (129 * b + j);
-  static_for<0, 8>([&](auto cc) {
-    constexpr int c = decltype(cc)::value;
-    const v2f* t2 = tw2 + (3 * c) * 4 + j;
-    v2f v[4] = {z[4 * c], cmul(z[4 * c + 1], t2[0]), cmul(z[4 * c + 2], t2[4]), cmul(z[4 * c + 3], t2[8])};
-    fft_reg<4, true>(v);
-    static_for<0, 4>([&](auto kc) {
-      constexpr int k2 = decltype(kc)::value;
-      dst[4 * c + 32 * k2] = v[k2];
-    });
-  });
-  wave_lds_sync();
-  FDOCT_FPR(pr, 5);
-  // 5. two columns per lane; the second one is read while the first is being transformed
-  const v2f* src = xch + lane;
-  v2f u[16], w[16];
-  static_for<0, 16>([&](auto bc) {
-    constexpr int bb = decltype(bc)::value;
-    u[bb] = src[129 * bb];
-  });
-  static_for<0, 16>([&](auto bc) {
-    constexpr int bb = decltype(bc)::value;
-    w[bb] = src[129 * bb + 64];
-  });
-  wave_lds_sync();
-  FDOCT_FPR(pr, 6);
-  // W_2048^(bb*l'), bb = 1..15, as powers of the one table entry W_2048^(l') (squarings / products, depth <= 6
-  // multiplies): 15 KB less LDS per workgroup than a full table, which is worth a wave per CU here
-  auto column = [&](v2f* col, v2f w1) {
-    v2f pw[16];
-    pw[1] = w1;
-    static_for<2, 16>([&](auto rc) {
-      constexpr int r = decltype(rc)::value;
-      pw[r] = (r & 1) ? cmul(pw[r - 1], pw[1]) : cmul(pw[r / 2], pw[r / 2]);
-    });
-    static_for<1, 16>([&](auto bc) {
-      constexpr int bb = decltype(bc)::value;
-      col[bb] = cmul(col[bb], pw[bb]);
-    });
-    fft_reg<16, true>(col);
-  };
-  column(u, tw3[lane]);
-  column(w, tw3[lane + 64]);
-  static_for<0, 16>([&](auto kc) {
-    constexpr int k3 = decltype(kc)::value;
-    z[2 * k3] = u[k3];
-    z[2 * k3 + 1] = w[k3];
-  });
-  FDOCT_FPR(pr, 7);
-}
-
-// ------------------------------------------------------------ input types --
-// One 8-sample chunk s0..s7 of a row as loaded (prefetched) from HBM.  unpack() gives the four pairs
-// (s0,s2) (s4,s6) (s1,s3) (s5,s7): evens and odds apart, so that the slope step's "previous sample" of an odd
-// pair IS the even pair, and the de-interleaved staging stores are whole registers quads (no shuffles).
-// chunk_pair_offset(q) = index of the first sample of pair q; the second one is two samples later.
-__device__ __forceinline__ constexpr int chunk_pair_offset(int q) { return (q & 1) * 4 + (q >> 1); }
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-typedef uint32_t u2v __attribute__((ext_vector_type(2)));
-template <typename IN_T>
-struct RawChunk;
-template <>
-struct RawChunk<uint16_t> {
-  uint4 v;
-  __device__ __forceinline__ void load(const void* row, int i0) {
-    // streaming load: camera samples are read once (nt keeps them from displacing the twiddle / plane lines in L2; +1.2 %,
-    // DESIGN.md 5 -- the sc0/sc1 scope bits change nothing)
-    const u4v t = __builtin_nontemporal_load(reinterpret_cast<const u4v*>(static_cast<const uint16_t*>(row) + i0));
-    v = make_uint4(t.x, t.y, t.z, t.w);
-  }
-  __device__ __forceinline__ void zero() { v = make_uint4(0, 0, 0, 0); }
-  __device__ __forceinline__ void pin() { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
-  __device__ __forceinline__ void pin_ordered() { asm volatile("" : "+v"(v.x) : : "memory"); }
-  __device__ __forceinline__ void unpack(v2f* x) const {
-    x[0] = mk((float)(v.x & 0xffffu), (float)(v.y & 0xffffu));
-    x[1] = mk((float)(v.z & 0xffffu), (float)(v.w & 0xffffu));
-    x[2] = mk((float)(v.x >> 16), (float)(v.y >> 16));
-    x[3] = mk((float)(v.z >> 16), (float)(v.w >> 16));
-  }
-};
-template <>
-struct RawChunk<uint8_t> {
-  uint2 v;
-  __device__ __forceinline__ void load(const void* row, int i0) {
-    const u2v t = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(static_cast<const uint8_t*>(row) + i0));
-    v = make_uint2(t.x, t.y);
-  }
-  __device__ __forceinline__ void zero() { v = make_uint2(0, 0); }
-  __device__ __forceinline__ void pin() { asm volatile("" : "+v"(v.x), "+v"(v.y)); }
-  __device__ __forceinline__ void pin_ordered() { asm volatile("" : "+v"(v.x) : : "memory"); }
-  __device__ __forceinline__ void unpack(v2f* x) const {
-    x[0] = mk((float)(v.x & 0xffu), (float)((v.x >> 16) & 0xffu));
-    x[1] = mk((float)(v.y & 0xffu), (float)((v.y >> 16) & 0xffu));
-    x[2] = mk((float)((v.x >> 8) & 0xffu), (float)(v.x >> 24));
-    x[3] = mk((float)((v.y >> 8) & 0xffu), (float)(v.y >> 24));
-  }
-};
-template <>
-struct RawChunk<float> {
-  float4 a, b;
-  __device__ __forceinline__ void load(const void* row, int i0) {
-    typedef float f4v __attribute__((ext_vector_type(4)));
-    const f4v* p = reinterpret_cast<const f4v*>(static_cast<const float*>(row) + i0);
-    const f4v ta = __builtin_nontemporal_load(p), tb = __builtin_nontemporal_load(p + 1);
-    a = make_float4(ta.x, ta.y, ta.z, ta.w);
-    b = make_float4(tb.x, tb.y, tb.z, tb.w);
-  }
-  __device__ __forceinline__ void zero() { a = b = make_float4(0, 0, 0, 0); }
-  __device__ __forceinline__ void pin() {
-    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w));
-  }
-  __device__ __forceinline__ void pin_ordered() { asm volatile("" : "+v"(a.x) : : "memory"); }
-  __device__ __forceinline__ void unpack(v2f* x) const {
-    x[0] = mk(a.x, a.z);
-    x[1] = mk(b.x, b.z);
-    x[2] = mk(a.y, a.w);
-    x[3] = mk(b.y, b.w);
-  }
-};
-
-template <int T>
-__device__ __forceinline__ float group_min(float v) {
-#pragma unroll
-  for (int m = T / 2; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-template <int T>
-__device__ __forceinline__ float group_max(float v) {
-#pragma unroll
-  for (int m = T / 2; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
-// One DPP step of a wave-wide f64 sum: v + (v moved by `CTRL`).  Only lane 63's total is used, so lanes that
-// the row mask leaves unwritten may hold anything; row shifts read 0 past the row edge (bound_ctrl).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_add_f64(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const int tlo = __builtin_amdgcn_mov_dpp(lo, CTRL, ROW_MASK, 0xf, true);
-  const int thi = __builtin_amdgcn_mov_dpp(hi, CTRL, ROW_MASK, 0xf, true);
-  return v + __hiloint2double(thi, tlo);
-}
-
-// Sum over the T lanes of a row group, returned to every lane of the group.  T == 64: DPP
-// row shifts / broadcasts (no LDS, no address registers) and a scalar broadcast of lane 63.
-template <int T>
-__device__ __forceinline__ double group_sum(double v) {
-  if constexpr (T == 64) {
-    v = dpp_add_f64<0x111, 0xf>(v);  // row_shr:1  -> lane i: v[i-1..i]
-    v = dpp_add_f64<0x112, 0xf>(v);  // row_shr:2  -> v[i-3..i]
-    v = dpp_add_f64<0x114, 0xf>(v);  // row_shr:4  -> v[i-7..i]
-    v = dpp_add_f64<0x118, 0xf>(v);  // row_shr:8  -> lane 15 of each row: the row's total
-    v = dpp_add_f64<0x142, 0xa>(v);  // row_bcast:15 -> rows 1,3 add the previous row's total
-    v = dpp_add_f64<0x143, 0xc>(v);  // row_bcast:31 -> rows 2,3 add lane 31
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-    return __hiloint2double(hi, lo);
-  } else {
-#pragma unroll
-    for (int m = T / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-  }
-}
-
-// One DPP step of a wave-wide f32 sum (lanes the row mask leaves out add 0).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add_f32(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true));
-}
-// The two cross-row steps of that sum, one v_add_f32_dpp each: row_bcast:15 into rows 1 and 3, then row_bcast:31 into rows 2
-// and 3.  The destination is tied to v, so rows outside a mask keep v.  (Written with the builtin above, each step is three
-// instructions -- a zero, a v_mov_b32_dpp into it, an add: the compiler does not fold a partial row mask into a float add,
-// because the rows left out would hold v where the source says v + 0, and those differ for v = -0.)  That difference cannot
-// reach group_sum_f32's result, which is lane 63 alone: lane 63 is in both masks, so it is added to in both steps; what it
-// adds is lane 47 as the row shifts left it (a DPP step reads its sources before any lane is written) and then lane 31, which
-// is in row 1 and so was itself added to in the first step.  No lane that a mask leaves out is read again.
-// The compiler does not see a DPP read inside an asm statement, so the two wait states that a VALU write of v needs before
-// a DPP read of it are in the statement itself.  The five that a VALU write of EXEC (v_cmpx) needs before a DPP operation are
-// not: the callers run this at the top level of a row, with every lane on (which the broadcasts assume as well: no bound_ctrl),
-// and the compiler writes EXEC from the scalar unit there.  A caller under a v_cmpx would have to wait them out itself.
-__device__ __forceinline__ float dpp_add_cross_rows_f32(float v) {
-  asm("s_nop 1\n\t"
-      "v_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
-      : "+v"(v));
-  return v;
-}
-
-// Sum over the T lanes of a row group in f32, returned to every lane of the group (T == 64: the DPP chain of
-// group_sum; ONE_EACH: one v_add_f32_dpp per step, the cross-row steps included -- the same bits either way).
-template <int T, bool ONE_EACH>
-__device__ __forceinline__ float group_sum_f32(float v) {
-  if constexpr (T == 64) {
-    v = dpp_add_f32<0x111, 0xf>(v);
-    v = dpp_add_f32<0x112, 0xf>(v);
-    v = dpp_add_f32<0x114, 0xf>(v);
-    v = dpp_add_f32<0x118, 0xf>(v);
-    if constexpr (ONE_EACH) {
-      v = dpp_add_cross_rows_f32(v);
-    } else {
-      v = dpp_add_f32<0x142, 0xa>(v);
-      v = dpp_add_f32<0x143, 0xc>(v);
-    }
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-  } else {
-#pragma unroll
-    for (int m = T / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-  }
-}
-
-// fma with a half-float second operand (the low / high half of hp), converted inside the instruction: a * f16(hp) + c.
-__device__ __forceinline__ float fma_mix_lo(float a, uint32_t hp, float c) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(hp), "v"(c));
-  return r;
-}
-__device__ __forceinline__ float fma_mix_hi(float a, uint32_t hp, float c) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(hp), "v"(c));
-  return r;
-}
-
-// Reads the 8 constants of chunk c of one constant plane pair in the RawChunk pair order.
-// Plane layout (see the staging loop in the kernel): chunk c, parity h, lane ln -> c*8T + h*4T + 4*ln.
-template <int T>
-__device__ __forceinline__ void load_consts(const float* plane_lane, int c, v2f* out) {
-  const float4 q0 = *reinterpret_cast<const float4*>(plane_lane + 8 * T * c);
-  const float4 q1 = *reinterpret_cast<const float4*>(plane_lane + 8 * T * c + 4 * T);
-  out[0] = mk(q0.x, q0.y);
-  out[1] = mk(q0.z, q0.w);
-  out[2] = mk(q1.x, q1.y);
-  out[3] = mk(q1.z, q1.w);
-}
 
 // ------------------------------------------------------------ fused kernel --
 // LOG2NC: log2 of the complex FFT length NC (= N/2 real path, N complex path)
@@ -597,30 +102,7 @@ __device__ __forceinline__ void load_consts(const float* plane_lane, int c, v2f*
 template <int LOG2NC, int T, int R1, int R2, int R3, int KIND, int WCH, typename IN_T, bool CPLX, bool LEAN, int STAGE, bool AVG,
           bool IB2D = false, int NORM = 0, bool TRO = false, bool PRECT = false>
 __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void fused_kernel(const FusedArgs a) {
-  constexpr int NC = 1 << LOG2NC;
-  constexpr int P = NC / T;
-  constexpr int RPW = 64 / T;  // rows per wave
-  constexpr int WC = 8 * T * WCH;
-  constexpr int NPR = 4 * WCH;  // sample pairs per lane
-  constexpr int LP = (R1 == 32) ? 5 : (R1 == 16) ? 4 : (R1 == 8) ? 3 : 2;
-  static_assert(R1 * R2 * R3 == NC, "radix plan");
-  static_assert(KIND == 0 || (KIND == 1 && T == 64 && R1 == 16 && R2 == 4 && R3 == 16) ||
-                    (KIND == 2 && T == 64 && R1 == 32 && R2 == 4 && R3 == 16),
-                "row-swap plans are 16 x 4 x 16 / 32 x 4 x 16 on a full wave");
-  constexpr int NPASS = (R3 > 1) ? 3 : 2;
-  // 1/background as two floats (fdoct_capi.cpp::reciprocal_words): always on the any-option kernel; the fast path has both
-  // instantiations (PRECT: fdoct_set_precise_division)
-  constexpr bool PREC = !LEAN || PRECT;
-  // the second word's form on the fast-path kernels with at most 32 samples per lane: a plane of half floats (fdoct_fused_rules.h)
-  constexpr bool IL16 = PRECT && fused_il_half(LEAN, WCH);
-  static_assert(!(PRECT && !LEAN), "the any-option kernel always multiplies by both words");
-  static_assert(!(PRECT && IB2D && !IL16), "a full-frame background on the fast path: the second word is prefetched as half floats");
-
-  // The row loop's trims (one v_add_f32_dpp per cross-row step of the wave sums; the row ticket as a plain ds_add_rtn_u32): the
-  // same results bit for bit, taken where they are measured to pay -- the 1024-point one-exchange plan writing rows.  The
-  // transposed-store kernels are at 256 VGPRs with scratch and allocate worse with either; with the ticket's wait fixed inside
-  // an asm statement the plans with four rows per wave lose what the compiler gains by placing it (EXPERIMENTS.md section 7).
-  constexpr bool TRIM = KIND == 1 && !TRO;
+  using X = FusedTraits<LOG2NC, T, R1, R2, R3, KIND, WCH, IN_T, CPLX, LEAN, STAGE, AVG, IB2D, NORM, TRO, PRECT>;
   __shared__ unsigned int row_ticket;  // next unclaimed row slot of this workgroup
   __shared__ unsigned int tr_arrived[4];  // TRO: rows of tile (q mod 4) in the ring
   // TRO: tiles q = i (mod 4) that have completed so far.  Tiles need not complete in order -- with a 4-row last tile of a
@@ -636,23 +118,18 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   __shared__ unsigned int grp_pub[4];       // tiles published to a group so far
   __shared__ unsigned int grp_arrived[4];   // waves of a group whose rows are deposited (cumulative: 4 per tile)
   __shared__ unsigned int grp_done[4];      // waves of a group that have finished their share of a write-out (cumulative)
-  static_assert(!TRO || (LEAN && STAGE == 0 && !CPLX && fused_tro_compiled(KIND, T, WCH) && (FUSED_TR_ROWS % (64 / T)) == 0),
-                "fused transposed store: fast path; a wave's rows lie in one tile");
   extern __shared__ __align__(16) unsigned char smem[];
-  const int cw = a.lds_planes ? WC : 0;          // resident-constant kernels: the host leaves the planes out
+  const int cw = a.lds_planes ? X::WC : 0;          // resident-constant kernels: the host leaves the planes out
   float* c_ib = reinterpret_cast<float*>(smem);  // [WC] 1/background
   float* c_win = c_ib + cw;                      // [WC] window
   float* c_g = c_win + cw;                       // [WC] fractionalk by sample index
   float* c_il = c_g + cw;                        // [WC] low word of 1/background (a.prec == 1: every kernel reads it from here, the resident-constant ones too)
-  const int cwl = (a.prec == 1 && STAGE != 2) ? (IL16 ? WC / 2 : WC) : 0;  // floats (the FFT-stage kernel reads no samples); IL16: 2 WC bytes
+  const int cwl = (a.prec == 1 && STAGE != 2) ? (X::IL16 ? X::WC / 2 : X::WC) : 0;  // floats (the FFT-stage kernel reads no samples); IL16: 2 WC bytes
   v2f* c_tw = reinterpret_cast<v2f*>(c_il + cwl);  // twiddle tables, a.tw_count entries
-  // (transposed-store kernels leave out of LDS what they read once into registers, so that the ring of finished rows can be
-  // larger: fdoct_fused_rules.h, fused_tw3_in_lds / fused_gi_in_lds)
-  constexpr bool TW3_LDS = fused_tw3_in_lds(KIND, LEAN, STAGE, TRO, IB2D && IL16), GI_LDS = fused_gi_in_lds(KIND, LEAN, STAGE, CPLX, AVG, TRO);
-  const int tw_lds = TW3_LDS ? a.tw_count : (R2 - 1) * R1;   // entries staged: all, or the step-3 table only
+  const int tw_lds = X::TW3_LDS ? a.tw_count : (R2 - 1) * R1;   // entries staged: all, or the step-3 table only
   v2f* c_ph = c_tw + tw_lds;                     // [NC] phase (CPLX only)
-  uint32_t* c_gi = reinterpret_cast<uint32_t*>(c_ph + (CPLX ? NC : 0));  // [NC] packed gather offsets
-  unsigned char* scratch0 = reinterpret_cast<unsigned char*>(c_gi + (GI_LDS ? NC : 0));
+  uint32_t* c_gi = reinterpret_cast<uint32_t*>(c_ph + (CPLX ? X::NC : 0));  // [NC] packed gather offsets
+  unsigned char* scratch0 = reinterpret_cast<unsigned char*>(c_gi + (X::GI_LDS ? X::NC : 0));
 
 #ifdef FDOCT_CLOCKPROBE
   const unsigned long long probe_c0 = __builtin_readcyclecounter(), probe_r0 = wall_clock64();
@@ -675,7 +152,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     c_win[slot] = in ? a.win[i] : 0.f;
     c_g[slot] = in ? a.g[i] : 0.f;
   }
-  if constexpr (IL16) {  // half-float pairs, already in the order the lanes read them (fdoct_capi.cpp)
+  if constexpr (X::IL16) {  // half-float pairs, already in the order the lanes read them (fdoct_capi.cpp)
     for (int i = tid; i < cwl; i += blockDim.x) reinterpret_cast<uint32_t*>(c_il)[i] = a.il16 ? a.il16[i] : 0u;
   } else {
     for (int i = tid; i < cwl; i += blockDim.x) {  // (the same slot rule)
@@ -688,136 +165,27 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     for (int i = tid; i < tw_lds; i += blockDim.x) c_tw[i] = gtw[i];
     if constexpr (CPLX) {
       const v2f* gph = reinterpret_cast<const v2f*>(a.phase);
-      for (int i = tid; i < NC; i += blockDim.x) c_ph[i] = gph[i];
+      for (int i = tid; i < X::NC; i += blockDim.x) c_ph[i] = gph[i];
     }
   }
-  constexpr bool TRO_INPLACE = TRO && RPW == 4;
-  constexpr unsigned GW = (unsigned)fused_tro_group_waves();   // waves of a group (TRO_INPLACE): a tile is 4 GW rows
-  if (tid == 0) row_ticket = TRO_INPLACE ? (blockDim.x >> 6) / GW : (blockDim.x >> 6);  // slots 0 .. nwaves-1 are the (computing) waves' first rows (groups' first tiles)
+  if (tid == 0) row_ticket = X::TRO_INPLACE ? (blockDim.x >> 6) / X::GW : (blockDim.x >> 6);  // slots 0 .. nwaves-1 are the (computing) waves' first rows (groups' first tiles)
   if (TRO && tid < 4) tr_arrived[tid] = tr_done[tid] = 0u;
-  if (TRO_INPLACE && tid < 4) grp_pub[tid] = grp_arrived[tid] = grp_done[tid] = 0u;
+  if (X::TRO_INPLACE && tid < 4) grp_pub[tid] = grp_arrived[tid] = grp_done[tid] = 0u;
   if (TRO && tid == 0) tr_ready = tr_wo_next = tr_wo_done = 0u;
   // gather table: entry n = ln + T*m is stored at [(m/4)][ln][m%4] so a lane's P entries are P/4
   // b128 reads with a 16-byte lane stride (re-read every row: cheaper than P resident VGPRs)
-  if constexpr (GI_LDS) {
-    for (int i = tid; i < NC; i += blockDim.x) {
+  if constexpr (X::GI_LDS) {
+    for (int i = tid; i < X::NC; i += blockDim.x) {
       const int ln = i & (T - 1), m = i / T;
       c_gi[(m >> 2) * 4 * T + 4 * ln + (m & 3)] = a.gidx[i];
     }
   }
   __syncthreads();
 
-  // ---- TRO: tiles.  Tile q of workgroup b is tile q * grid + b of the batch (front to back); tiles never straddle B-scans
-  // (the last tile of a B-scan may be short).  Wave-uniform, scalar unit.
-  constexpr unsigned TR = TRO_INPLACE ? 4u * GW : (unsigned)FUSED_TR_ROWS;
-  auto tro_tile = [&](unsigned tq, unsigned& g, unsigned& r0, unsigned& nrows) -> bool {  // false: past the end of the batch
-    // workgroups b, b + 8, b + 16 .. run on the same XCD (round-robin dispatch) at about the same time: they get a run of
-    // NEIGHBOURING tiles, so that the two 64-byte halves of every 128-byte line of the B-scan meet in one L2 (a
-    // performance matter only: any bijection of the workgroups is correct)
-    const unsigned nx = gridDim.x >> 3;
-    const unsigned bperm = (gridDim.x & 7u) ? blockIdx.x : (blockIdx.x & 7u) * nx + (blockIdx.x >> 3);
-    const unsigned gt = tq * gridDim.x + bperm;
-    if (gt >= a.tr_total_tiles) return false;
-    g = __umulhi(gt, a.tr_tpf_magic);  // gt / tiles-per-frame: floor(2^32 / tpf) under-estimates by at most one
-    unsigned tf = gt - g * a.tr_tpf;
-    if (tf >= a.tr_tpf) {
-      g++;
-      tf -= a.tr_tpf;
-    }
-    r0 = tf * TR;
-    const unsigned left = (unsigned)a.H - r0;
-    nrows = left < TR ? left : TR;
-    return true;
-  };
-  // ring slots: one of a few compile-time values (kTroRingChoices), so that "mod RS" stays a multiplication; the launch picks
-  // the largest that fits the LDS (wave-uniform: a scalar branch)
   const unsigned RS = (unsigned)__builtin_amdgcn_readfirstlane((int)a.tr_ring);
-  auto ring_mod = [&](unsigned x) -> unsigned {
-    switch (RS) {
-      case 21: return x % 21u;
-      case 22: return x % 22u;
-      case 23: return x % 23u;
-      case 24: return x % 24u;
-      case 26: return x % 26u;
-      case 28: return x % 28u;
-      case 32: return x % 32u;
-      case 40: return x % 40u;
-      case 44: return x % 44u;
-      case 48: return x % 48u;
-      default: return x % 20u;
-    }
-  };
-  // the ring lies behind the waves' row buffers; a slot is D + 4 floats (the pad moves consecutive rows 4 banks apart)
-  float* const tro_ring = reinterpret_cast<float*>(scratch0 + (size_t)(blockDim.x >> 6) * RPW * a.scratch_bytes);
+  float* const tro_ring = reinterpret_cast<float*>(scratch0 + (size_t)(blockDim.x >> 6) * X::RPW * a.scratch_bytes);
   const int tro_slot = a.D + 4;
-  // One write-out step: bins s0 .. s0 + SB - 1 of tile tq, all its rows.  Lane (dg, rq) takes rows 4 rq .. 4 rq + 3 and bins
-  // 4 dg .. 4 dg + 3: four ds_read_b128 (one per row), four 16-byte stores (one per bin: the lanes of a row-quad group cover
-  // TR * 4 contiguous bytes of the B-scan).  When both images are asked for the ring holds bscan and the logarithm is taken
-  // here (the same instruction on the same value as the epilogue's).
-  constexpr int TRO_RQ = TR / 4, TRO_DGN = 64 / TRO_RQ, TRO_SB = 4 * TRO_DGN;
-  auto tro_step = [&](unsigned tq, unsigned g, unsigned r0, unsigned nrows, int s0) {
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const int rq = lane % TRO_RQ, dg = lane / TRO_RQ;
-    const int Dn = a.D, Hn = a.H;
-    if (4 * rq >= (int)nrows) return;
-    const bool both = a.out_mag && a.out_db;
-    const bool mask = both && a.dcmask && Dn > 4;  // dB bins 0, 1 <- bin 4 (main:1237-1238); alone, dB arrives masked
-    float* const out0 = a.out_mag ? a.out_mag : a.out_db;
-    const int Hs = Hn;
-    const int vout = (4 * dg * Hs + 4 * rq) * 4;
-    const float* rowp[4];
-    if constexpr (TRO_INPLACE) {
-      // rows 4 rq .. 4 rq + 3 of the tile lie in the row buffers of wave rq of the group (tq names the GROUP here): row i of the
-      // tile is row buffer 16 group + i, buffers scratch_bytes apart (1060 floats: four banks on, like the ring's slots)
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-        rowp[i] = reinterpret_cast<const float*>(scratch0 + (size_t)(TR * tq + 4u * (unsigned)rq + (unsigned)i) * a.scratch_bytes) + 4 * dg + s0;
-    } else {
-      const unsigned sl0 = ring_mod(TR * tq + 4u * (unsigned)rq);  // this lane's four rows: ring slots (TR tq + 4 rq + i) mod RS
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const unsigned sl = sl0 + i >= RS ? sl0 + i - RS : sl0 + i;
-        rowp[i] = tro_ring + sl * tro_slot + 4 * dg + s0;
-      }
-    }
-    const size_t goff = ((size_t)g * Dn) * Hn + r0;
-    __amdgpu_buffer_rsrc_t rout0 = __builtin_amdgcn_make_buffer_rsrc(out0 + goff, 0, 0x7ffffff0, 0x00020000);
-    f4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) v[i] = *reinterpret_cast<const f4*>(rowp[i]);
-    // Cache policy of the stores (the last argument): 0 = write-back.  The two 64-byte halves of a 128-byte line of the B-scan
-    // come from neighbouring tiles, which tro_tile hands to workgroups of the same XCD: with write-back stores they meet in that
-    // L2 and leave it as one line.  Measured (C2, M A-scans/s): nt 277, write-back 329, sc1 357-376; with the tile pairing sc1
-    // 367-380, write-back 395-406.
-#pragma unroll
-    for (int bb = 0; bb < 4; bb++) {
-      const f4 w = {v[0][bb], v[1][bb], v[2][bb], v[3][bb]};
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, w), rout0, vout, ((s0 + bb) * Hs) * 4, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_nop %0" ::"n"(FDOCT_TRO_NOP - 1));
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (both) {
-      __amdgpu_buffer_rsrc_t rout1 = __builtin_amdgcn_make_buffer_rsrc(a.out_db + goff, 0, 0x7ffffff0, 0x00020000);
-      f4 v4 = {0.f, 0.f, 0.f, 0.f};  // bin 4 of the four rows (DC mask)
-      if (mask && s0 == 0 && dg == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) v4[i] = rowp[i][4];
-      }
-#pragma unroll
-      for (int bb = 0; bb < 4; bb++) {
-        f4 w = {v[0][bb], v[1][bb], v[2][bb], v[3][bb]};
-        if (mask && bb < 2 && s0 == 0 && dg == 0) w = v4;
-#pragma unroll
-        for (int k = 0; k < 4; k++) w[k] = a.db_scale * fast_log2(w[k]);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, w), rout1, vout, ((s0 + bb) * Hs) * 4, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop %0" ::"n"(FDOCT_TRO_NOP - 1));
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  };
+  const TroGeom<X> tro{a, RS, tro_ring, tro_slot, scratch0, lane};
   // Tile tq of this workgroup has just completed (all its rows are in the ring).
   // Tiles need not complete in order (see tr_done), but everything that waits or claims counts tiles IN ORDER: the tile is
   // counted in tr_done, then the in-order counter *inorder is advanced over every tile that is complete by now -- by this
@@ -854,7 +222,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   // traffic -- so they are batched: tr_wo_next and tr_ready are read together, the steps-done counter is cumulative and bumped
   // without a return value (tile q is out when it reaches (q + 1) SPT), and only the claim itself is a round trip of its own.)
   auto tro_try_step = [&](unsigned s, unsigned ready) -> bool {  // s = tr_wo_next as just read, ready = complete tiles
-    const unsigned spt = (unsigned)a.D / (unsigned)TRO_SB;
+    const unsigned spt = (unsigned)a.D / (unsigned)X::TRO_SB;
     if (s >= ready * spt) return false;
     unsigned got = 0u;
     if (lane == 0) {
@@ -864,9 +232,9 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     if (!__builtin_amdgcn_readfirstlane((int)got)) return true;  // another wave took it: something is going on
     const unsigned tq = s / spt, k = s - tq * spt;
     unsigned g, r0, nrows;
-    (void)tro_tile(tq, g, r0, nrows);
+    (void)tro.tile(tq, g, r0, nrows);
     asm volatile("" ::: "memory");
-    tro_step(tq, g, r0, nrows, (int)k * TRO_SB);
+    tro.step(tq, g, r0, nrows, (int)k * X::TRO_SB);
     asm volatile("" ::: "memory");  // the step's LDS reads have returned (they fed stores that have been issued)
     if (lane == 0) __hip_atomic_fetch_add(&tr_wo_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     return true;
@@ -883,7 +251,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   };
   unsigned tro_done_seen = 0u;  // steps written out, as last read (the counter only grows: a valid lower bound)
 
-  unsigned char* scr = scratch0 + (size_t)(wave * RPW + sub) * a.scratch_bytes;
+  unsigned char* scr = scratch0 + (size_t)(wave * X::RPW + sub) * a.scratch_bytes;
   float* stg = reinterpret_cast<float*>(scr);
   v2f* xch = reinterpret_cast<v2f*>(scr);
 
@@ -894,22 +262,16 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   const v2f* tw_p2 = c_tw;                                       // pass 2 table: (R2-1) x R1
   // pass 3 table: (R3-1) x (R1*R2) (row-swap plans: the step-5 table); kernels that hold its entries in registers and need
   // the LDS for something else (TW3_LDS false) read them once from the global table
-  const v2f* tw_p3 = TW3_LDS ? c_tw + (R2 - 1) * R1 : reinterpret_cast<const v2f*>(a.tw) + (R2 - 1) * R1;
+  const v2f* tw_p3 = X::TW3_LDS ? c_tw + (R2 - 1) * R1 : reinterpret_cast<const v2f*>(a.tw) + (R2 - 1) * R1;
 
-  // Fast-path row-swap plan (the benchmark configuration): everything that does not depend on the row --
-  // the per-column constants, the gather addresses and the FFT twiddles -- stays in registers (2 waves per
-  // SIMD, 256 VGPRs), which removes half of the LDS traffic per row.  Every other instantiation re-reads
-  // them from LDS each row.
-  constexpr bool RES = fused_resident_consts(KIND, LEAN, AVG, WCH, STAGE);
-  constexpr bool GRES = LEAN && STAGE != 2 && KIND == 1 && !CPLX && !AVG;  // (with averaging the accumulators need those registers)
-  uint32_t gaddr[GRES ? 2 * P : 1];
-  if constexpr (GRES) {  // 2 LDS byte addresses per FFT point
+  uint32_t gaddr[X::GRES ? 2 * X::P : 1];
+  if constexpr (X::GRES) {  // 2 LDS byte addresses per FFT point
     const uint4* gl4 = reinterpret_cast<const uint4*>(c_gi) + l;
     const uint32_t sbase = (uint32_t)(uintptr_t)scr;  // LDS byte address of this wave's staging buffer
 #pragma unroll
-    for (int q = 0; q < P / 4; q++) {
+    for (int q = 0; q < X::P / 4; q++) {
       uint4 g4;
-      if constexpr (GI_LDS)
+      if constexpr (X::GI_LDS)
         g4 = gl4[q * T];
       else   // (straight from the global table: entry n = l + T m)
         g4 = make_uint4(a.gidx[l + T * (4 * q)], a.gidx[l + T * (4 * q + 1)], a.gidx[l + T * (4 * q + 2)], a.gidx[l + T * (4 * q + 3)]);
@@ -922,32 +284,19 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     }
   }
 
-  constexpr bool RESTW = LEAN && KIND == 1 && STAGE != 1;
-  constexpr bool ILDMA_ = IB2D && IL16 && !TRO;  // (= ILDMA, defined with the prefetch buffers below)
-  // (the transposed-store variant, and every variant that multiplies by both words of the reciprocal background, is a
-  // few registers over the budget with everything resident: their 12 step-3 twiddles come from LDS every row)
-  constexpr int RES2 = !RESTW ? 0 : (TRO ? 0 : (PREC ? (IL16 ? ((IB2D && !ILDMA_) ? FDOCT_PREC16_T2_IB2D : (ILDMA_ ? FDOCT_PREC16_T2_DMA : FDOCT_PREC16_T2)) : FDOCT_PREC_T2) : 12));
-  // (the transposed store with a full-frame background and both words holds 48 prefetch registers: its step-5 twiddles come
-  // from LDS too, or the row loop spills)
-  constexpr bool RES3 = RESTW && !(TRO && IB2D && IL16);
-  v2f r_t2[RES2 ? RES2 : 1], r_t3[RES3 ? 15 : 1];
-  if constexpr (RES2 > 0 || RES3) {
+  v2f r_t2[X::RES2 ? X::RES2 : 1], r_t3[X::RES3 ? 15 : 1];
+  if constexpr (X::RES2 > 0 || X::RES3) {
     v2f t2tmp[12], t3tmp[15];
     fft1024_rowswap_twiddles(lane, tw_p2, tw_p3, t2tmp, t3tmp);
-    if constexpr (RES2 > 0) {
+    if constexpr (X::RES2 > 0) {
 #pragma unroll
-      for (int i = 0; i < RES2; i++) r_t2[i] = t2tmp[i];
+      for (int i = 0; i < X::RES2; i++) r_t2[i] = t2tmp[i];
     }
-    if constexpr (RES3) {
+    if constexpr (X::RES3) {
 #pragma unroll
       for (int i = 0; i < 15; i++) r_t3[i] = t3tmp[i];
     }
   }
-  constexpr bool RESC = RES;
-  static_assert(TW3_LDS || RES3, "the step-5 table stays out of LDS only where its entries are resident");
-  static_assert(GI_LDS || GRES, "the gather table stays out of LDS only where its addresses are resident");
-  static_assert(!(IB2D || NORM) || (fused_resident_consts(KIND, LEAN, AVG, WCH, STAGE) && STAGE == 0),
-                "fast-path options: resident-constant kernels only");
   // NORM: scale/shift of input frame (o / H) * A + ai (host guarantees rows < 2^31)
   float nsc = 1.f, nsh = 0.f, nmn = 0.f;
   auto frame_scale = [&](long long o, int ai) {
@@ -959,85 +308,34 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       nmn = mmx.x;
     }
   };
-  v2f r_ib[RESC ? NPR : 1], r_win[RESC ? NPR : 1], r_g[RESC ? NPR : 1];
-  // IB2D + both words: the half-float pattern of the same background row is prefetched with it -- into a per-wave LDS slot by
-  // the global -> LDS loads of gfx950 (global_load_lds_dwordx4: no registers held through the transform; ILDMA), or, where the
-  // LDS belongs to the ring of the transposed store, into 16 registers
-  constexpr bool ILDMA = IB2D && IL16 && !TRO;
-  uint4 r_il16[(IB2D && IL16 && !ILDMA) ? WCH : 1];
+  v2f r_ib[X::RES ? X::NPR : 1], r_win[X::RES ? X::NPR : 1], r_g[X::RES ? X::NPR : 1];
+  uint4 r_il16[(IB2D && X::IL16 && !X::ILDMA) ? WCH : 1];
   // (the slots lie behind the waves' row buffers: 2 WC bytes each)
-  unsigned char* const il_dma = scratch0 + (size_t)(blockDim.x >> 6) * RPW * a.scratch_bytes + (size_t)wave * (2 * WC);
-  // The averaging fast-path kernels with more than 32 samples per lane (C4): the half-float pattern of the second word stays
-  // RESIDENT -- 4 registers per chunk, loaded once per wave (the kernel has them to spare since the low words' source became a
-  // compile-time property) -- instead of sixteen 16-byte loads of the float low words per input A-scan from the global plane.
-  constexpr bool IL16R = LEAN && PRECT && fused_il_global(LEAN, AVG, WCH, T) && STAGE != 2;
-  uint4 r_il16r[IL16R ? WCH : 1];
-  if constexpr (IL16R) {
+  unsigned char* const il_dma = scratch0 + (size_t)(blockDim.x >> 6) * X::RPW * a.scratch_bytes + (size_t)wave * (2 * X::WC);
+  uint4 r_il16r[X::IL16R ? WCH : 1];
+  if constexpr (X::IL16R) {
     const uint4* h4 = reinterpret_cast<const uint4*>(a.il16) + l;
 #pragma unroll
     for (int c = 0; c < WCH; c++) r_il16r[c] = h4[T * c];
   }
-  // IB2D: (re)load r_ib with the reciprocal-background row of output row o (any o: rows repeat every H)
-  auto issue_ib2d = [&](long long o) {
-    if constexpr (IB2D) {
-      const unsigned rr = (o < a.total_out_rows) ? (unsigned)o % (unsigned)a.H : 0u;  // host guarantees rows < 2^31
-      const float4* p4 = reinterpret_cast<const float4*>(a.ib2d + (size_t)rr * WC + 8 * l);
-#pragma unroll
-      for (int c = 0; c < WCH; c++) {
-        const float4 q0 = p4[2 * T * c], q1 = p4[2 * T * c + 1];
-        r_ib[4 * c + 0] = mk(q0.x, q0.y);
-        r_ib[4 * c + 1] = mk(q0.z, q0.w);
-        r_ib[4 * c + 2] = mk(q1.x, q1.y);
-        r_ib[4 * c + 3] = mk(q1.z, q1.w);
-      }
-      if constexpr (ILDMA) {
-        typedef const __attribute__((address_space(1))) void* gptr_t;
-        typedef __attribute__((address_space(3))) void* lptr_t;
-        const uint4* h4 = reinterpret_cast<const uint4*>(a.il16_2d) + (size_t)rr * (WC / 8) + l;
-#pragma unroll
-        for (int c = 0; c < WCH; c++)   // lane l's 16 bytes of chunk c land at slot + (c T + l) 16: the order the row top reads them in
-          __builtin_amdgcn_global_load_lds((gptr_t)(h4 + T * c), (lptr_t)(il_dma + c * T * 16), 16, 0, 0);
-      } else if constexpr (IL16) {
-        const uint4* h4 = reinterpret_cast<const uint4*>(a.il16_2d) + (size_t)rr * (WC / 8) + l;
-#pragma unroll
-        for (int c = 0; c < WCH; c++) r_il16[c] = h4[T * c];
-      }
-    }
-  };
-  if constexpr (RESC) {
+  if constexpr (X::RES) {
     // straight from the global tables (W == WC here), 32 bytes per lane and chunk, into the pair order
-    auto load_plane = [&](const float* tab, int c, v2f* out) {
-      const float4* p4 = reinterpret_cast<const float4*>(tab + 8 * (l + T * c));
-      const float4 q0 = p4[0], q1 = p4[1];
-      out[0] = mk(q0.x, q0.z);
-      out[1] = mk(q1.x, q1.z);
-      out[2] = mk(q0.y, q0.w);
-      out[3] = mk(q1.y, q1.w);
-    };
 #pragma unroll
     for (int c = 0; c < WCH; c++) {
-      if constexpr (!IB2D) load_plane(a.ib, c, r_ib + 4 * c);
-      load_plane(a.win, c, r_win + 4 * c);
-      load_plane(a.g, c, r_g + 4 * c);
+      if constexpr (!IB2D) load_plane<T>(a.ib, c, r_ib + 4 * c, l);
+      load_plane<T>(a.win, c, r_win + 4 * c, l);
+      load_plane<T>(a.g, c, r_g + 4 * c, l);
     }
   }
 
   const long long total = a.total_out_rows;
-  // Row slots: slot s of this workgroup is rows (s*gridDim.x + blockIdx.x)*RPW .. +RPW-1, so the chip sweeps the
-  // batch front to back.  Waves take slots from a workgroup-wide ticket counter instead of a fixed stride: the
-  // hardware favours the oldest wave of a SIMD, which with a static split finishes its share long before its
-  // younger sibling and leaves the SIMD with one wave for the last quarter of the launch.
-  // The ticket is claimed a row's work before it is consumed: at the row top for the prefetch in mid-row, or -- in
-  // the FFT-stage kernel, which prefetches at the row top -- one whole row ahead (EARLY).
-  constexpr bool EARLY = STAGE == 2;
-  auto slot_row = [&](unsigned s) { return ((long long)s * gridDim.x + blockIdx.x) * RPW; };
-  // TRIM kernels: the add is written out as the instruction, with its wait.  As an atomic builtin inside `if (lane == 0)` the
+  // The row ticket (row slots: fdoct_fused_row.h).  TRIM kernels: the add is written out as the instruction, with its wait.  As an atomic builtin inside `if (lane == 0)` the
   // compiler's atomic optimiser elects a lane a second time (v_mbcnt twice, a compare, a count of exec, a second exec mask and
   // branch, a v_readfirstlane and an add of the lane's rank) for a wave that has one lane left.  The other kernels keep the
   // builtin, where the compiler is free to place the wait (see TRIM).
   auto claim = [&]() -> unsigned {
     unsigned t = 0;
-    if constexpr (!TRIM) {
+    if constexpr (!X::TRIM) {
       if (lane == 0) t = __hip_atomic_fetch_add(&row_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     } else if (lane == 0) {
       const unsigned at = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned*)&row_ticket;
@@ -1050,51 +348,15 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   // (An asm ds_add_rtn_u32 whose result stays in flight until it is needed would save the LDS round trip the compiler
   // waits out here at every row top -- about 0.5 % -- but nothing stops the register allocator from copying the
   // not-yet-written result register in the instantiations that are short of registers; tried and withdrawn.)
-  auto ticket_value = [&](unsigned t) -> unsigned { return (unsigned)__builtin_amdgcn_readfirstlane((int)t); };
-  // one row per wave (T == 64): everything row-related is wave-uniform; saying so keeps the 64-bit row arithmetic on the
-  // scalar unit (the compiler cannot see it through the loop-carried ticket)
-  auto uni64 = [&](long long v) -> long long {
-    if constexpr (RPW == 1) {
-      const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)v);
-      const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32));
-      return (long long)(((unsigned long long)hi << 32) | lo);
-    } else {
-      return v;
-    }
-  };
-  // TRO: ticket t of this workgroup is row t % TR of its tile t / TR (the missing rows of a short tile use up tickets that
-  // name no row).
-  struct TroRow {
-    unsigned t, tq, rt, g, r0, nrows;  // ticket, workgroup tile number, row in tile, B-scan, first row of the tile in the B-scan, rows of the tile
-    bool dummy;                        // (four rows per wave) a short tile has no rows for this wave: it recomputes rows of the tile and stores nothing
-  };
-  // (RPW > 1, round 6: a claim names RPW consecutive rows -- RPW divides the tile and, host-checked, the frame height, so the
-  // rows of a claim are all there or all missing; t, rt count ROWS: the first row of the claim)
-  auto tro_map = [&](unsigned tc, TroRow& tr) -> int {  // tc: the claimed ticket.  0: rows; 1: no such rows in this (short) tile; 2: past the end of the batch
-    const unsigned t = tc * (unsigned)RPW;
-    tr.t = t;
-    tr.tq = t / TR;
-    tr.rt = t % TR;
-    if (!tro_tile(tr.tq, tr.g, tr.r0, tr.nrows)) return 2;
-    return tr.rt < tr.nrows ? 0 : 1;
-  };
-  auto tro_take = [&](unsigned t, TroRow& tr) -> long long {  // t: a claimed ticket (uniform); claims on while tickets name no row
-    for (;;) {
-      const int k = tro_map(t, tr);
-      if (k == 0) return (long long)tr.g * a.H + (tr.r0 + tr.rt);
-      if (k == 2) return a.total_out_rows;
-      t = ticket_value(claim());
-    }
-  };
   // ---- four rows per wave: tiles are owned by GROUPS of four waves (see grp_* above).  Wave m of a group takes rows 4 m .. 4 m + 3
   // of the group's tile; in a short last tile of a B-scan (4, 8 or 12 rows) the waves without rows recompute rows of the tile and
   // deposit nothing, so that every wave of a group walks through the same two meetings per tile.
-  const unsigned grp = (unsigned)wave / GW, mem = (unsigned)wave % GW;
+  const unsigned grp = (unsigned)wave / X::GW, mem = (unsigned)wave % X::GW;
   unsigned grp_seq = 0u;   // tiles this group has finished
   auto grp_rows = [&](unsigned tq, TroRow& tr) -> long long {
     tr.t = 0u;
     tr.tq = tq;
-    if (!tro_tile(tq, tr.g, tr.r0, tr.nrows)) return a.total_out_rows;
+    if (!tro.tile(tq, tr.g, tr.r0, tr.nrows)) return a.total_out_rows;
     const unsigned rt = 4u * mem;
     tr.dummy = rt >= tr.nrows;
     tr.rt = tr.dummy ? rt % tr.nrows : rt;
@@ -1139,23 +401,16 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   };
   TroRow tro_cur{}, tro_next{};
   long long o_wave;  // wave-uniform
-  if constexpr (TRO_INPLACE)
+  if constexpr (X::TRO_INPLACE)
     o_wave = grp_rows(grp, tro_cur);   // the groups' first tiles are their indices (row_ticket starts behind them)
   else if constexpr (TRO)
-    o_wave = tro_take((unsigned)wave, tro_cur);
+    o_wave = tro.take((unsigned)wave, tro_cur, claim);
   else
-    o_wave = slot_row((unsigned)wave);
-  auto claim_row = [&]() -> unsigned {   // (four rows per wave: only a group's leader claims -- tiles, not rows)
-    if constexpr (TRO_INPLACE) return mem == 0u ? claim() : 0u;
-    return claim();
-  };
-  unsigned ticket = EARLY ? claim_row() : 0u;
+    o_wave = slot_row<X>((unsigned)wave);
+  unsigned ticket = X::EARLY ? claim_row<X>(claim, mem) : 0u;
 
-  const int W = LEAN ? WC : a.W;
-  // staging layout (even/odd sample planes when the gather stride is about 2): fixed by the plan on the fast path,
-  // where W == WC and N == NC or 2 NC (the same rule as the host's select_plan)
-  constexpr bool SPLIT_LEAN = (2 * WC >= 3 * NC) && (WC <= 3 * NC);
-  const bool split = LEAN ? SPLIT_LEAN : (a.split != 0);
+  const int W = LEAN ? X::WC : a.W;
+  const bool split = LEAN ? X::SPLIT_LEAN : (a.split != 0);
   const int A = AVG ? a.A : 1;  // AVG == false: compiled for one frame per output (no frame arithmetic at all)
   const unsigned char* frames = static_cast<const unsigned char*>(a.frames);
   const int i0l = 8 * l;  // this lane's sample offset inside a chunk
@@ -1171,7 +426,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         in_row = (g * A + avg_i) * (long long)a.H + (o - g * a.H);
       }
     }
-    const void* row = frames + uni64(in_row) * a.pitch_bytes;
+    const void* row = frames + uni64<X>(in_row) * a.pitch_bytes;
 #pragma unroll
     for (int c = 0; c < WCH; c++) {
       const int i0 = i0l + 8 * T * c;
@@ -1187,7 +442,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   // vmcnt(0) with the loads as the youngest VMEM operations, and the stores that follow get a
   // whole row of work to drain.  A wait at the loop top would also wait for those stores.
   // STAGE 2 streams the packed k-linear rows instead of camera samples
-  v2f znext[STAGE == 2 ? P : 1];
+  v2f znext[STAGE == 2 ? X::P : 1];
   auto issue_zloads = [&](long long o, int avg_i) {
     if constexpr (STAGE == 2) {
       const bool valid = o < total;
@@ -1198,24 +453,17 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
           in_row = (g * A + avg_i) * (long long)a.H + (o - g * a.H);
         }
       }
-      const v2f* zr = reinterpret_cast<const v2f*>(a.ylin) + uni64(in_row) * NC + l;
+      const v2f* zr = reinterpret_cast<const v2f*>(a.ylin) + uni64<X>(in_row) * X::NC + l;
 #pragma unroll
-      for (int m = 0; m < P; m++) znext[m] = valid ? __builtin_nontemporal_load(zr + T * m) : mk(0.f, 0.f);
+      for (int m = 0; m < X::P; m++) znext[m] = valid ? __builtin_nontemporal_load(zr + T * m) : mk(0.f, 0.f);
     }
   };
-  // Two-word division on the fast-path kernels with at most 32 samples per lane (PREC): the 32 low words of a lane are
-  // row-invariant, but there is no register to keep them in through the transform; they are read from the workgroup's LDS
-  // plane at every row top (ilx).  (Re-loading them from a global plane behind the previous pass's magnitudes instead -- older
-  // than the row's stores, so that the wait never includes a store -- was measured and lost: 489-491 against 509 M A-scans/s
-  // on C2, tools/ab.sh.  The LDS-bound averaging kernels with more samples per lane do read them from global memory: prec == 3.)
-  constexpr bool ILX = PREC && LEAN && WCH <= 4;
-  static_assert(!IL16 || ILX, "half-float second word: the kernels that read the row's low words at its top");
-  v2f ilx[(ILX && !IL16) ? NPR : 1];
-  uint4 ilh[IL16 ? WCH : 1];  // IL16: chunk c's four half-float pairs (pair q = dword q), 16 registers instead of 32
+  v2f ilx[(X::ILX && !X::IL16) ? X::NPR : 1];
+  uint4 ilh[X::IL16 ? WCH : 1];  // IL16: chunk c's four half-float pairs (pair q = dword q), 16 registers instead of 32
   if (o_wave < total) {
     // (the first row like every later one: the full-frame background's rows -- and the global -> LDS load of its half-float
     // pattern -- are issued BEFORE the samples, so that a wait for the samples covers them: loads return in order)
-    issue_ib2d(o_wave + sub);
+    issue_ib2d<X>(a, o_wave + sub, r_ib, r_il16, il_dma, l);
     if constexpr (STAGE == 2)
       issue_zloads(o_wave + sub, 0);
     else
@@ -1229,15 +477,15 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
   pr.start();
 #endif
   while (o_wave < total) {
-    o_wave = uni64(o_wave);
+    o_wave = uni64<X>(o_wave);
     const long long o = o_wave + sub;
     const bool valid = o < total;
     long long o_next = total;
-    if constexpr (EARLY) {
-      o_next = slot_row(ticket_value(ticket));  // claimed one row ago
-      ticket = claim_row();
+    if constexpr (X::EARLY) {
+      o_next = slot_row<X>(ticket_value(ticket));  // claimed one row ago
+      ticket = claim_row<X>(claim, mem);
     } else {
-      ticket = claim_row();  // back long before the prefetch below needs it
+      ticket = claim_row<X>(claim, mem);  // back long before the prefetch below needs it
     }
     long long gi = 0;  // output group (frame when A == 1) and row inside the frame
     int r = 0;
@@ -1248,15 +496,15 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       }
     }
 
-    float acc[P];
+    float acc[X::P];
 #pragma unroll
-    for (int m = 0; m < P; m++) acc[m] = 0.f;
+    for (int m = 0; m < X::P; m++) acc[m] = 0.f;
 
     for (int ai = 0; ai < A; ai++) {
-      v2f z[P];
+      v2f z[X::P];
       if constexpr (STAGE == 2) {
 #pragma unroll
-        for (int m = 0; m < P; m++) z[m] = znext[m];
+        for (int m = 0; m < X::P; m++) z[m] = znext[m];
         if (ai + 1 < A)
           issue_zloads(o, ai + 1);
         else
@@ -1265,8 +513,8 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       // ---------------- A2: dark, normalise, pi frame, background
       // (fast path, low words of the reciprocal background in LDS: their reads are issued here, ahead of everything the row
       // does with them -- the samples are still packed, so this is where registers are to spare)
-      if constexpr (IL16) {
-        if constexpr (ILDMA) {
+      if constexpr (X::IL16) {
+        if constexpr (X::ILDMA) {
           // The slot was filled by global_load_lds a row ago.  Explicit wait, not the compiler's own tracking of
           // LDS writes by that instruction: the samples in `raw` were issued AFTER the DMA and loads return in order, so an
           // empty asm that consumes a sample register makes the compiler wait for it here, and its memory clobber keeps the
@@ -1284,38 +532,34 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
 #pragma unroll
           for (int c = 0; c < WCH; c++) ilh[c] = h4[T * c];
         }
-      } else if constexpr (ILX) {
+      } else if constexpr (X::ILX) {
 #pragma unroll
         for (int c = 0; c < WCH; c++) load_consts<T>(c_il + c0l, c, ilx + 4 * c);
       }
-      v2f v[NPR];  // sample pairs: v[4c+q] = samples 8*(l+T*c) + chunk_pair_offset(q), +2
+      v2f v[X::NPR];  // sample pairs: v[4c+q] = samples 8*(l+T*c) + chunk_pair_offset(q), +2
 #pragma unroll
       for (int c = 0; c < WCH; c++) raw[c].unpack(v + 4 * c);
-      // Fast-path normalisations.  With the two-word division (PREC) the normalised sample p = (v - min) * scale is carried as two
-      // floats as well -- rounding it is a rounding at the size of the DC level, random from sample to sample -- and formed
-      // inside the division below (NPREC: v stays the camera sample here, nmn / nsc are the row's or the frame's).
-      constexpr bool NPREC = NORM != 0 && PREC;
-      if constexpr (NORM == 1 && !NPREC) {  // main:1128-1129, same expression as the general kernel below
+      // Fast-path normalisations (NPREC: formed inside the division below; v stays the camera sample here)
+      if constexpr (NORM == 1 && !X::NPREC) {  // main:1128-1129, same expression as the general kernel below
 #pragma unroll
-        for (int i = 0; i < NPR; i++) v[i] = pk_fma(v[i], mk(nsc, nsc), mk(nsh, nsh));
+        for (int i = 0; i < X::NPR; i++) v[i] = pk_fma(v[i], mk(nsc, nsc), mk(nsh, nsh));
       }
       if constexpr (NORM == 2) {  // main:88-97, 1126: the general kernel's row-wise normalisation, W == WC here
         float mn = INFINITY, mx = -INFINITY;
 #pragma unroll
-        for (int i = 0; i < NPR; i++) {
-          mn = fminf(mn, fminf(v[i].x, v[i].y));
-          mx = fmaxf(mx, fmaxf(v[i].x, v[i].y));
+        for (int i = 0; i < X::NPR; i++) {
+          pair_minmax(v[i], mn, mx);
         }
         mn = group_min<T>(mn);
         mx = group_max<T>(mx);
         const float sc = (mx - mn > 2.220446049250313e-16f) ? 1.f / (mx - mn) : 0.f;
-        if constexpr (NPREC) {
+        if constexpr (X::NPREC) {
           nmn = mn;
           nsc = sc;
         } else {
           const float sh = -mn * sc;
 #pragma unroll
-          for (int i = 0; i < NPR; i++) v[i] = pk_fma(v[i], mk(sc, sc), mk(sh, sh));
+          for (int i = 0; i < X::NPR; i++) v[i] = pk_fma(v[i], mk(sc, sc), mk(sh, sh));
         }
       }
 
@@ -1340,8 +584,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             if (i0l + 8 * T * c < W) {
 #pragma unroll
               for (int p = 0; p < 4; p++) {
-                mn = fminf(mn, fminf(v[4 * c + p].x, v[4 * c + p].y));
-                mx = fmaxf(mx, fmaxf(v[4 * c + p].x, v[4 * c + p].y));
+                pair_minmax(v[4 * c + p], mn, mx);
               }
             }
           }
@@ -1366,9 +609,9 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       // instructions per sample pair instead of four.  Sample 0 has slopes[0] = slopes[1] (main:1161):
       // a_0 = (1 - g_0) w_0, b_0 = +g_0 w_1, and t_1 stands in for t_(-1).
       float mh = 0.f, ml = 0.f;
-      v2f av[NPR], bv[NPR];
+      v2f av[X::NPR], bv[X::NPR];
       if (!FDOCT_ABL(1)) {
-        v2f ibv[NPR];
+        v2f ibv[X::NPR];
         bool from_lds = true;
         if constexpr (!LEAN) {
           if (a.ib2d) {
@@ -1377,12 +620,9 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             for (int c = 0; c < WCH; c++) {
               const int i0 = i0l + 8 * T * c;
               if (i0 < W) {
-                const float4* p4 = reinterpret_cast<const float4*>(a.ib2d + (size_t)r * WC + i0);  // rows are padded to WC
+                const float4* p4 = reinterpret_cast<const float4*>(a.ib2d + (size_t)r * X::WC + i0);  // rows are padded to WC
                 const float4 q0 = p4[0], q1 = p4[1];
-                ibv[4 * c + 0] = mk(q0.x, q0.y);  // a.ib2d holds each 8-sample group evens first, then odds
-                ibv[4 * c + 1] = mk(q0.z, q0.w);
-                ibv[4 * c + 2] = mk(q1.x, q1.y);
-                ibv[4 * c + 3] = mk(q1.z, q1.w);
+                evens_odds_pairs(q0, q1, ibv + 4 * c);  // a.ib2d holds each 8-sample group evens first, then odds
               } else {
 #pragma unroll
                 for (int p = 0; p < 4; p++) ibv[4 * c + p] = mk(0.f, 0.f);
@@ -1393,11 +633,10 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         // fast path with at most 32 samples per lane: 1/background stays in registers through the sum and the
         // subtraction (resident, or read once from the LDS plane), so x is never formed -- the row sum is accumulated
         // by fma (four chains), t = fma(v, 1/yb, -mh) - ml rounds once, and the mean needs no f64
-        constexpr bool FMAX = LEAN && WCH <= 4;
-        if constexpr (FMAX) {
-          if constexpr (RESC) {
+        if constexpr (X::FMAX) {
+          if constexpr (X::RES) {
 #pragma unroll
-            for (int i = 0; i < NPR; i++) ibv[i] = r_ib[i];
+            for (int i = 0; i < X::NPR; i++) ibv[i] = r_ib[i];
           } else {
 #pragma unroll
             for (int c = 0; c < WCH; c++) load_consts<T>(c_ib + c0l, c, ibv + 4 * c);
@@ -1416,42 +655,33 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
           // workgroup's LDS plane (there is no register left to keep them resident), read at the row top (ilx).
           // (the 64 samples 8 l of the first chunk.  The middle chunk was tried in round 6 -- it is what the any-option kernel below
           // takes its single-chunk estimate from -- and left C2's flat 1e-3 dB pass rate at 0.9999 instead of 1: kept as it was.)
-          const float c0 = group_sum_f32<T, TRIM>((NPREC ? (v[0].x - nmn) * nsc : v[0].x) * ibv[0].x) * (1.f / (float)T);
+          const float c0 = group_sum_f32<T, X::TRIM>((X::NPREC ? (v[0].x - nmn) * nsc : v[0].x) * ibv[0].x) * (1.f / (float)T);
           // IL16: what the first word leaves out, v * il = (v * ib) * rho = (c0 + d) * rho with rho = il / ib (|rho| <= 2^-24), is
           // c0 * rho up to d * rho -- below the rounding of d.  rho * 2^38 comes as half floats (ten bits of a correction that is
           // 8 x the tolerance at fringes of 1e-3 of the DC level), v_fma_mix_f32 converts them inside the fma.
-          const float c0s = c0 * 3.637978807091713e-12f;  // 2^-38 (kPrec16Shift)
-          auto second_word = [&](v2f d, int i) -> v2f {
-            if constexpr (IL16) {
-              const uint4 hq = ilh[i >> 2];
-              const uint32_t hp = (i & 3) == 0 ? hq.x : (i & 3) == 1 ? hq.y : (i & 3) == 2 ? hq.z : hq.w;
-              return mk(fma_mix_lo(c0s, hp, d.x), fma_mix_hi(c0s, hp, d.y));
-            } else {
-              return d;
-            }
-          };
-          if constexpr (NPREC) {
+          const float c0s = c0 * kTwoPowMinus38;
+          if constexpr (X::NPREC) {
             // p = (v - min) * scale as two floats (v - min is exact on the camera's integer samples; p_lo = the product's exact
             // residual), times ib + il: nothing of normalise-and-divide rounds at the size of the DC level
 #pragma unroll
-            for (int i = 0; i < NPR; i++) {
+            for (int i = 0; i < X::NPR; i++) {
               const v2f vm = v[i] - mk(nmn, nmn);
               const v2f ph = vm * mk(nsc, nsc);
               const v2f pl = pk_fma(vm, mk(nsc, nsc), -ph);
-              if constexpr (IL16)
-                v[i] = pk_fma(pl, ibv[i], second_word(pk_fma(ph, ibv[i], mk(-c0, -c0)), i));
+              if constexpr (X::IL16)
+                v[i] = pk_fma(pl, ibv[i], second_word<X>(ilh, c0s, pk_fma(ph, ibv[i], mk(-c0, -c0)), i));
               else
                 v[i] = pk_fma(pl, ibv[i], pk_fma(ph, ilx[i], pk_fma(ph, ibv[i], mk(-c0, -c0))));
             }
-          } else if constexpr (IL16) {
+          } else if constexpr (X::IL16) {
 #pragma unroll
-            for (int i = 0; i < NPR; i++) v[i] = second_word(pk_fma(v[i], ibv[i], mk(-c0, -c0)), i);
-          } else if constexpr (PREC) {
+            for (int i = 0; i < X::NPR; i++) v[i] = second_word<X>(ilh, c0s, pk_fma(v[i], ibv[i], mk(-c0, -c0)), i);
+          } else if constexpr (X::PREC) {
 #pragma unroll
-            for (int i = 0; i < NPR; i++) v[i] = pk_fma(v[i], ilx[i], pk_fma(v[i], ibv[i], mk(-c0, -c0)));
+            for (int i = 0; i < X::NPR; i++) v[i] = pk_fma(v[i], ilx[i], pk_fma(v[i], ibv[i], mk(-c0, -c0)));
           } else {
 #pragma unroll
-            for (int i = 0; i < NPR; i++) v[i] = pk_fma(v[i], ibv[i], mk(-c0, -c0));
+            for (int i = 0; i < X::NPR; i++) v[i] = pk_fma(v[i], ibv[i], mk(-c0, -c0));
           }
           v2f s4[4] = {v[0], v[1], v[2], v[3]};
 #pragma unroll
@@ -1460,10 +690,10 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             for (int p = 0; p < 4; p++) s4[p] += v[4 * c + p];
           }
           const v2f part = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-          mh = group_sum_f32<T, TRIM>(part.x + part.y) * (1.f / (float)WC);  // mean of d (W == WC on this path)
-          if constexpr (RESC) {
+          mh = group_sum_f32<T, X::TRIM>(part.x + part.y) * (1.f / (float)X::WC);  // mean of d (W == WC on this path)
+          if constexpr (X::RES) {
 #pragma unroll
-            for (int i = 0; i < NPR; i++) {
+            for (int i = 0; i < X::NPR; i++) {
               av[i] = r_win[i];
               bv[i] = r_g[i];
             }
@@ -1472,7 +702,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             for (int c = 0; c < WCH; c++) load_consts<T>(c_g + c0l, c, bv + 4 * c);
           }
 #pragma unroll
-          for (int i = 0; i < NPR; i++) v[i] -= mk(mh, mh);
+          for (int i = 0; i < X::NPR; i++) v[i] -= mk(mh, mh);
         } else {
           // WCH <= 4: all reciprocal-background reads are issued up front (one LDS wait); wider rows read
           // them chunk by chunk to stay inside the register budget
@@ -1481,14 +711,13 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             for (int c = 0; c < WCH; c++) load_consts<T>(c_ib + c0l, c, ibv + 4 * c);
           }
           double sum = 0.0;
-          constexpr bool CMEAN = LEAN;  // the fast-path rows that are too wide for the block above (C4, C1): the same mean, see there
           float c0 = 0.f;
           [[maybe_unused]] bool have_c0 = false;
           v2f s4[4] = {mk(0.f, 0.f), mk(0.f, 0.f), mk(0.f, 0.f), mk(0.f, 0.f)};
 #pragma unroll
           for (int cc = 0; cc < WCH; cc++) {
             // (any-option kernel: the chunks from the MIDDLE of the row on -- c0 comes from the first chunk taken, see below)
-            const int c = CMEAN ? cc : (cc + WCH / 2) % WCH;
+            const int c = X::CMEAN ? cc : (cc + WCH / 2) % WCH;
             if (from_lds && WCH > 4) load_consts<T>(c_ib + c0l, c, ibv + 4 * c);
             // low words of 1/background (see the block above): from the LDS plane, or -- full-frame background -- from the
             // frame's own row in global memory
@@ -1496,37 +725,34 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             // kernel and host: a run-time branch on a.prec here made the compiler zero and merge the eight registers of every
             // chunk, 130 v_mov per input A-scan of C4 -- round 5)
             v2f ilv[4] = {mk(0.f, 0.f), mk(0.f, 0.f), mk(0.f, 0.f), mk(0.f, 0.f)};
-            if constexpr (IL16R) {
+            if constexpr (X::IL16R) {
               // (resident half-float pattern: applied below as c0 * rho)
-            } else if constexpr (LEAN && PREC && fused_il_global(LEAN, AVG, WCH, T)) {
+            } else if constexpr (LEAN && X::PREC && fused_il_global(LEAN, AVG, WCH, T)) {
               // (averaging fast-path kernels that are short of LDS: the same plane, in the same order, from global memory -- L1 / L2
               // hits; the wave's stores, which such a load would have to wait behind, come once per A input rows there)
               load_consts<T>(a.ilp + c0l, c, ilv);
-            } else if constexpr (LEAN && PREC) {
+            } else if constexpr (LEAN && X::PREC) {
               load_consts<T>(c_il + c0l, c, ilv);
             } else if (!LEAN && a.prec == 1) {
               load_consts<T>(c_il + c0l, c, ilv);
             } else if constexpr (!LEAN) {
               if (a.prec == 2 && i0l + 8 * T * c < W) {
-                const float4* p4 = reinterpret_cast<const float4*>(a.il2d + (size_t)r * WC + i0l + 8 * T * c);
+                const float4* p4 = reinterpret_cast<const float4*>(a.il2d + (size_t)r * X::WC + i0l + 8 * T * c);
                 const float4 q0 = p4[0], q1 = p4[1];
-                ilv[0] = mk(q0.x, q0.y);
-                ilv[1] = mk(q0.z, q0.w);
-                ilv[2] = mk(q1.x, q1.y);
-                ilv[3] = mk(q1.z, q1.w);
+                evens_odds_pairs(q0, q1, ilv);
               }
             }
-            if constexpr (CMEAN) {
-              if (c == 0) c0 = group_sum_f32<T, TRIM>(v[0].x * ibv[0].x) * (1.f / (float)T);
-              if constexpr (IL16R) {   // what the first word leaves out is c0 * rho up to d * rho (see the fast path above)
-                const float c0s = c0 * 3.637978807091713e-12f;  // 2^-38 (kPrec16Shift)
+            if constexpr (X::CMEAN) {
+              if (c == 0) c0 = group_sum_f32<T, X::TRIM>(v[0].x * ibv[0].x) * (1.f / (float)T);
+              if constexpr (X::IL16R) {   // what the first word leaves out is c0 * rho up to d * rho (see the fast path above)
+                const float c0s = c0 * kTwoPowMinus38;
                 const uint32_t hq[4] = {r_il16r[c].x, r_il16r[c].y, r_il16r[c].z, r_il16r[c].w};
 #pragma unroll
                 for (int p = 0; p < 4; p++) {
                   const v2f d = pk_fma(v[4 * c + p], ibv[4 * c + p], mk(-c0, -c0));
                   v[4 * c + p] = mk(fma_mix_lo(c0s, hq[p], d.x), fma_mix_hi(c0s, hq[p], d.y));
                 }
-              } else if constexpr (PREC) {
+              } else if constexpr (X::PREC) {
 #pragma unroll
                 for (int p = 0; p < 4; p++) v[4 * c + p] = pk_fma(v[4 * c + p], ilv[p], pk_fma(v[4 * c + p], ibv[4 * c + p], mk(-c0, -c0)));
               } else {
@@ -1591,8 +817,8 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
                 }
               }
               if (!have_c0 && (LEAN || 8 * T * c < W)) {
-                const float cnt = group_sum_f32<T, TRIM>(in_row ? 1.f : 0.f);
-                c0 = group_sum_f32<T, TRIM>(in_row ? v[4 * c].x * ibv[4 * c].x : 0.f) / cnt;   // (cnt >= 1: the chunk's first lane is in the row)
+                const float cnt = group_sum_f32<T, X::TRIM>(in_row ? 1.f : 0.f);
+                c0 = group_sum_f32<T, X::TRIM>(in_row ? v[4 * c].x * ibv[4 * c].x : 0.f) / cnt;   // (cnt >= 1: the chunk's first lane is in the row)
                 have_c0 = true;
               }
 #pragma unroll
@@ -1609,9 +835,9 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             __builtin_amdgcn_sched_barrier(0);
           }
           // ---------------- A3: DC removal (mean in double; CMEAN: mean of the deviations from c0, in float)
-          if constexpr (CMEAN) {
+          if constexpr (X::CMEAN) {
             const v2f part = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-            mh = group_sum_f32<T, TRIM>(part.x + part.y) * (1.f / (float)WC);
+            mh = group_sum_f32<T, X::TRIM>(part.x + part.y) * (1.f / (float)X::WC);
             ml = 0.f;
           } else {
             sum = group_sum<T>(sum);
@@ -1624,12 +850,12 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
 #pragma unroll
             for (int c = 0; c < WCH; c++) load_consts<T>(c_g + c0l, c, bv + 4 * c);
           }
-          if constexpr (CMEAN) {
+          if constexpr (X::CMEAN) {
 #pragma unroll
-            for (int i = 0; i < NPR; i++) v[i] -= mk(mh, mh);
+            for (int i = 0; i < X::NPR; i++) v[i] -= mk(mh, mh);
           } else {
 #pragma unroll
-            for (int i = 0; i < NPR; i++) v[i] = (v[i] - mk(mh, mh)) - mk(ml, ml);
+            for (int i = 0; i < X::NPR; i++) v[i] = (v[i] - mk(mh, mh)) - mk(ml, ml);
           }
         }
       }
@@ -1642,7 +868,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         float prev_last = 0.f;  // t of the sample just before this lane's chunk
 #pragma unroll
         for (int c = 0; c < WCH; c++) {
-          if constexpr (!RESC && WCH > 4) {
+          if constexpr (!X::RES && WCH > 4) {
             load_consts<T>(c_win + c0l, c, av + 4 * c);
             load_consts<T>(c_g + c0l, c, bv + 4 * c);
           }
@@ -1671,14 +897,14 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
           if (LEAN || (i0l + 8 * T * c < W)) {
             if (split) {
               *reinterpret_cast<float4*>(stl + 4 * T * c) = make_float4(sE0.x, sE0.y, sE1.x, sE1.y);
-              *reinterpret_cast<float4*>(stl + 4 * T * c + WC / 2) = make_float4(sO0.x, sO0.y, sO1.x, sO1.y);
+              *reinterpret_cast<float4*>(stl + 4 * T * c + X::WC / 2) = make_float4(sO0.x, sO0.y, sO1.x, sO1.y);
             } else {
               *reinterpret_cast<float4*>(stl + 8 * T * c) = make_float4(sE0.x, sO0.x, sE0.y, sO0.y);
               *reinterpret_cast<float4*>(stl + 8 * T * c + 4) = make_float4(sE1.x, sO1.x, sE1.y, sO1.y);
             }
           }
         }
-        if (l == 0) stg[WC] = 0.f;  // source of data_ylin[0] and data_ylin[N-1] (defined 0)
+        if (l == 0) stg[X::WC] = 0.f;  // source of data_ylin[0] and data_ylin[N-1] (defined 0)
       }
       wave_lds_sync();
       FDOCT_FPR(pr, 1);   // window + slope step, staging stores
@@ -1689,50 +915,49 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         int na = ai + 1;
         if (na == A) {
           na = 0;
-          if constexpr (TRO_INPLACE)
+          if constexpr (X::TRO_INPLACE)
             o_next = grp_rows(grp_next_tile(ticket), tro_next);
           else if constexpr (TRO)
-            o_next = tro_take(ticket_value(ticket), tro_next);
+            o_next = tro.take(ticket_value(ticket), tro_next, claim);
           else
-            o_next = slot_row(ticket_value(ticket));
+            o_next = slot_row<X>(ticket_value(ticket));
           no = o_next + sub;
-          issue_ib2d(no);  // r_ib was consumed at the top of this pass
+          issue_ib2d<X>(a, no, r_ib, r_il16, il_dma, l);  // r_ib was consumed at the top of this pass
         }
         issue_loads(no, na);
         frame_scale(no, na);
       }
 
       // ---------------- A5 (second half) + A6: gather into FFT registers
-      static_assert(P % 4 == 0, "gather table is read four entries at a time");
-      uint32_t gsrc[P];  // packed 16-bit LDS byte offsets (relative to this row's staging buffer)
-      if constexpr (!GRES) {
+      uint32_t gsrc[X::P];  // packed 16-bit LDS byte offsets (relative to this row's staging buffer)
+      if constexpr (!X::GRES) {
         const uint4* gl4 = reinterpret_cast<const uint4*>(c_gi) + l;
 #pragma unroll
-        for (int q = 0; q < P / 4; q++) {
+        for (int q = 0; q < X::P / 4; q++) {
           const uint4 g4 = gl4[q * T];
           gsrc[4 * q + 0] = g4.x; gsrc[4 * q + 1] = g4.y; gsrc[4 * q + 2] = g4.z; gsrc[4 * q + 3] = g4.w;
         }
       }
       if (FDOCT_ABL(2)) {
 #pragma unroll
-        for (int m = 0; m < P; m++) z[m] = v[m % NPR];
+        for (int m = 0; m < X::P; m++) z[m] = v[m % X::NPR];
       } else if constexpr (CPLX) {
         const v2f* phl = c_ph + l;
 #pragma unroll
-        for (int m = 0; m < P; m++) {
+        for (int m = 0; m < X::P; m++) {
           const float y = *reinterpret_cast<const float*>(scr + (gsrc[m] & 0xffffu));
           z[m] = phl[T * m] * mk(y, y);
         }
-      } else if constexpr (GRES) {
+      } else if constexpr (X::GRES) {
 #pragma unroll
-        for (int m = 0; m < P; m++) {
+        for (int m = 0; m < X::P; m++) {
           const float zx = *reinterpret_cast<const __attribute__((address_space(3))) float*>(gaddr[2 * m]);
           const float zy = *reinterpret_cast<const __attribute__((address_space(3))) float*>(gaddr[2 * m + 1]);
           z[m] = mk(zx, zy);
         }
       } else {
 #pragma unroll
-        for (int m = 0; m < P; m++) {
+        for (int m = 0; m < X::P; m++) {
           const float zx = *reinterpret_cast<const float*>(scr + (gsrc[m] & 0xffffu));
           const float zy = *reinterpret_cast<const float*>(scr + (gsrc[m] >> 16));
           z[m] = mk(zx, zy);
@@ -1745,42 +970,42 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       if constexpr (STAGE == 1) {
         // resample stage: the packed k-linear row goes to memory, 8 bytes per lane, coalesced
         if (valid) {
-          v2f* zr = reinterpret_cast<v2f*>(a.ylin) + o * NC + l;
+          v2f* zr = reinterpret_cast<v2f*>(a.ylin) + o * X::NC + l;
 #pragma unroll
-          for (int m = 0; m < P; m++) __builtin_nontemporal_store(z[m], zr + T * m);
+          for (int m = 0; m < X::P; m++) __builtin_nontemporal_store(z[m], zr + T * m);
         }
       } else {
       // ---------------- A7: NC-point inverse DFT
       if constexpr (KIND == 1) {
-        if (!FDOCT_ABL(4)) fft1024_rowswap<RES2, RES3>(z, lane, xch, tw_p2, tw_p3, r_t2, r_t3, pr);
+        if (!FDOCT_ABL(4)) fft1024_rowswap<X::RES2, X::RES3>(z, lane, xch, tw_p2, tw_p3, r_t2, r_t3, pr);
       } else if constexpr (KIND == 2) {
         if (!FDOCT_ABL(4)) fft2048_rowswap(z, lane, xch, tw_p2, tw_p3, pr);
       } else if (!FDOCT_ABL(4)) {
-        constexpr int NTW2 = (P / R2) * (R2 - 1);
-        constexpr int NTW3 = (R3 > 1) ? (P / R3) * (R3 - 1) : 1;
-        pass_compute<NC, T, R1, 1, false, LP, true>(z, l, xch, nullptr);
+        constexpr int NTW2 = (X::P / R2) * (R2 - 1);
+        constexpr int NTW3 = (R3 > 1) ? (X::P / R3) * (R3 - 1) : 1;
+        pass_compute<X::NC, T, R1, 1, false, X::LP, true>(z, l, xch, nullptr);
         v2f tw2[NTW2];
-        pass_twiddles<NC, T, R2, R1>(tw2, l, tw_p2);  // queued behind the exchange writes
+        pass_twiddles<X::NC, T, R2, R1>(tw2, l, tw_p2);  // queued behind the exchange writes
         wave_lds_sync();
-        pass_readback<NC, T, LP>(z, l, xch);
+        pass_readback<X::NC, T, X::LP>(z, l, xch);
         wave_lds_sync();
-        if constexpr (NPASS == 3) {
-          pass_compute<NC, T, R2, R1, false, LP, true>(z, l, xch, tw2);
+        if constexpr (X::NPASS == 3) {
+          pass_compute<X::NC, T, R2, R1, false, X::LP, true>(z, l, xch, tw2);
           v2f tw3[NTW3];
-          pass_twiddles<NC, T, R3, R1 * R2>(tw3, l, tw_p3);
+          pass_twiddles<X::NC, T, R3, R1 * R2>(tw3, l, tw_p3);
           wave_lds_sync();
-          pass_readback<NC, T, LP>(z, l, xch);
+          pass_readback<X::NC, T, X::LP>(z, l, xch);
           wave_lds_sync();
-          pass_compute<NC, T, R3, R1 * R2, true, LP, true>(z, l, xch, tw3);
+          pass_compute<X::NC, T, R3, R1 * R2, true, X::LP, true>(z, l, xch, tw3);
         } else {
-          pass_compute<NC, T, R2, R1, true, LP, true>(z, l, xch, tw2);
+          pass_compute<X::NC, T, R2, R1, true, X::LP, true>(z, l, xch, tw2);
         }
       }
 
       // ---------------- A8: magnitude (+ untangle on the real path)
       if (FDOCT_ABL(32)) {
 #pragma unroll
-        for (int m = 0; m < P; m++) acc[m] += z[m].x + z[m].y;
+        for (int m = 0; m < X::P; m++) acc[m] += z[m].x + z[m].y;
       } else if constexpr (CPLX) {
         // slot m is bin l + T*m: with D <= NC/2 (the usual half-depth display) the upper half of the slots is
         // never stored, so its magnitudes (and the epilogue below) are skipped -- a wave-uniform branch
@@ -1791,78 +1016,24 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
             acc[m] = AVG ? acc[m] + fast_sqrt(q.x + q.y) : fast_sqrt(q.x + q.y);
           });
         };
-        mag_slots(IC<0>{}, IC<P / 2>{});
-        if (a.D > NC / 2) mag_slots(IC<P / 2>{}, IC<P>{});
+        mag_slots(IC<0>{}, IC<X::P / 2>{});
+        if (a.D > X::NC / 2) mag_slots(IC<X::P / 2>{}, IC<X::P>{});
       } else {
-        // Bins k and NC-k come out of the same two values: with Zp = Z[NC-k],
-        //   A = Z[k] + conj(Zp), B = Z[k] - conj(Zp), q = w^k * B:  2X[k] = A - i*q,  2|X[NC-k]| = |A + i*q|
-        // (E[NC-k] = conj E[k], O[NC-k] = conj O[k], w^(NC-k) = -conj w^k; the 1/2 is folded into the
-        // window on the host).  So each lane takes its LOWER-half registers m < P/2 (bins k = l + T*m <
-        // NC/2), fetches the partner Z[NC-k] from lane (T-l)%T -- register P-1-m there, or (P-m)%P when
-        // l == 0 -- and produces both magnitudes: half the permutes and half the arithmetic of doing
-        // every bin on its own.  acc[m] = |X[l + T*m]|, acc[P/2 + m] = |X[NC - l - T*m]|; the slot that
-        // would be bin NC (lane 0, m = 0) carries bin NC/2 (self-paired, lane 0 register P/2) instead.
-        const int plane = ((lane & ~(T - 1)) | ((T - l) & (T - 1))) << 2;  // byte address for bpermute
-        // keep the per-bin phasors utw*const from being hoisted out of the row loop (they would cost
-        // resident registers or, worse, scratch reloads): utw is opaque from here
-        v2f utw_row = utw;
-        asm volatile("" : "+v"(utw_row));
-        constexpr int PH = P / 2;
-        v2f pz[PH];
-        // every lane publishes the register its reader wants; all permutes are issued before any of
-        // the arithmetic (one LDS round trip)
-        static_for<0, PH>([&](auto mc) {
-          constexpr int m = decltype(mc)::value;
-          constexpr int pm1 = P - 1 - m;      // asked for by lane T-l' != 0
-          constexpr int pm0 = (P - m) % P;    // asked for by lane 0 (of itself)
-          const float sx = (l == 0) ? z[pm0].x : z[pm1].x;
-          const float sy = (l == 0) ? z[pm0].y : z[pm1].y;
-          pz[m] = mk(__int_as_float(__builtin_amdgcn_ds_bpermute(plane, __float_as_int(sx))),
-                     __int_as_float(__builtin_amdgcn_ds_bpermute(plane, __float_as_int(sy))));
-        });
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<0, PH>([&](auto mc) {
-          constexpr int m = decltype(mc)::value;
-          const v2f A_ = add_conj(z[m], pz[m]);
-          const v2f B_ = sub_conj(z[m], pz[m]);
-          // w^k = exp(2*pi*i*(l + T*m)/N) = utw * exp(2*pi*i*m/(2P))
-          const v2f q = cmul(twc<m, 2 * P, true>(utw_row), B_);
-          const v2f Xa = add_mulmi(A_, q);   // A - i*q
-          const v2f Xb = sub_mulmi(A_, q);   // A + i*q
-          const v2f Xa2 = Xa * Xa, Xb2 = Xb * Xb;
-          const float lo_mag = fast_sqrt(Xa2.x + Xa2.y);
-          acc[m] = AVG ? acc[m] + lo_mag : lo_mag;
-          float hi2 = Xb2.x + Xb2.y;
-          if constexpr (m == 0) {
-            // bin NC/2: Z[NC/2] = zc is its own partner and only lane 0 keeps the result, so only lane 0's phasor counts:
-            // utw = (1, +-0) there (exp of 0) and the PH/(2P) turn is an exact quarter turn.  Run through the general formula
-            // that gives  A = zc + conj(zc) = (2x, +0),  B = zc - conj(zc) = (+0, 2y),  q = i*utw*B = (-2y, +0) and
-            // X = A - i*q = (2x + 0, 0 + 2y): every step is exact (doubling is; x - x and the products with 0 are zeros,
-            // and adding a zero changes at most the sign of a zero), so X is zc + zc up to the sign of a zero component.
-            // The square discards that sign (both give +0), hence |X|^2 below has the bits the general formula had for
-            // every finite zc, zeros of either sign included -- and one square root serves both selections.
-            const v2f Xc = z[PH] + z[PH];
-            const v2f Xc2 = Xc * Xc;
-            const float mid2 = Xc2.x + Xc2.y;
-            hi2 = (l == 0) ? mid2 : hi2;
-          }
-          const float hi = fast_sqrt(hi2);
-          acc[PH + m] = AVG ? acc[PH + m] + hi : hi;
-        });
+        untangle_magnitudes<X>(z, acc, utw, lane, l);
       }
       }  // STAGE != 1
       FDOCT_FPR(pr, 8);   // untangle + magnitude (+ accumulate)
       // the prefetched samples have had this whole pass to arrive (see the comment at the first issue_loads)
       if constexpr (STAGE == 2) {
 #pragma unroll
-        for (int m = 0; m < P; m++) asm volatile("" : "+v"(znext[m]));
+        for (int m = 0; m < X::P; m++) asm volatile("" : "+v"(znext[m]));
       } else {
 #pragma unroll
         for (int c = 0; c < WCH; c++) raw[c].pin();
         if constexpr (IB2D) {
 #pragma unroll
-          for (int i = 0; i < NPR; i++) asm volatile("" : "+v"(r_ib[i]));
-          if constexpr (IL16 && !ILDMA) {
+          for (int i = 0; i < X::NPR; i++) asm volatile("" : "+v"(r_ib[i]));
+          if constexpr (X::IL16 && !X::ILDMA) {
 #pragma unroll
             for (int c = 0; c < WCH; c++) asm volatile("" : "+v"(r_il16[c].x), "+v"(r_il16[c].y), "+v"(r_il16[c].z), "+v"(r_il16[c].w));
           }
@@ -1874,10 +1045,10 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       continue;
     }
 
-    if constexpr (TRO && !TRO_INPLACE) {
+    if constexpr (TRO && !X::TRO_INPLACE) {
       // the ring slot of this row (ticket mod RS) last held the row of ticket - RS: its tile must have been written out
-      const unsigned need = tro_cur.t >= RS ? (tro_cur.t - RS) / TR + 1u : 0u;
-      const unsigned need_steps = need * ((unsigned)a.D / (unsigned)TRO_SB);
+      const unsigned need = tro_cur.t >= RS ? (tro_cur.t - RS) / X::TR + 1u : 0u;
+      const unsigned need_steps = need * ((unsigned)a.D / (unsigned)X::TRO_SB);
       // (the write-out this waits for may be this wave's own to do; the bound is the exit condition a spinning wave must
       // have all the same and is reported through a.tr_fault)
       for (unsigned spin = 0; tro_done_seen < need_steps; spin++) {
@@ -1892,8 +1063,8 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     }
     // ---------------- A9/A10: average, epsilon, dB, DC mask, store
     const int D = a.D;
-    const bool upper_slots = !CPLX || D > NC / 2;  // complex path, half-depth output: slots >= P/2 are never stored
-    float outv[P];
+    const bool upper_slots = !CPLX || D > X::NC / 2;  // complex path, half-depth output: slots >= P/2 are never stored
+    float outv[X::P];
     // (without averaging the epsilon add goes two slots to a packed add: each half rounds like the single add)
     auto add_eps = [&](auto lo_c, auto hi_c) {
       if constexpr (AVG) {
@@ -1908,12 +1079,12 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         }
       }
     };
-    add_eps(IC<0>{}, IC<P / 2>{});
+    add_eps(IC<0>{}, IC<X::P / 2>{});
     if (upper_slots) {
-      add_eps(IC<P / 2>{}, IC<P>{});
+      add_eps(IC<X::P / 2>{}, IC<X::P>{});
     } else {
 #pragma unroll
-      for (int m = P / 2; m < P; m++) outv[m] = 1.f;
+      for (int m = X::P / 2; m < X::P; m++) outv[m] = 1.f;
     }
     // slot -> depth bin.  Complex path: slot m is bin l + T*m.  Real path (see the untangle above):
     // slots m < P/2 are bins l + T*m, slots P/2 + m are bins NC - l - T*m (lane 0, m = 0: bin NC/2).
@@ -1926,30 +1097,30 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
     // wave's valid rows: the hardware drops the rows past the end of the batch and, with one row per wave, whatever lies
     // past the crop.
     auto store_row = [&](float* obase, const float* val) {
-      constexpr int NLO = CPLX ? P : P / 2;
+      constexpr int NLO = CPLX ? X::P : X::P / 2;
       constexpr bool BUF = !TRO;  // (the transposed store's rows go into LDS: plain ds_write_b32)
       // o_wave is wave-uniform by construction (slot_row of a wave-uniform ticket); say so for RPW > 1 too, or the
       // descriptor would be built per lane and the stores wrapped in a waterfall loop
       const long long ow = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(o_wave >> 32)) << 32) |
                                        (unsigned)__builtin_amdgcn_readfirstlane((int)o_wave));
       const long long left = total - ow;  // >= 1 inside the row loop
-      int nrows = left < RPW ? (int)left : RPW;
+      int nrows = left < X::RPW ? (int)left : X::RPW;
       float* wbase = obase + (size_t)ow * D;  // the wave's first row
-      float* orow = wbase + ((RPW > 1) ? (size_t)sub * D : 0);
+      float* orow = wbase + ((X::RPW > 1) ? (size_t)sub * D : 0);
       // this row's ring slot (LDS: the stores below are ds_write_b32); the RPW rows of a wave take consecutive slots (the ring
       // is a whole number of them: fused_tro_ring_pick)
-      if constexpr (TRO_INPLACE)
-        orow = reinterpret_cast<float*>(scratch0 + (size_t)(wave * RPW + sub) * a.scratch_bytes);   // the row's own buffer, free since the untangle
+      if constexpr (X::TRO_INPLACE)
+        orow = reinterpret_cast<float*>(scratch0 + (size_t)(wave * X::RPW + sub) * a.scratch_bytes);   // the row's own buffer, free since the untangle
       else if constexpr (TRO)
-        orow = tro_ring + (ring_mod(tro_cur.t) + (unsigned)sub) * tro_slot;
+        orow = tro_ring + (tro.ring_mod(tro_cur.t) + (unsigned)sub) * tro_slot;
       __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(BUF ? wbase : nullptr, 0, BUF ? nrows * D * 4 : 0, 0x00020000);
       // bin index -> store; lo(m) = bin l + T*m, hi(m) = bin NC - l - T*m, hi0 = slot P/2 (lane 0: bin NC/2)
       float* plo = orow + l;
-      float* phi = orow + (NC - l);
+      float* phi = orow + (X::NC - l);
       // per-lane byte offsets of the ascending and of the descending run; opaque to the optimiser so that "+ constant"
       // stays an add the backend folds into the instruction's immediate offset (it does not fold the `or` it would become)
-      const int vrow = (RPW > 1) ? 4 * sub * D : 0;
-      int vlo = vrow + 4 * l, vhi = vrow + 4 * (NC - T * (P / 2 - 1) - l);
+      const int vrow = (X::RPW > 1) ? 4 * sub * D : 0;
+      int vlo = vrow + 4 * l, vhi = vrow + 4 * (X::NC - T * (X::P / 2 - 1) - l);
       if constexpr (BUF) asm volatile("" : "+v"(vlo), "+v"(vhi));
       auto st_lo = [&](int m, float v) {
         if constexpr (BUF)
@@ -1959,23 +1130,23 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       };
       auto st_hi = [&](int m, float v) {
         if constexpr (BUF)
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, vhi + 4 * T * (P / 2 - 1 - m), 0, 2);
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, vhi + 4 * T * (X::P / 2 - 1 - m), 0, 2);
         else
           phi[-T * m] = v;
       };
       auto st_hi0 = [&](float v) {  // slot P/2 of lane 0 is bin NC/2
         if constexpr (BUF)
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, vrow + 4 * ((l == 0) ? NC / 2 : NC - l), 0, 2);
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, vrow + 4 * ((l == 0) ? X::NC / 2 : X::NC - l), 0, 2);
         else
-          *((l == 0) ? orow + NC / 2 : phi) = v;
+          *((l == 0) ? orow + X::NC / 2 : phi) = v;
       };
-      if (D == NC || (BUF && RPW == 1 && (D % T) != 0)) {  // full depth: nothing to crop; ragged crop of a wave-per-row plan: the hardware drops bins >= D
+      if (D == X::NC || (BUF && X::RPW == 1 && (D % T) != 0)) {  // full depth: nothing to crop; ragged crop of a wave-per-row plan: the hardware drops bins >= D
 #pragma unroll
         for (int m = 0; m < NLO; m++) st_lo(m, val[m]);
         if constexpr (!CPLX) {
           st_hi0(val[NLO]);
 #pragma unroll
-          for (int m = 1; m < P / 2; m++) st_hi(m, val[NLO + m]);
+          for (int m = 1; m < X::P / 2; m++) st_hi(m, val[NLO + m]);
         }
       } else if ((D % T) == 0) {
         // cropped to whole T-bin slots (the usual half-depth display): which slots are stored is the same for every
@@ -1985,10 +1156,10 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         for (int m = 0; m < NLO; m++)
           if (m < nfull) st_lo(m, val[m]);
         if constexpr (!CPLX) {
-          const int h = (NC - D) / T;  // >= 1: hi slot m holds bins NC - T*m - l, all below D iff m > h
-          if (((l == 0) ? NC / 2 : NC - l) < D) st_hi0(val[NLO]);
+          const int h = (X::NC - D) / T;  // >= 1: hi slot m holds bins NC - T*m - l, all below D iff m > h
+          if (((l == 0) ? X::NC / 2 : X::NC - l) < D) st_hi0(val[NLO]);
 #pragma unroll
-          for (int m = 1; m < P / 2; m++) {
+          for (int m = 1; m < X::P / 2; m++) {
             if (m > h) {
               st_hi(m, val[NLO + m]);
             } else if (m == h) {
@@ -2001,26 +1172,26 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
         for (int m = 0; m < NLO; m++)
           if (l + T * m < D) st_lo(m, val[m]);
         if constexpr (!CPLX) {
-          if (((l == 0) ? NC / 2 : NC - l) < D) st_hi0(val[NLO]);
+          if (((l == 0) ? X::NC / 2 : X::NC - l) < D) st_hi0(val[NLO]);
 #pragma unroll
-          for (int m = 1; m < P / 2; m++)
-            if (NC - l - T * m < D) st_hi(m, val[NLO + m]);
+          for (int m = 1; m < X::P / 2; m++)
+            if (X::NC - l - T * m < D) st_hi(m, val[NLO + m]);
         }
       }
     };
-    const bool deposit = valid && !(TRO_INPLACE && tro_cur.dummy);   // (a wave without rows in a short tile stores nothing)
+    const bool deposit = valid && !(X::TRO_INPLACE && tro_cur.dummy);   // (a wave without rows in a short tile stores nothing)
     if (deposit && a.out_mag && !FDOCT_ABL(128)) store_row(a.out_mag, outv);
     // (transposed store with both images asked for: the ring holds bscan, the write-out step takes the logarithm)
     if (a.out_db && !(TRO && a.out_mag)) {
-      float db[P];
+      float db[X::P];
 #pragma unroll
-      for (int m = 0; m < P / 2; m++) db[m] = FDOCT_ABL(64) ? outv[m] : a.db_scale * fast_log2(outv[m]);  // db_scale carries ln 2
+      for (int m = 0; m < X::P / 2; m++) db[m] = FDOCT_ABL(64) ? outv[m] : a.db_scale * fast_log2(outv[m]);  // db_scale carries ln 2
       if (upper_slots) {
 #pragma unroll
-        for (int m = P / 2; m < P; m++) db[m] = FDOCT_ABL(64) ? outv[m] : a.db_scale * fast_log2(outv[m]);
+        for (int m = X::P / 2; m < X::P; m++) db[m] = FDOCT_ABL(64) ? outv[m] : a.db_scale * fast_log2(outv[m]);
       } else {
 #pragma unroll
-        for (int m = P / 2; m < P; m++) db[m] = 0.f;
+        for (int m = X::P / 2; m < X::P; m++) db[m] = 0.f;
       }
       if (a.dcmask && T > 4 && D > 4) {  // (the reference indexes row 4 unconditionally; with D <= 4 there is none: no mask)
         // depth bins 0 and 1 <- bin 4 (main:1237-1238): bins 0, 1, 4 are slot 0 of lanes 0, 1, 4
@@ -2030,21 +1201,21 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       if (deposit && !FDOCT_ABL(128)) store_row(a.out_db, db);
       if (FDOCT_ABL(128)) {  // keep the values alive: without this the whole row would be dead code
 #pragma unroll
-        for (int m = 0; m < P; m++) asm volatile("" ::"v"(db[m]));
+        for (int m = 0; m < X::P; m++) asm volatile("" ::"v"(db[m]));
       }
     }
     o_wave = o_next;
     FDOCT_FPR(pr, 9);     // epilogue: average, epsilon, dB, stores (+ the transposed store's ring wait)
-    if constexpr (TRO_INPLACE) {
+    if constexpr (X::TRO_INPLACE) {
       // the wave's rows lie in its own row buffers: meet the group, write the tile out together (wave m takes steps m, m + 4, ...:
       // each step reads all sixteen rows, four of them from every wave's buffers), meet again -- nobody may start staging its
       // next rows before every wave of the group has read what it needs -- and go on
       wave_lds_sync();
-      const unsigned target = GW * (grp_seq + 1u);
+      const unsigned target = X::GW * (grp_seq + 1u);
       grp_meet(&grp_arrived[grp], target);
       asm volatile("" ::: "memory");
-      const unsigned spt = (unsigned)a.D / (unsigned)TRO_SB;
-      for (unsigned k = mem; k < spt; k += GW) tro_step(grp, tro_cur.g, tro_cur.r0, tro_cur.nrows, (int)(k * (unsigned)TRO_SB));
+      const unsigned spt = (unsigned)a.D / (unsigned)X::TRO_SB;
+      for (unsigned k = mem; k < spt; k += X::GW) tro.step(grp, tro_cur.g, tro_cur.r0, tro_cur.nrows, (int)(k * (unsigned)X::TRO_SB));
       asm volatile("" ::: "memory");   // the steps' LDS reads have returned (they fed stores that have been issued)
       wave_lds_sync();
       grp_meet(&grp_done[grp], target);
@@ -2055,26 +1226,28 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
       wave_lds_sync();
       // count the row, and read the write-out state in the same LDS round trip
       unsigned cnt = 0u;
-      if (lane == 0) cnt = __hip_atomic_fetch_add(&tr_arrived[tro_cur.tq & 3u], (unsigned)RPW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (lane == 0) cnt = __hip_atomic_fetch_add(&tr_arrived[tro_cur.tq & 3u], (unsigned)X::RPW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       const unsigned s_l = __hip_atomic_load(&tr_wo_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       const unsigned r_l = __hip_atomic_load(&tr_ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       unsigned ready = (unsigned)__builtin_amdgcn_readfirstlane((int)r_l);
-      if ((unsigned)__builtin_amdgcn_readfirstlane((int)cnt) + (unsigned)RPW == tro_cur.nrows)  // the tile is complete: publish it
+      if ((unsigned)__builtin_amdgcn_readfirstlane((int)cnt) + (unsigned)X::RPW == tro_cur.nrows)  // the tile is complete: publish it
         ready = tro_publish(tro_cur.tq, &tr_ready);
       // (one write-out step per row put into the ring: 400 M A-scans/s on C2 against 392 with two and 385 with four)
       (void)tro_try_step((unsigned)__builtin_amdgcn_readfirstlane((int)s_l), ready);
       tro_cur = tro_next;
     }
   }
-  if constexpr (TRO && !TRO_INPLACE) {
+  if constexpr (TRO && !X::TRO_INPLACE) {
     // all rows of this wave are done: help until the workgroup's last tile is out (it completes when its last row is in the
     // ring, which needs no help from here; the bound is the exit condition a spinning wave must have all the same)
+    // (TroGeom::bperm() written out again, on purpose: calling it here exchanges two s_mov in the averaging two-word
+    // transposed-store kernels -- profiles/fused_phases_codeobj_identity.txt)
     const unsigned nx_ = gridDim.x >> 3;
     const unsigned bp_ = (gridDim.x & 7u) ? blockIdx.x : (blockIdx.x & 7u) * nx_ + (blockIdx.x >> 3);
     const unsigned my_tiles = bp_ < a.tr_total_tiles ? (a.tr_total_tiles - bp_ + gridDim.x - 1u) / gridDim.x : 0u;
     for (unsigned spin = 0;; spin++) {
       const unsigned outn = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&tr_wo_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-      if (outn >= my_tiles * ((unsigned)a.D / (unsigned)TRO_SB)) break;
+      if (outn >= my_tiles * ((unsigned)a.D / (unsigned)X::TRO_SB)) break;
       if (tro_writeout(4)) {
         spin = 0;
         continue;
@@ -2104,173 +1277,7 @@ __global__ __launch_bounds__(fused_max_block(1 << LOG2NC, T, LEAN, KIND)) void f
 }
 
 #ifndef FDOCT_ONLY_PLAN  // (per-plan translation units hold the fused kernels only)
-// ---------------------------------------------------------- small kernels --
-// Whole-frame min/max (main:1128-1129) of the raw samples, one float2 per frame.
-template <typename IN_T>
-__global__ void minmax_kernel(const void* frames, long long pitch_bytes, int W, int H, const float* yd,
-                              int yd_2d, float2* out) {
-  const int f = blockIdx.x;
-  const unsigned char* base = static_cast<const unsigned char*>(frames) + (long long)f * H * pitch_bytes;
-  float mn = INFINITY, mx = -INFINITY;
-  for (int r = 0; r < H; r++) {
-    const IN_T* row = reinterpret_cast<const IN_T*>(base + (long long)r * pitch_bytes);
-    for (int i = threadIdx.x; i < W; i += blockDim.x) {
-      float x = (float)row[i];
-      if (yd) x -= yd[(yd_2d ? (size_t)r * W : 0) + i];
-      mn = fminf(mn, x);
-      mx = fmaxf(mx, x);
-    }
-  }
-  __shared__ float smn[16], smx[16];
-  mn = group_min<64>(mn);
-  mx = group_max<64>(mx);
-  if ((threadIdx.x & 63) == 0) {
-    smn[threadIdx.x >> 6] = mn;
-    smx[threadIdx.x >> 6] = mx;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < (int)(blockDim.x >> 6); w++) {
-      mn = fminf(mn, smn[w]);
-      mx = fmaxf(mx, smx[w]);
-    }
-    out[f] = make_float2(mn, mx);
-  }
-}
-
-// The same for plain integer camera frames (no dark frame, 16-byte-aligned rows): a streaming reduction with
-// 16-byte loads and packed 16-bit min/max, MINMAX_PARTS workgroups per frame, then one thread per frame folds the
-// partial results.  HBM-bound: one read of the batch.
-constexpr int MINMAX_PARTS = 16;
-typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-
-template <typename IN_T>
-__global__ __launch_bounds__(256) void minmax_fast_kernel(const void* frames, long long pitch_bytes, int row_vecs, int H,
-                                                           float2* partial) {
-  const int f = blockIdx.y;
-  const unsigned char* base = static_cast<const unsigned char*>(frames) + (long long)f * H * pitch_bytes;
-  us2 mn = (us2){0xffff, 0xffff}, mx = (us2){0, 0};
-  auto fold = [&](unsigned w) {
-    if constexpr (sizeof(IN_T) == 2) {
-      const us2 x = __builtin_bit_cast(us2, w);
-      mn = __builtin_elementwise_min(mn, x);
-      mx = __builtin_elementwise_max(mx, x);
-    } else {  // four bytes: even and odd ones as two 16-bit pairs
-      const us2 x0 = __builtin_bit_cast(us2, w & 0x00ff00ffu), x1 = __builtin_bit_cast(us2, (w >> 8) & 0x00ff00ffu);
-      mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(x0, x1));
-      mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(x0, x1));
-    }
-  };
-  for (int r = blockIdx.x; r < H; r += gridDim.x) {
-    const uint4* row = reinterpret_cast<const uint4*>(base + (long long)r * pitch_bytes);
-    for (int v = threadIdx.x; v < row_vecs; v += blockDim.x) {
-      const uint4 q = row[v];
-      fold(q.x);
-      fold(q.y);
-      fold(q.z);
-      fold(q.w);
-    }
-  }
-  unsigned lo = mn.x < mn.y ? mn.x : mn.y, hi = mx.x > mx.y ? mx.x : mx.y;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned l2 = __shfl_xor(lo, m, 64), h2 = __shfl_xor(hi, m, 64);
-    lo = l2 < lo ? l2 : lo;
-    hi = h2 > hi ? h2 : hi;
-  }
-  __shared__ unsigned slo[4], shi[4];
-  if ((threadIdx.x & 63) == 0) {
-    slo[threadIdx.x >> 6] = lo;
-    shi[threadIdx.x >> 6] = hi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; w++) {
-      lo = slo[w] < lo ? slo[w] : lo;
-      hi = shi[w] > hi ? shi[w] : hi;
-    }
-    partial[(size_t)f * gridDim.x + blockIdx.x] = make_float2((float)lo, (float)hi);
-  }
-}
-
-__global__ void minmax_finish_kernel(const float2* partial, int parts, int nframes, float2* out) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= nframes) return;
-  float2 r = partial[(size_t)f * parts];
-  for (int i = 1; i < parts; i++) {
-    const float2 p = partial[(size_t)f * parts + i];
-    r.x = fminf(r.x, p.x);
-    r.y = fmaxf(r.y, p.y);
-  }
-  out[f] = r;
-}
-
-// (rows x cols) -> (cols x rows) per group, through a 32x33 LDS tile.
-__global__ void transpose_kernel(const float* in, float* out, int rows, int cols) {
-  __shared__ float tile[32][33];
-  const size_t goff = (size_t)blockIdx.z * rows * cols;
-  int x = blockIdx.x * 32 + threadIdx.x;
-  int y0 = blockIdx.y * 32;
-  for (int j = threadIdx.y; j < 32; j += blockDim.y) {
-    int y = y0 + j;
-    if (x < cols && y < rows) tile[j][threadIdx.x] = in[goff + (size_t)y * cols + x];
-  }
-  __syncthreads();
-  int ox = blockIdx.y * 32 + threadIdx.x;  // row index of input
-  int oy0 = blockIdx.x * 32;
-  for (int j = threadIdx.y; j < 32; j += blockDim.y) {
-    int oy = oy0 + j;  // col index of input
-    if (ox < rows && oy < cols) out[goff + (size_t)oy * rows + ox] = tile[threadIdx.x][j];
-  }
-}
-
-// The same for rows and cols that are multiples of 4 (every B-scan of the bench and of the shipped configurations): a
-// 64 x 64 tile, 16 bytes per lane on both sides -- a wave reads 4 rows x 256 bytes and writes 4 output rows x 256 bytes,
-// non-temporal (each byte is touched once).  Tile rows are padded to 65 floats: the column reads of the second phase
-// (rows 4 r4 + i of column c) land two lanes per bank.
-__global__ void __launch_bounds__(256) transpose64_kernel(const float* in, float* out, int rows, int cols) {
-  typedef float f4v __attribute__((ext_vector_type(4)));
-  __shared__ float tile[64][65];
-  const size_t goff = (size_t)blockIdx.z * rows * cols;
-  const int x0 = blockIdx.x * 64, y0 = blockIdx.y * 64;  // tile origin: column, row of the input
-  const int q = threadIdx.x & 15, p = threadIdx.x >> 4;  // 16 lanes x 16 bytes across, 16 lines down per pass
-#pragma unroll
-  for (int pass = 0; pass < 4; pass++) {
-    const int y = y0 + p + 16 * pass, x = x0 + 4 * q;
-    if (y < rows && x < cols) {
-      const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(in + goff + (size_t)y * cols + x));
-      float* t = &tile[p + 16 * pass][4 * q];
-      t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int pass = 0; pass < 4; pass++) {
-    const int c = p + 16 * pass;           // input column = output row
-    const int oy = x0 + c, ox = y0 + 4 * q;  // output row, first of four output columns (= input rows)
-    if (oy < cols && ox < rows) {
-      const f4v v = {tile[4 * q][c], tile[4 * q + 1][c], tile[4 * q + 2][c], tile[4 * q + 3][c]};
-      __builtin_nontemporal_store(v, reinterpret_cast<f4v*>(out + goff + (size_t)oy * rows + ox));
-    }
-  }
-}
-
-// data_y as the reference holds it, CV_64F (main:987, 1125): split once into two f32 planes, x = hi + lo to 2^-48 of x.  The
-// kernels that take f32 frames carry lo into the division by the background next to hi (FusedArgs::frames_lo), so that a
-// frame of non-integer samples is not rounded at the size of the DC level (camera frames are integers: lo is 0 there).
-__global__ void f64_split_kernel(const double* in, long long pitch_elems, float* hi, float* lo, int W, long long rows) {
-  const long long n = rows * W;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    const long long r = i / W;
-    const int c = (int)(i - r * W);
-    const double x = in[r * pitch_elems + c];
-    const float h = (float)x;
-    hi[i] = h;
-    const double l = x - (double)h;
-    lo[i] = (l == l && h - h == 0.f) ? (float)l : 0.f;   // (inf / nan: no low word)
-  }
-}
+#include "fdoct_prepass_kernels.inc"
 
 #endif  // !FDOCT_ONLY_PLAN
 
@@ -2491,61 +1498,7 @@ hipError_t launch_fused(const FusedPlan& p, const FusedArgs& a, int dtype, bool 
   return hipErrorInvalidValue;
 }
 
-int minmax_partial_count(int nframes) { return nframes * MINMAX_PARTS; }
-
-hipError_t launch_minmax(const void* frames, int dtype, long long pitch_bytes, int W, int H, int nframes,
-                         const float* yd, int yd_2d, float2* out, float2* partial, hipStream_t st) {
-  const int es = dtype == FDOCT_K_U16 ? 2 : 1;
-  if (!yd && partial && (dtype == FDOCT_K_U16 || dtype == FDOCT_K_U8) && (W * es) % 16 == 0 && pitch_bytes % 16 == 0 &&
-      (reinterpret_cast<uintptr_t>(frames) % 16) == 0) {
-    // frames ride in gridDim.y (<= 65535 per launch): longer batches go in slices
-    for (int f0 = 0; f0 < nframes; f0 += 65535) {
-      const int nf = nframes - f0 < 65535 ? nframes - f0 : 65535;
-      const dim3 g(MINMAX_PARTS, nf), b(256);
-      const void* fr = static_cast<const unsigned char*>(frames) + (long long)f0 * H * pitch_bytes;
-      float2* part = partial + (size_t)f0 * MINMAX_PARTS;
-      if (dtype == FDOCT_K_U16)
-        hipLaunchKernelGGL(minmax_fast_kernel<uint16_t>, g, b, 0, st, fr, pitch_bytes, W * es / 16, H, part);
-      else
-        hipLaunchKernelGGL(minmax_fast_kernel<uint8_t>, g, b, 0, st, fr, pitch_bytes, W * es / 16, H, part);
-    }
-    hipLaunchKernelGGL(minmax_finish_kernel, dim3((nframes + 255) / 256), dim3(256), 0, st, partial, MINMAX_PARTS, nframes, out);
-    return hipGetLastError();
-  }
-  dim3 g(nframes), b(1024);
-  switch (dtype) {
-    case FDOCT_K_U16: hipLaunchKernelGGL(minmax_kernel<uint16_t>, g, b, 0, st, frames, pitch_bytes, W, H, yd, yd_2d, out); break;
-    case FDOCT_K_U8: hipLaunchKernelGGL(minmax_kernel<uint8_t>, g, b, 0, st, frames, pitch_bytes, W, H, yd, yd_2d, out); break;
-    case FDOCT_K_F32: hipLaunchKernelGGL(minmax_kernel<float>, g, b, 0, st, frames, pitch_bytes, W, H, yd, yd_2d, out); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_transpose(const float* in, float* out, int rows, int cols, int groups, hipStream_t st) {
-  // groups ride in gridDim.z and row tiles in gridDim.y (<= 65535 each per launch): more go in slices
-  const int ytiles = (rows + 31) / 32;
-  if (ytiles > 65535) return hipErrorInvalidValue;  // > 2 M rows per B-scan
-  const bool wide = rows % 4 == 0 && cols % 4 == 0 && ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0);
-  for (int g0 = 0; wide && g0 < groups; g0 += 65535) {
-    const int ng = groups - g0 < 65535 ? groups - g0 : 65535;
-    const size_t off = (size_t)g0 * rows * cols;
-    hipLaunchKernelGGL(transpose64_kernel, dim3((cols + 63) / 64, (rows + 63) / 64, ng), dim3(256), 0, st, in + off, out + off, rows, cols);
-  }
-  if (wide) return hipGetLastError();
-  for (int g0 = 0; g0 < groups; g0 += 65535) {
-    const int ng = groups - g0 < 65535 ? groups - g0 : 65535;
-    const size_t off = (size_t)g0 * rows * cols;
-    dim3 b(32, 8), g((cols + 31) / 32, ytiles, ng);
-    hipLaunchKernelGGL(transpose_kernel, g, b, 0, st, in + off, out + off, rows, cols);
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_f64_split(const double* in, long long pitch_elems, float* hi, float* lo, int W, long long rows, hipStream_t st) {
-  hipLaunchKernelGGL(f64_split_kernel, dim3(2048), dim3(256), 0, st, in, pitch_elems, hi, lo, W, rows);
-  return hipGetLastError();
-}
+#include "fdoct_prepass_launch.inc"
 
 #endif  // !FDOCT_ONLY_PLAN
 

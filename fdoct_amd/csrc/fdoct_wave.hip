@@ -2,7 +2,7 @@
 //
 // Every build/*.ini of the reference uses a numfftpoints that is not a power of two (2560 = 2^9*5, 2880 = 2^6*3^2*5, 640)
 // and all but the webcam one the x4 zero-pad upsampling (zeropadrowwise, BscanFFT.cpp:180-245), so none of them fits the
-// power-of-two fused plans of fdoct_kernels.hip.  Rows are short there (160 .. 720 samples), which makes the
+// power-of-two fused plans of fdoct_kernels.hip (fdoct_fused_*.h).  Rows are short there (160 .. 720 samples), which makes the
 // workgroup-per-row kernel of fdoct_generic.hip a chain of ~25 workgroup barriers per A-scan with a handful of
 // instructions between them.  Here ONE 64-lane wave owns an A-scan from the camera samples to the depth profile:
 //   * no workgroup barrier at all: a wave's LDS operations execute in program order, so every hand-off inside the

@@ -7,15 +7,15 @@ makes a test say so instead of passing one stride short.
 Keep the figures equal to the launch code they are taken from:"""
 
 PASS = 2048 * 256        # elements one pass of dim3(2048) x dim3(256) takes: movavg_f64_kernel<double>, <float>, movavg_kernel
-#                          fdoct_generic.hip:670, :674, :680; f64_split_kernel fdoct_kernels.hip:2546
+#                          fdoct_generic.hip:670, :674, :680; f64_split_kernel fdoct_prepass_launch.inc:56
 PASS_BLOCK = 256
-MINMAX_PARTS = 16        # workgroups per frame of minmax_fast_kernel: rows r += 16                   fdoct_kernels.hip:2144, :2164
-MINMAX_BLOCK = 256       # ... threads of each: 16-byte vectors v += 256                             fdoct_kernels.hip:2166, :2504
+MINMAX_PARTS = 16        # workgroups per frame of minmax_fast_kernel: rows r += 16                   fdoct_prepass_kernels.inc:40, :60
+MINMAX_BLOCK = 256       # ... threads of each: 16-byte vectors v += 256                             fdoct_prepass_kernels.inc:62, fdoct_prepass_launch.inc:14
 VEC_BYTES = 16
-MINMAX_THREADS = 1024    # minmax_kernel: i += 1024                                                  fdoct_kernels.hip:2117, :2515
-FINISH_BLOCK = 256       # frames per workgroup of minmax_finish_kernel                              fdoct_kernels.hip:2197, :2512
+MINMAX_THREADS = 1024    # minmax_kernel: i += 1024                                                  fdoct_prepass_kernels.inc:13, fdoct_prepass_launch.inc:25
+FINISH_BLOCK = 256       # frames per workgroup of minmax_finish_kernel                              fdoct_prepass_kernels.inc:93, fdoct_prepass_launch.inc:22
 SLICE = 65535            # frames of one minmax_fast_kernel launch (gridDim.y), groups of one transpose launch (gridDim.z)
-#                          fdoct_kernels.hip:2502, :2530, :2536
+#                          fdoct_prepass_launch.inc:12, :40, :46
 GEN_MAX_PER_CU = 6       # generic_kernel: grid = min(CUs x per_cu, out_rows), 1 <= per_cu <= 6       fdoct_route.cpp:504-507
 GEN_TICKET_WORDS = 64    # row counters used in turn, gen_ticket_seq++ % 64                          fdoct_route.cpp:692-702
 LDS_BYTES = 160 * 1024
@@ -127,7 +127,7 @@ MANY_D_NARROW = 30                   # no multiple of 4: transpose_kernel
 
 
 def transpose_wide(rows, cols, aligned=True):
-    """launch_transpose takes transpose64_kernel (fdoct_kernels.hip:2529)."""
+    """launch_transpose takes transpose64_kernel (fdoct_prepass_launch.inc:39)."""
     return rows % 4 == 0 and cols % 4 == 0 and aligned
 
 

@@ -1,4 +1,4 @@
-"""numpy model of the data movement of the fused HIP kernel (fdoct_amd/csrc/fdoct_kernels.hip).
+"""numpy model of the data movement of the fused HIP kernel (fdoct_amd/csrc/fdoct_kernels.hip and the fdoct_fused_*.h it includes).
 
 It mirrors, index for index, how a group of T lanes holding P = NC/T complex
 points each runs the Stockham passes (registers -> twiddle -> radix butterfly ->
@@ -111,7 +111,7 @@ def bank_conflicts(accesses, bytes_per_lane, group, nbanks):
 
 
 def fft1024_rowswap_model(x):
-    """numpy model of fft1024_rowswap (fdoct_kernels.hip): unscaled inverse DFT of 1024 complex points
+    """numpy model of fft1024_rowswap (fdoct_fused_fft.h): unscaled inverse DFT of 1024 complex points
     with index split n = 64*m + 16*a + b and output k = k1 + 16*k2 + 64*k3.  Mirrors the kernel's
     register/lane placement: reg[lane][r]."""
     N = 1024
@@ -151,7 +151,7 @@ def fft1024_rowswap_model(x):
 
 
 def fft2048_rowswap_model(x):
-    """numpy model of fft2048_rowswap (fdoct_kernels.hip): unscaled inverse DFT of 2048 complex points, index split
+    """numpy model of fft2048_rowswap (fdoct_fused_fft.h): unscaled inverse DFT of 2048 complex points, index split
     n = 64*m + 16*a + b (m: 32 registers, a: 16-lane row, b: lane in row), output k = k1 + 32*k2 + 128*k3.
     Final register s + 2*k3 of lane l holds bin l + 64*(s + 2*k3) (natural slot order)."""
     N = 2048

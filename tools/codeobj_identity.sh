@@ -1,15 +1,17 @@
 #!/bin/bash
 # Are the device code objects of two builds of fdoct_amd/csrc the same?  For refactors that must not change the shipped kernels.
-#   usage: tools/codeobj_identity.sh <parent csrc dir> <head csrc dir> > profiles/<record>.txt
+#   usage: tools/codeobj_identity.sh <parent csrc dir> <head csrc dir> ["<object names>"] > profiles/<record>.txt
 # Both directories hold the objects of the default build (`make -C fdoct_amd/csrc`), built from the same relative path with the
-# same flags.  Per object the gfx950 code object is unbundled and three texts are hashed (SHA-256): the disassembly of .text,
+# same flags.  A third argument (or OBJS in the environment) names other objects, without ".o", in place of the default build's
+# 24: the instrument builds of tests/test_dev_builds.py compiled to objects in both directories, for one.
+# Per object the gfx950 code object is unbundled and three texts are hashed (SHA-256): the disassembly of .text,
 # the contents of .rodata (kernel descriptors) and the ELF notes (registers, scratch, LDS, argument layout).  The raw objects are
 # NOT compared: they carry a source-derived identifier in .dynstr that a comment-only edit changes.  Exit status 1 on a difference.
 set -euo pipefail
 PARENT=$1
 HEAD=$2
 LLVM=${LLVM:-$(hipconfig -l)}   # the directory of ROCm's clang and llvm-* tools
-OBJS="fdoct_kernels $(for i in 0 1 2 3 4 5 6 7 8; do echo fdoct_kernels_p$i; done) $(for i in 0 1 2 3 4 5 6 7 8; do echo fdoct_kernels_q$i; done) fdoct_generic fdoct_wave fdoct_wave_x1 fdoct_wave_x2 fdoct_big"
+OBJS=${3:-${OBJS:-"fdoct_kernels $(for i in 0 1 2 3 4 5 6 7 8; do echo fdoct_kernels_p$i; done) $(for i in 0 1 2 3 4 5 6 7 8; do echo fdoct_kernels_q$i; done) fdoct_generic fdoct_wave fdoct_wave_x1 fdoct_wave_x2 fdoct_big"}}
 TMP=$(mktemp -d)
 trap 'rm -rf "$TMP"' EXIT
 
