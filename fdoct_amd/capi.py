@@ -109,6 +109,13 @@ MANUALAVG_ABI_SYMBOLS = ["fdoct_manualavg_plan", "fdoct_manualavg_begin", "fdoct
 # every symbol include/fdoct_saveframes.h declares: per-frame saves while averaging (saveframes) and the chain's raw-magnitudes
 # switch, likewise on their own
 SAVEFRAMES_ABI_SYMBOLS = ["fdoct_set_raw_magnitudes", "fdoct_get_raw_magnitudes", "fdoct_saveframes"]
+# every symbol include/fdoct_calibrate.h declares: BscanDark's calibration on the device (normalisations, held captures,
+# composition).  They live in libfdoct_calibrate.so, an add-on library over libfdoct_hip.so (whose exported symbols are a closed
+# set); load_library attaches them to the object it returns
+CALIBRATE_ABI_SYMBOLS = ["fdoct_normalize_rows_minmax", "fdoct_calibrate_capture", "fdoct_calibrate_compose", "fdoct_calibrate_state",
+                         "fdoct_calibrate_clear"]
+# fdoct_cal_slot (include/fdoct_calibrate.h)
+CAL_DARK, CAL_REFERENCE, CAL_SAMPLE = range(3)
 # fdoct_manualavg_mode (include/fdoct_manualavg.h)
 MANUALAVG_REFERENCE, MANUALAVG_KEEP_ALL = 0, 1
 # fdoct_ref_role (include/fdoct_capture.h)
@@ -133,6 +140,11 @@ def shard_frames(nframes_total, averages, part, nparts):
     if rc:
         raise FdoctError(rc, "fdoct_shard_frames: bad arguments")
     return first.value, first.value + count.value
+
+
+def calibrate_library_path():
+    """The add-on library of include/fdoct_calibrate.h, in the package next to the in-tree core library it is linked against."""
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfdoct_calibrate.so")
 
 
 def load_library():
@@ -257,6 +269,19 @@ def load_library():
     lib.fdoct_get_raw_magnitudes.argtypes = [C.c_void_p]
     lib.fdoct_saveframes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    # include/fdoct_calibrate.h: the add-on library's entry points, attached to the core library's object
+    cal_path = calibrate_library_path()
+    if not os.path.exists(cal_path):
+        raise FdoctError(-3, "%s not found: build it with `make -C fdoct_amd/csrc` (or __graft_entry__.build())" % cal_path)
+    cal = C.CDLL(cal_path)
+    for name in CALIBRATE_ABI_SYMBOLS:
+        setattr(lib, name, getattr(cal, name))
+    lib.fdoct_normalize_rows_minmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_double, C.c_double,
+                                                C.c_int, C.c_void_p, C.c_int]
+    lib.fdoct_calibrate_capture.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p]
+    lib.fdoct_calibrate_compose.argtypes = [C.c_void_p, C.c_void_p]
+    lib.fdoct_calibrate_state.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    lib.fdoct_calibrate_clear.argtypes = [C.c_void_p]
     _lib = lib
     return lib
 
@@ -771,6 +796,68 @@ class Reconstructor:
         """... on device-resident rows (raw device addresses; d_out_ptr None: in place).  Enqueues on the handle's stream."""
         self._check(self.lib.fdoct_lowpass_rows(self.h, d_in_ptr, MEM_DEVICE, rows, width, pitch,
                                                 d_in_ptr if d_out_ptr is None else d_out_ptr, MEM_DEVICE))
+
+    # -- BscanDark's calibration on the device (include/fdoct_calibrate.h)
+    def normalize_rows_minmax(self, rows, lo=0.0001, hi=1.0, per_row=True, out=None):
+        """cv::normalize(.., lo, hi, NORM_MINMAX) on a float64 (rows, width) array, or one row, in host memory: every row on its
+        own (per_row, normalizerows) or the array as one plane.  Returns a new array; or normalises into `out`, which has the rows'
+        shape and strides (a view with padded rows passes its pitch on) and may be `rows` itself."""
+        a = np.asarray(rows)
+        if out is None:
+            a = np.ascontiguousarray(a)
+            out = np.empty_like(a)
+        if a.dtype != np.float64 or a.ndim not in (1, 2) or a.size == 0 or a.strides[-1] != 8:
+            raise FdoctError(-1, "normalize_rows_minmax takes float64 rows of contiguous samples")
+        if out.dtype != np.float64 or out.shape != a.shape or out.strides != a.strides:
+            raise FdoctError(-1, "out must be float64 of the rows' shape and strides")
+        nrows, width = (1, a.shape[0]) if a.ndim == 1 else a.shape
+        pitch = a.strides[0] if a.ndim == 2 and nrows > 1 else 0
+        self._check(self.lib.fdoct_normalize_rows_minmax(self.h, a.ctypes.data, MEM_HOST, nrows, width, pitch, float(lo), float(hi),
+                                                         int(bool(per_row)), out.ctypes.data, MEM_HOST))
+        return out
+
+    def normalize_rows_minmax_device(self, d_ptr, rows, width, pitch=0, lo=0.0001, hi=1.0, per_row=True, d_out_ptr=None):
+        """... on device-resident rows (raw device addresses; d_out_ptr None: in place).  Enqueues on the handle's stream."""
+        self._check(self.lib.fdoct_normalize_rows_minmax(self.h, d_ptr, MEM_DEVICE, rows, width, pitch, float(lo), float(hi),
+                                                         int(bool(per_row)), d_ptr if d_out_ptr is None else d_out_ptr, MEM_DEVICE))
+
+    def calibrate_capture(self, slot, frames, out=False):
+        """One of BscanDark's captures (CAL_DARK / CAL_REFERENCE / CAL_SAMPLE) on host frames: accumulated, normalised and
+        filtered on the device and held there; CAL_DARK also becomes the handle's dark frame.  out=True returns the result as
+        float64 (H, W) -- for the reference and sample slots that is the call's only download."""
+        if slot not in (CAL_DARK, CAL_REFERENCE, CAL_SAMPLE):
+            raise FdoctError(-1, "calibrate_capture: slot is CAL_DARK, CAL_REFERENCE or CAL_SAMPLE")
+        a, n, pitch = _frame_batch(frames)
+        res = np.empty((self.cfg.height, self.cfg.width), np.float64) if out else None
+        self._check(self.lib.fdoct_calibrate_capture(self.h, slot, a.ctypes.data, _NP2DT[a.dtype], MEM_HOST, n, pitch,
+                                                     res.ctypes.data if out else None))
+        return res
+
+    def calibrate_capture_device(self, slot, d_ptr, dtype, nframes, pitch=0, out=False):
+        """... on device-resident frames (raw device address)."""
+        if slot not in (CAL_DARK, CAL_REFERENCE, CAL_SAMPLE):
+            raise FdoctError(-1, "calibrate_capture_device: slot is CAL_DARK, CAL_REFERENCE or CAL_SAMPLE")
+        res = np.empty((self.cfg.height, self.cfg.width), np.float64) if out else None
+        self._check(self.lib.fdoct_calibrate_capture(self.h, slot, d_ptr, dtype, MEM_DEVICE, nframes, pitch,
+                                                     res.ctypes.data if out else None))
+        return res
+
+    def calibrate_compose(self, out=False):
+        """BscanDark.cpp:996 from the three held captures, (yr - yd) + (ys - yd): the result becomes the handle's background.
+        out=True returns it as float64 (H, W)."""
+        res = np.empty((self.cfg.height, self.cfg.width), np.float64) if out else None
+        self._check(self.lib.fdoct_calibrate_compose(self.h, res.ctypes.data if out else None))
+        return res
+
+    def calibrate_state(self):
+        """(dark, reference, sample) as bools: which captures the handle holds."""
+        held = (C.c_int * 3)()
+        self._check(self.lib.fdoct_calibrate_state(self.h, held))
+        return tuple(bool(x) for x in held)
+
+    def calibrate_clear(self):
+        """Drops the three held captures; the handle's dark frame and background stay."""
+        self._check(self.lib.fdoct_calibrate_clear(self.h))
 
     # -- spinjnt's output binning (include/fdoct_bscanbin.h).  Host batches are float32 like the readouts'.
     def bscan_bin(self, bscan, binx, biny, upx=None, upy=None, multiplyfactor=None, jscan=None, layout=LAYOUT_ROWMAJOR,

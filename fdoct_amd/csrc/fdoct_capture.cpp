@@ -6,8 +6,7 @@
 // back to the device once more, for lpfilter.
 #include "../../include/fdoct_capture.h"
 
-#include "fdoct_capture_kernels.h"
-#include "fdoct_ctx.h"
+#include "fdoct_capture_plan.h"
 
 using namespace fdoct_impl;
 
@@ -15,16 +14,9 @@ namespace {
 
 bool has_frontend(const fdoct_ctx* h) { return h->fe_median > 0 || h->fe_binx > 1 || h->fe_biny > 1; }
 
-// What a call does with its frames, decided (and refused) before anything is enqueued.
-struct FramePlan {
-  StagePlan stage;  // the frames are its item 0; a call adds its outputs
-  fdoct::CaptureFrames cf;  // what the kernels read: front_passes fills it
-  fdoct_dtype dtype = FDOCT_U16;
-  bool frontend = false;
-  bool colour = false;  // interleaved B,G,R frames (fdoct_set_colour_input): es is 3, the colour stage runs in the front end's place
-  int nframes = 0, raw_w = 0, raw_h = 0;
-  size_t es = 0, pitch = 0;
-};
+}  // namespace
+
+namespace fdoct_impl {  // (declared in fdoct_capture_plan.h: fdoct_calibrate.cpp plans its frames the same way)
 
 int plan_frames(fdoct_ctx* h, const char* fn, const void* frames, fdoct_dtype dtype, fdoct_memspace space, int nframes,
                 size_t pitch_bytes, FramePlan* p) {
@@ -70,6 +62,10 @@ int front_passes(fdoct_ctx* h, FramePlan& p, const void* src) {
   p.cf.frames = o ? o : src, p.cf.dt = dt, p.cf.pitch = pitch, p.cf.nframes = p.nframes, p.cf.H = h->H, p.cf.W = h->W;
   return FDOCT_OK;
 }
+
+}  // namespace fdoct_impl
+
+namespace {
 
 RefFrame* ref_of(fdoct_ctx* h, int role) {
   return role == FDOCT_REF_BACKGROUND ? &h->yb : role == FDOCT_REF_PI ? &h->yp : role == FDOCT_REF_DARK ? &h->yd : nullptr;

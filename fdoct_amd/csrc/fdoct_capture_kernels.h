@@ -1,6 +1,6 @@
 // fdoct_capture_kernels.h -- launchers of the reference-frame capture (fdoct_capture.hip) behind include/fdoct_capture.h and
 // of BscanDark's low-pass filter on captured frames (fdoct_lowpass.hip) behind include/fdoct_lowpass.h.
-// Internal: fdoct_capture.cpp and fdoct_lowpass.cpp are the only callers.
+// Internal: fdoct_capture.cpp, fdoct_lowpass.cpp and fdoct_calibrate.cpp (whose captures start with the same accumulation) are the only callers.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -13,6 +13,7 @@
 //   fdoct_colour.cpp  those of include/fdoct_colour.h (the webcam's interleaved B,G,R frames: channelnum)
 //   fdoct_manualavg.cpp those of include/fdoct_manualavg.h (manual averaging of B-scans: manualaccum and its counter)
 //   fdoct_saveframes.cpp those of include/fdoct_saveframes.h (per-frame saves while averaging; the raw-magnitudes switch)
+//   fdoct_calibrate.cpp those of include/fdoct_calibrate.h (BscanDark's calibration: device-side normalisations, held captures, composition)
 //   fdoct_stage.h     the staging plan of host-memory arguments: the side entry points', fdoct_process's single shot (stage_reserve / stage_upload / stage_finish, below, commit it)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
@@ -74,6 +75,7 @@ class Buffer {
     p_ = nullptr;
     bytes_ = 0;
   }
+  void swap(Buffer& o) noexcept { std::swap(p_, o.p_), std::swap(bytes_, o.bytes_), std::swap(flags_, o.flags_); }
   // at least `bytes`, grown only (the old contents are not kept)
   int reserve(fdoct_ctx* h, size_t bytes) {
     if (bytes_ >= bytes && p_) return FDOCT_OK;
@@ -228,6 +230,12 @@ struct fdoct_ctx {
   // (kernel_eps) and write no dB.  A run-time setting like `averages`: fdoct_clone_to_device carries it, the state blob does not.
   bool raw_mag = false;
   DevBuf<double> d_sf_part;        // partial (min, max) pairs of the pictures' dB values, per image (fdoct_saveframes_kernels.h)
+  // BscanDark's calibration (fdoct_calibrate.cpp): the dark / reference / sample captures held on the device.  Measurement state
+  // like the peak holds, so neither fdoct_export_state nor fdoct_clone_to_device carries it
+  DevBuf<double> d_cal[3];         // H x W doubles each, indexed by fdoct_cal_slot
+  bool cal_held[3] = {false, false, false};
+  DevBuf<double> ws_cal_next;      // the frame a capture is writing: swapped with its slot when the capture has succeeded
+  DevBuf<double> ws_cal_mm;        // min / max partials and the (scale, shift) pairs made from them (MinMaxShape::ws_doubles)
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;

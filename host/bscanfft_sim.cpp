@@ -11,6 +11,7 @@
 //                [--rowwisenormalize 0|1] [--donotnormalize 0|1] [--repeat K] [--threshold dB] --out prefix
 //                [--gpus N [--devices d0,d1,...]] [--precise-division | --one-word-division]
 //                [--roi-mean ascanat,vertpos,width] [--capture-background N [--capture-lowpass] [--capture-raw]] [--max-intensity]
+//                [--calibrate-dark-ref-sample N [--capture-lowpass] [--capture-raw]]
 //                [--bscan-bin BX,BY[,BINVALUEX,BINVALUEY]] [--channel N] [--manual-averages M [--manual-keep-all]] [--save-frames]
 //
 // --gpus N: one process, N handles (fdoct_clone_to_device), one host thread per handle; the frames are sharded with
@@ -26,6 +27,11 @@
 // reconstructed; --background is then not needed.  --capture-lowpass ends that capture with BscanDark's lpfilter (the ini's
 // lowpassfilter), --capture-raw skips its moving average (the ini's saveinterferograms; include/fdoct_lowpass.h); with either,
 // the captured frame is also written as <prefix>_background.f64 (H x W doubles).
+// --calibrate-dark-ref-sample N: BscanDark's calibration (BscanDark.cpp:996, 1005-1222) instead of a background file: the first
+// 3 N frames of --frames are the dark, the reference-arm and the sample-arm capture of N frames each (the d / r / t keys), made
+// and held on the GPU (include/fdoct_calibrate.h); the dark capture becomes data_yd, and data_yb = (yr - yd) + (ys - yd) is
+// composed there from the three.  Those frames are not reconstructed, --background is not needed, and the composed frame is
+// written as <prefix>_background.f64.  --capture-lowpass and --capture-raw act on the three captures as they do on the 'b' key's.
 // --bscan-bin BX,BY[,BINVALUEX,BINVALUEY]: spinjnt's output binning (bscanbinx, bscanbiny and the software binvalues;
 // BscanFFTspinjnt.cpp:1856-1861) on every output B-scan between the chain and everything written below, on the GPU
 // (include/fdoct_bscanbin.h), with the reference's own arguments: upx = BX * BINVALUEY, upy = BY and multiplyfactor =
@@ -63,6 +69,7 @@
 
 #include "../include/fdoct.h"
 #include "../include/fdoct_bscanbin.h"
+#include "../include/fdoct_calibrate.h"
 #include "../include/fdoct_capture.h"
 #include "../include/fdoct_colour.h"
 #include "../include/fdoct_lowpass.h"
@@ -102,6 +109,7 @@ int main(int argc, char** argv) {
   int roi[3] = {-1, 0, 0};         // --roi-mean ascanat,vertpos,width (-1: off)
   int capture_bg = 0;              // --capture-background N (0: read --background)
   int capture_lowpass = 0, capture_raw = 0;  // --capture-lowpass, --capture-raw: fdoct_set_capture_options
+  int calibrate_n = 0;             // --calibrate-dark-ref-sample N (0: no calibration)
   bool max_intensity = false;      // --max-intensity
   int bbin[4] = {0, 0, 1, 1};      // --bscan-bin bscanbinx,bscanbiny[,binvaluex,binvaluey] (0: off)
   int channel = -1;                // --channel channelnum (-1: mono frames)
@@ -150,6 +158,7 @@ int main(int argc, char** argv) {
       }
     }
     else if (a == "--capture-background") capture_bg = std::atoi(next());
+    else if (a == "--calibrate-dark-ref-sample") calibrate_n = std::atoi(next());
     else if (a == "--capture-lowpass") capture_lowpass = 1;
     else if (a == "--capture-raw") capture_raw = 1;
     else if (a == "--max-intensity") max_intensity = true;
@@ -175,7 +184,12 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
-  if (frames_path.empty() || (bg_path.empty() && capture_bg <= 0) || capture_bg < 0 || cfg.width <= 0 || cfg.height <= 0 || cfg.numfftpoints <= 0) {
+  if (calibrate_n < 0 || (calibrate_n > 0 && capture_bg > 0)) {
+    std::fprintf(stderr, "--calibrate-dark-ref-sample takes a positive frame count and replaces --capture-background\n");
+    return 1;
+  }
+  const int captured_frames = capture_bg + 3 * calibrate_n;  // the frames at the head of --frames that make the background
+  if (frames_path.empty() || (bg_path.empty() && captured_frames <= 0) || capture_bg < 0 || cfg.width <= 0 || cfg.height <= 0 || cfg.numfftpoints <= 0) {
     std::fprintf(stderr, "usage: see the header of host/bscanfft_sim.cpp\n");
     return 1;
   }
@@ -216,12 +230,12 @@ int main(int argc, char** argv) {
     }
   };
   load(frames_path, &frames, frame_channels);
-  if (capture_bg == 0) load(bg_path, &bg, 1);
-  const int nframes_file = (int)(frames.size() / frame_bytes) - capture_bg;  // (the captured frames are not reconstructed)
-  const unsigned char* live = frames.data() + (size_t)capture_bg * frame_bytes;
+  if (captured_frames == 0) load(bg_path, &bg, 1);
+  const int nframes_file = (int)(frames.size() / frame_bytes) - captured_frames;  // (the captured frames are not reconstructed)
+  const unsigned char* live = frames.data() + (size_t)captured_frames * frame_bytes;
   if (nframes_file < 1) {
-    if (capture_bg > 0)
-      std::fprintf(stderr, "%s: no frames are left to reconstruct after the %d captured as the background\n", frames_path.c_str(), capture_bg);
+    if (captured_frames > 0)
+      std::fprintf(stderr, "%s: no frames are left to reconstruct after the %d captured as the background\n", frames_path.c_str(), captured_frames);
     else
       std::fprintf(stderr, "%s holds no complete %dx%d frame\n", frames_path.c_str(), cfg.width, cfg.height);
     return 1;
@@ -232,7 +246,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   int bg_rows = 0;
-  if (capture_bg > 0) bg_rows = cfg.height;
+  if (captured_frames > 0) bg_rows = cfg.height;
   else if (bg.size() >= (size_t)cfg.width * cfg.height * es) bg_rows = cfg.height;
   else if (bg.size() >= (size_t)cfg.width * es) bg_rows = 1;
   else {
@@ -251,7 +265,26 @@ int main(int argc, char** argv) {
     return 1;
   }
   // the 'b' key: data_yb <- backg (sim:803-813)
-  if (capture_bg > 0) {  // ... or the live 'b' key: accumulate(data_y, baccum) over the first frames, main:1041-1064
+  const char* bg_call = capture_bg > 0 ? "fdoct_capture_reference" : "fdoct_set_background";
+  if (calibrate_n > 0) {  // ... or BscanDark's d / r / t keys and BscanDark.cpp:996, all on the device
+    bg_call = "fdoct_calibrate_capture";
+    if ((rc = fdoct_set_capture_options(h, capture_lowpass, capture_raw))) {
+      std::fprintf(stderr, "fdoct_set_capture_options: %s\n", fdoct_last_error(h));
+      return 1;
+    }
+    const int slots[3] = {FDOCT_CAL_DARK, FDOCT_CAL_REFERENCE, FDOCT_CAL_SAMPLE};
+    for (int k = 0; k < 3 && !rc; k++)
+      rc = fdoct_calibrate_capture(h, slots[k], frames.data() + (size_t)k * calibrate_n * frame_bytes, dt, FDOCT_MEM_HOST, calibrate_n, 0, nullptr);
+    if (!rc) {
+      bg_call = "fdoct_calibrate_compose";
+      std::vector<double> composed((size_t)cfg.width * cfg.height);
+      rc = fdoct_calibrate_compose(h, composed.data());
+      if (!rc) {
+        std::ofstream f(out + "_background.f64", std::ios::binary);
+        f.write(reinterpret_cast<const char*>(composed.data()), (std::streamsize)(composed.size() * sizeof(double)));
+      }
+    }
+  } else if (capture_bg > 0) {  // ... or the live 'b' key: accumulate(data_y, baccum) over the first frames, main:1041-1064
     const bool options = capture_lowpass || capture_raw;
     std::vector<double> captured(options ? (size_t)cfg.width * cfg.height : 0);
     if (options && (rc = fdoct_set_capture_options(h, capture_lowpass, capture_raw))) {
@@ -267,7 +300,7 @@ int main(int argc, char** argv) {
   } else
     rc = fdoct_set_background(h, bg.data(), dt, bg_rows, 0);
   if (rc) {
-    std::fprintf(stderr, "%s: %s\n", capture_bg > 0 ? "fdoct_capture_reference" : "fdoct_set_background", fdoct_last_error(h));
+    std::fprintf(stderr, "%s: %s\n", bg_call, fdoct_last_error(h));
     return 1;
   }
   if (precise >= 0 && (rc = fdoct_set_precise_division(h, precise))) {

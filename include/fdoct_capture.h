@@ -38,8 +38,8 @@
  *   options           fdoct_lowpass.h adds two switches of the handle, both off by default: BscanDark's lpfilter as the last
  *                     step of BACKGROUND, DARK and NONE, and the saveinterferograms branch (1003-1036), which accumulates the
  *                     binned frames without the moving average (1024).
- * Not covered: an asynchronous form of the capture, and BscanDark's composition data_yb = (yr - yd) + (ys - yd), which a host
- * forms from three FDOCT_REF_NONE captures and passes to the background setter of fdoct.h; INTEGRATION.md 2d shows it.
+ * Not covered: an asynchronous form of the capture.  BscanDark's composition data_yb = (yr - yd) + (ys - yd) and captures whose
+ * normalisations stay on the device are fdoct_calibrate.h's; this call downloads its sums and normalises them on the host.
  * The division is a division (acc[i] / nframes), as the CPU restatement of this project divides everywhere the reference
  * writes `Mat / scalar`.
  */
