@@ -114,6 +114,9 @@ SAVEFRAMES_ABI_SYMBOLS = ["fdoct_set_raw_magnitudes", "fdoct_get_raw_magnitudes"
 # set); load_library attaches them to the object it returns
 CALIBRATE_ABI_SYMBOLS = ["fdoct_normalize_rows_minmax", "fdoct_calibrate_capture", "fdoct_calibrate_compose", "fdoct_calibrate_state",
                          "fdoct_calibrate_clear"]
+# every symbol include/fdoct_complex.h declares: the complex A-scan (re, im) of the chain.  It lives in libfdoct_complex.so, a second
+# add-on library over libfdoct_hip.so; load_library attaches it likewise
+COMPLEX_ABI_SYMBOLS = ["fdoct_process_complex"]
 # fdoct_cal_slot (include/fdoct_calibrate.h)
 CAL_DARK, CAL_REFERENCE, CAL_SAMPLE = range(3)
 # fdoct_manualavg_mode (include/fdoct_manualavg.h)
@@ -145,6 +148,11 @@ def shard_frames(nframes_total, averages, part, nparts):
 def calibrate_library_path():
     """The add-on library of include/fdoct_calibrate.h, in the package next to the in-tree core library it is linked against."""
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfdoct_calibrate.so")
+
+
+def complex_library_path():
+    """The add-on library of include/fdoct_complex.h, in the package next to the in-tree core library it is linked against."""
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfdoct_complex.so")
 
 
 def load_library():
@@ -282,6 +290,14 @@ def load_library():
     lib.fdoct_calibrate_compose.argtypes = [C.c_void_p, C.c_void_p]
     lib.fdoct_calibrate_state.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     lib.fdoct_calibrate_clear.argtypes = [C.c_void_p]
+    # include/fdoct_complex.h: likewise
+    cx_path = complex_library_path()
+    if not os.path.exists(cx_path):
+        raise FdoctError(-3, "%s not found: build it with `make -C fdoct_amd/csrc` (or __graft_entry__.build())" % cx_path)
+    cx = C.CDLL(cx_path)
+    for name in COMPLEX_ABI_SYMBOLS:
+        setattr(lib, name, getattr(cx, name))
+    lib.fdoct_process_complex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
     return lib
 
@@ -1019,6 +1035,34 @@ class Reconstructor:
         """Enqueue on the handle's stream; pointers are raw device addresses (e.g. tensor.data_ptr())."""
         self._check(self.lib.fdoct_process_async(self.h, d_frames_ptr, dtype, nframes, pitch_bytes, d_bscan_ptr,
                                                  d_db_ptr, layout))
+
+    def process_complex(self, frames, layout=LAYOUT_ROWMAJOR, out=None):
+        """The complex A-scans of `frames` (numpy, as process() takes them): fdoct_process_complex.  Returns complex64 of shape
+        (nframes, H, D), or (nframes, D, H) in the transposed layout: X[b] of every frame's every A-scan, unscaled; its modulus is
+        what process() gives with raw magnitudes.  `averages` must be 1.  PCIe-inclusive, synchronous.  out: a caller-owned
+        C-contiguous complex64 array of that shape instead of a fresh one."""
+        a = np.ascontiguousarray(frames)
+        if a.ndim == 2:
+            a = a[None]
+        if a.dtype not in _NP2DT:
+            raise FdoctError(-1, "unsupported frame dtype %s" % a.dtype)
+        if a.ndim == 4 and (a.shape[3] != 3 or a.dtype != np.uint8):
+            raise FdoctError(-1, "colour frames are (nframes, rows, cols, 3) uint8")
+        n, h, d = a.shape[0], self.cfg.height, self.cfg.numdisplaypoints
+        shp = (n, d, h) if layout == LAYOUT_TRANSPOSED else (n, h, d)
+        if out is None:
+            out = np.empty(shp, np.complex64)
+        elif out.dtype != np.complex64 or out.shape != shp or not out.flags.c_contiguous:
+            raise FdoctError(-1, "result array must be C-contiguous complex64 of shape %s" % (shp,))
+        self._check(self.lib.fdoct_process_complex(self.h, a.ctypes.data, _NP2DT[a.dtype], MEM_HOST, n, a.strides[1], out.ctypes.data,
+                                                   MEM_HOST, layout))
+        return out
+
+    def process_complex_device(self, d_frames_ptr, dtype, nframes, pitch_bytes, d_out_ptr, layout=LAYOUT_ROWMAJOR):
+        """... on device-resident frames into nframes * H * D (re, im) float pairs of device memory (raw addresses, d_out_ptr aligned
+        to 8 bytes).  Enqueues on the handle's stream."""
+        self._check(self.lib.fdoct_process_complex(self.h, d_frames_ptr, dtype, MEM_DEVICE, int(nframes), int(pitch_bytes), d_out_ptr,
+                                                   MEM_DEVICE, layout))
 
     def set_timing(self, on=True):
         """Device-side timing events for process_device() (process() always has them); see fdoct_set_timing."""

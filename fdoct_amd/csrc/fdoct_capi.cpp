@@ -549,16 +549,16 @@ long long fdoct_jit_compile_check(int width, int multiplier, int numfftpoints, i
   std::string reason;
   long long n = -1;
   const int kdt = kernel_dtype(dtype);
+  // (FDOCT_JIT_CHECK_OPT: the kernel's option mask -- fdoct_wave.h, FDOCT_WAVE_OPT_* -- for build checks of the optional stages; the
+  // shape is judged with it, as a call's route judges it: a display beyond numfftpoints / 2 needs the mirror option or complex rows)
+  const char* eo = std::getenv("FDOCT_JIT_CHECK_OPT");
+  const int opt = eo ? std::atoi(eo) : 0;
   if (!gcn_arch || !*gcn_arch)
     reason = "no architecture named";
-  else if (!wave_jit_shape_ok(width, multiplier, numfftpoints, numdisplaypoints))
+  else if (!wave_jit_shape_ok(width, multiplier, numfftpoints, numdisplaypoints, opt))
     reason = "the wave-per-row kernel cannot take this shape";
   else
-  {
-    // (FDOCT_JIT_CHECK_OPT: the kernel's option mask -- fdoct_wave.h, FDOCT_WAVE_OPT_* -- for build checks of the optional stages)
-    const char* eo = std::getenv("FDOCT_JIT_CHECK_OPT");
-    n = wave_jit_compile_only(width, multiplier, numfftpoints, kdt, numdisplaypoints, eo ? std::atoi(eo) : 0, gcn_arch, &reason);
-  }
+    n = wave_jit_compile_only(width, multiplier, numfftpoints, kdt, numdisplaypoints, opt, gcn_arch, &reason);
   if (why && why_len > 0) std::snprintf(why, (size_t)why_len, "%s", reason.c_str());
   return n;
 } FDOCT_CATCH_RETURN(nullptr, -1)

@@ -14,6 +14,7 @@
 //   fdoct_manualavg.cpp those of include/fdoct_manualavg.h (manual averaging of B-scans: manualaccum and its counter)
 //   fdoct_saveframes.cpp those of include/fdoct_saveframes.h (per-frame saves while averaging; the raw-magnitudes switch)
 //   fdoct_calibrate.cpp those of include/fdoct_calibrate.h (BscanDark's calibration: device-side normalisations, held captures, composition)
+//   fdoct_complex.cpp that of include/fdoct_complex.h (the complex A-scan: the chain through fdoct_route.cpp's enqueue_complex, the D x H layout)
 //   fdoct_stage.h     the staging plan of host-memory arguments: the side entry points', fdoct_process's single shot (stage_reserve / stage_upload / stage_finish, below, commit it)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
@@ -236,6 +237,8 @@ struct fdoct_ctx {
   bool cal_held[3] = {false, false, false};
   DevBuf<double> ws_cal_next;      // the frame a capture is writing: swapped with its slot when the capture has succeeded
   DevBuf<double> ws_cal_mm;        // min / max partials and the (scale, shift) pairs made from them (MinMaxShape::ws_doubles)
+  // the complex A-scan (fdoct_complex.cpp): the chain's row-major pairs on their way to the D x H layout
+  DevBuf<float2> ws_cx;
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
@@ -430,6 +433,7 @@ struct Call {
   long long in_rows = 0, out_rows = 0;
   size_t es = 0;                    // bytes per sample of the CALLER's frames (the algorithmic-bytes figure)
   float *k_mag = nullptr, *k_db = nullptr;          // where the chain's kernel writes (the caller's arrays, or the transpose pass's input)
+  float2* k_cx = nullptr;           // the complex call (enqueue_complex): (re, im) pairs go here and k_mag / k_db stay null
   float *d_out_bscan = nullptr, *d_out_db = nullptr;
   hipStream_t st = nullptr;
 };
@@ -456,6 +460,9 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
 int check_call(fdoct_ctx* h, fdoct_dtype dtype, size_t pitch_bytes, const float* out_bscan, const float* out_db);
 int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes,
             float* d_out_bscan, float* d_out_db, fdoct_layout layout);
+// The complex A-scan of device-resident frames, row-major [nframes H D] (re, im) pairs (include/fdoct_complex.h: the add-on library's
+// entry point calls it).  d_out null: the checks and the route only -- nothing is enqueued.
+int enqueue_complex(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes, float2* d_out);
 
 // ---- fdoct_pipeline.cpp ---------------------------------------------------------------------------------------------------
 bool host_pointer_is_pinned(const void* p);

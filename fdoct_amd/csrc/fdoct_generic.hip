@@ -235,7 +235,9 @@ __device__ __forceinline__ float load_sample(const void* row, int dtype, int i) 
 // loops all stride by blockDim.x, and a CU with one 256-thread workgroup is one wave per SIMD waiting on its own barriers.
 // IP: ONE DFT buffer instead of two (rows of 8000 ... 16000 complex points: 4096 samples upsampled x8): every step that would
 // read one buffer and write the other reads its inputs into registers, meets at a barrier, then writes.
-template <int NT, int MINB, bool IP = false>
+// CX: the complex A-scan instead of its magnitude (include/fdoct_complex.h): the first D bins of the final transform go to
+// a.out_cx as (re, im) pairs straight from the untangle, and the accumulate / epsilon / log epilogue is not run.
+template <int NT, int MINB, bool IP = false, bool CX = false>
 __global__ __launch_bounds__(NT, MINB) void generic_kernel(const GenericArgs a) {
   extern __shared__ __align__(16) unsigned char gsm[];
   const int W = a.W, M = a.M, MW = a.W * a.M, N = a.N, D = a.D, L = a.L;
@@ -566,18 +568,31 @@ __global__ __launch_bounds__(NT, MINB) void generic_kernel(const GenericArgs a) 
           const float ax = zk.x + zp.x, ay = zk.y - zp.y, bx = zk.x - zp.x, by = zk.y + zp.y;
           const float qx = fmaf(-w.y, by, w.x * bx), qy = fmaf(w.y, bx, w.x * by);
           const float xr = ax + qy, xi = ay - qx;
-          const float m = 0.5f * sqrtf(fmaf(xr, xr, xi * xi));
-          accbuf[b] = (ai == 0) ? m : accbuf[b] + m;  // each bin belongs to one thread: no race
+          if constexpr (CX) {  // X[b] itself; above N/2 the conjugate of its mirror bin
+            a.out_cx[(size_t)o * D + b] = make_float2(0.5f * xr, b > NC ? -0.5f * xi : 0.5f * xi);
+          } else {
+            const float m = 0.5f * sqrtf(fmaf(xr, xr, xi * xi));
+            accbuf[b] = (ai == 0) ? m : accbuf[b] + m;  // each bin belongs to one thread: no race
+          }
         }
       } else {
         const float2* X = (a.blu_m && !IP) ? bluestein_inverse(fin, fout, N, a) : fft_lds<true, IP, R16>(fin, fout, N, a.rad_n, a.mag_n, a.npass_n, a.tw_n, tid);
         for (int b = tid; b < D; b += nt) {
           const float2 x = X[b];
-          const float m = sqrtf(fmaf(x.x, x.x, x.y * x.y));
-          accbuf[b] = (ai == 0) ? m : accbuf[b] + m;
+          if constexpr (CX) {
+            a.out_cx[(size_t)o * D + b] = x;
+          } else {
+            const float m = sqrtf(fmaf(x.x, x.x, x.y * x.y));
+            accbuf[b] = (ai == 0) ? m : accbuf[b] + m;
+          }
         }
       }
       __syncthreads();
+    }
+    if constexpr (CX) {  // (the pairs are out: no average, epsilon or dB -- the host launches this form with A == 1 only)
+      o = a.row_ticket ? next_row[parity] : o + gridDim.x;
+      parity ^= 1;
+      continue;
     }
 
     // ---- A9/A10
@@ -638,6 +653,12 @@ hipError_t launch_generic(const GenericArgs& a, int grid, size_t lds, hipStream_
   int nt = per_cu >= 3 ? 256 : (per_cu == 2 ? 512 : 1024);
   if (force_nt == 256 || force_nt == 512 || force_nt == 1024) nt = force_nt;
   if (a.radix16) nt = 1024;  // (the plan holds radix-16 passes: only the 1024-thread kernels have them)
+  if (a.out_cx) {  // the complex A-scan: the same four forms with the CX switch
+    if (a.inplace) return launch_generic_one<generic_kernel<1024, 1, true, true>>(a, grid, 1024, lds, st);
+    if (nt == 1024) return launch_generic_one<generic_kernel<1024, 1, false, true>>(a, grid, 1024, lds, st);
+    if (nt == 512) return launch_generic_one<generic_kernel<512, 2, false, true>>(a, grid, 512, lds, st);
+    return launch_generic_one<generic_kernel<256, 6, false, true>>(a, grid, 256, lds, st);
+  }
   if (a.inplace) return launch_generic_one<generic_kernel<1024, 1, true>>(a, grid, 1024, lds, st);  // (one DFT buffer: the host has checked its limits)
   if (nt == 1024) return launch_generic_one<generic_kernel<1024, 1>>(a, grid, 1024, lds, st);
   if (nt == 512) return launch_generic_one<generic_kernel<512, 2>>(a, grid, 512, lds, st);

@@ -153,6 +153,7 @@ struct GenericArgs {
   float* out_mag;
   float* out_db;
   unsigned* row_ticket;      // launch-wide row counter, zero at launch (rows beyond the workgroups' first are claimed from it), or null
+  float2* out_cx;            // not null: the complex A-scan instead (include/fdoct_complex.h) -- [rows*D] (re, im), A == 1, out_mag / out_db unused
 };
 
 hipError_t launch_generic(const GenericArgs& a, int grid, size_t lds, hipStream_t st);

@@ -350,10 +350,16 @@ static bool transposed_store_callable(const fdoct_ctx* h, fdoct_dtype dtype, uin
 
 // Decides the route of a call.  frames_addr / pitch_bytes / out addresses: as the caller gave them (fdoct_prepare: an aligned,
 // packed set-up).  May rebuild device tables and compile (hipRTC) -- never launches.
-int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
-                 uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r) {
+// cx: the route of the complex A-scan (enqueue_complex): the same checks and passes in front of the chain, the family restricted to the
+// two whose kernels write it -- the wave-per-row kernel compiled at run time with FDOCT_WAVE_OPT_CXOUT for every shape it takes, the
+// workgroup-per-row kernel for the rest -- whatever the handle's plan; rows only the long-row path takes are refused.  Reads the handle's
+// adopted plan and changes none of it.
+static int choose_route_of(fdoct_ctx* h, bool cx, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
+                           uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r) {
   int rc;
-  if ((rc = h->plan.fused ? ensure_fused_tables(h) : ensure_generic_tables(h))) return rc;
+  if (cx && h->plan.gen.use_big)
+    return fail(h, FDOCT_ERR_UNSUPPORTED, "the complex A-scan is not written by the long-row path (rows that do not fit a compute unit's LDS)");
+  if ((rc = (h->plan.fused && !cx) ? ensure_fused_tables(h) : ensure_generic_tables(h))) return rc;
   if (h->D > h->N) return fail(h, FDOCT_ERR_INVALID, "numdisplaypoints > numfftpoints");
   const int W = h->W, H = h->H, D = h->D, A = h->A;
   const long long out_rows = (long long)(nframes / A) * H;
@@ -385,7 +391,7 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
   const int wave_opt = (h->yp.rows ? FDOCT_WAVE_OPT_PI : 0) | (h->yd.rows ? FDOCT_WAVE_OPT_DARK : 0) |
                        (h->bandpass && h->M > 1 ? FDOCT_WAVE_OPT_BANDPASS : 0) | (h->cfg.rowwisenormalize ? FDOCT_WAVE_OPT_ROWNORM : 0) |
                        (r->need_minmax ? FDOCT_WAVE_OPT_FRAMENORM : 0) | (!h->phase.empty() ? FDOCT_WAVE_OPT_CPLX : 0) |
-                       (h->phase.empty() && D > h->N / 2 ? FDOCT_WAVE_OPT_DEEP : 0);
+                       (h->phase.empty() && D > h->N / 2 ? FDOCT_WAVE_OPT_DEEP : 0) | (cx ? FDOCT_WAVE_OPT_CXOUT : 0);
   // The wave-per-row kernel's launch, where its tables leave room for at least one wave's buffers: as many waves as LDS and
   // the shape's register budget allow, at most one workgroup per CU.
   auto wave_fits = [&](int opt) {
@@ -404,7 +410,7 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
   // for the handle does the binning in its own loads (FDOCT_WAVE_OPT_BIN2) and the pass over the raw frames is skipped.
   // (Measured on the shipped shapes, tools/bench_generic.py with and without FDOCT_JIT=0: + 4.5 % on 160-sample 8-bit rows, + 5 % on
   // 640-sample 16-bit rows, - 1 % on 640-sample 8-bit rows -- twenty 2-byte loads per lane cost what the pass saves: those keep the pass.)
-  if (h->fe_median == 0 && h->fe_binx == 2 && h->fe_biny == 2 && (dtype == FDOCT_U16 || (dtype == FDOCT_U8 && W <= 320)) && h->cfg.movavgn == 0 &&
+  if (!cx && h->fe_median == 0 && h->fe_binx == 2 && h->fe_biny == 2 && (dtype == FDOCT_U16 || (dtype == FDOCT_U8 && W <= 320)) && h->cfg.movavgn == 0 &&
       h->jit && !h->plan.fused && !h->plan.gen.use_big && h->plan_override > -2 && h->phase.empty() && D <= h->N / 2 && !r->need_minmax &&
       (frames_addr % 4 == 0) && (pitch_bytes % 4 == 0) && pitch_bytes >= es * 2 * (size_t)W && out_rows < 0x7fffffffLL &&
       wave_jit_shape_ok(W, h->M, h->N, D)) {
@@ -454,7 +460,7 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
   // the specialised kernels read 16-byte vectors; anything else goes through the generic kernel
   const size_t valign = (kdt == FDOCT_K_U8) ? 8 : 16;
   const bool misaligned = (kaddr % valign) || (kpitch % valign);
-  const bool run_generic = !h->plan.fused || misaligned;
+  const bool run_generic = cx || !h->plan.fused || misaligned;
   if (run_generic && (rc = ensure_generic_tables(h))) return rc;
   if (run_generic && h->staged) return fail(h, FDOCT_ERR_UNSUPPORTED, "staged mode needs a specialised kernel for this configuration");
 
@@ -465,7 +471,7 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
     std::string why;
     if ((rc = make_fused_launch(h->plan, fused_launch_inputs(h, kdt, nframes, r->need_minmax, r->frames_lo(), want_tro), &r->fused, &why))) return fail(h, rc, why);
   }
-  r->transpose_pass = transposed && !r->fused.tro;
+  r->transpose_pass = !cx && transposed && !r->fused.tro;   // (the complex call's D x H layout is made by its own entry point)
 
   // the acquisition configurations the reference ships: one wave per A-scan (fdoct_wave.hip) instead of one workgroup
   // (frames handed over as doubles carry a low word per sample: the fused any-option, workgroup-per-row and long-row kernels take it)
@@ -475,7 +481,7 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
   bool run_wave = r->bin2_in_kernel;
   bool wave_builtin = false;
   if (wave_scope && !run_wave) {
-    wave_builtin = wave_opt == 0 && wave_kernel_available(W, h->M, h->N, kdt, D);
+    wave_builtin = wave_opt == 0 && wave_kernel_available(W, h->M, h->N, kdt, D);   // (never the complex call's: its option bit is set)
     // any other shape the template can take: compiled for this handle's geometry at run time (fdoct_set_jit); the first call
     // (or fdoct_prepare) pays the compile, a refusal falls back to the workgroup-per-row kernel
     if (!wave_builtin && h->jit && wave_jit_shape_ok(W, h->M, h->N, D, wave_opt)) {
@@ -516,6 +522,11 @@ int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t 
   return FDOCT_OK;
 }
 
+int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
+                 uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r) {
+  return choose_route_of(h, false, dtype, frames_addr, pitch_bytes, out_bscan_addr, out_db_addr, layout, nframes, r);
+}
+
 // After the chain's kernel(s) of any family: end-of-kernel event, the transpose pass where the chain did not write D x H itself,
 // end-of-call event, and the call's figures for fdoct_get_timing.
 int finish_launch(fdoct_ctx* h, const Route& r, const Call& c, bool staged_timing) {
@@ -529,7 +540,7 @@ int finish_launch(fdoct_ctx* h, const Route& r, const Call& c, bool staged_timin
   h->last_kernel = r.family;
   h->timing.ascans = (uint64_t)c.in_rows;
   h->timing.bytes_in = (uint64_t)c.in_rows * h->W * c.es;
-  h->timing.bytes_out = (uint64_t)c.out_rows * h->D * 4 * ((c.d_out_bscan ? 1 : 0) + (c.d_out_db ? 1 : 0));
+  h->timing.bytes_out = (uint64_t)c.out_rows * h->D * 4 * ((c.d_out_bscan ? 1 : 0) + (c.d_out_db ? 1 : 0) + (c.k_cx ? 2 : 0));
   h->timing_pending = h->record_now;
   h->timing_staged = staged_timing;
   return FDOCT_OK;
@@ -569,6 +580,7 @@ int launch_family_wave(fdoct_ctx* h, const Route& r, const Call& c) {
   wa.yd = h->d_yd; wa.yd_2d = h->yd.rows > 1;
   wa.minmax = r.need_minmax ? h->d_minmax : nullptr;
   wa.phase = h->d_phase;
+  wa.out_cx = c.k_cx;
 #ifdef FDOCT_WAVE_PROBE  // measurement build: per-phase cycles of the first workgroups' waves, printed every 50 calls
   {
     static unsigned long long* d_probe = nullptr;
@@ -689,6 +701,7 @@ int launch_family_generic(fdoct_ctx* h, const Route& r, const Call& c) {
   ga.db_scale = kDbScale;
   ga.out_mag = c.k_mag;
   ga.out_db = c.k_db;
+  ga.out_cx = c.k_cx;
   {
     // the launch's row counter: one of 64 words used in turn, zeroed on the stream in front of the launch (no host
     // synchronisation; 64 launches of one handle are never in flight together)
@@ -977,6 +990,46 @@ int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nfram
     case FDOCT_KERNEL_GENERIC: return launch_family_generic(h, r, c);
     default: return launch_family_fused(h, r, c);
   }
+}
+
+// The complex A-scan (include/fdoct_complex.h; the entry point is the add-on library's, fdoct_complex.cpp): the chain of enqueue_one up
+// to the final transform, whose first numdisplaypoints bins go out as (re, im) pairs, row-major, to d_out -- [nframes H D].  Device
+// memory on both sides, enqueues only.  d_out null: every check, the route (which may compile) and nothing else -- what the entry point
+// asks before it copies host frames up; frames_addr is then all that is read of d_frames.
+int enqueue_complex(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes, float2* d_out) {
+  if (!h) return FDOCT_ERR_INVALID;
+  if (!d_frames || nframes <= 0) return fail(h, FDOCT_ERR_INVALID, "no frames");
+  if (!h->yb.rows) return fail(h, FDOCT_ERR_STATE, "no background set (fdoct_set_background)");
+  // the reference averages magnitudes (main:1192-1211); a mean of complex A-scans is another quantity, which nothing here defines
+  if (h->A != 1 || h->sim_group != 1) return fail(h, FDOCT_ERR_UNSUPPORTED, "the complex A-scan needs averages = 1");
+  const size_t es = frame_pixel_bytes(h, dtype);
+  if (!es) return fail(h, FDOCT_ERR_INVALID, "bad dtype");
+  if (pitch_bytes && pitch_bytes < es * h->W * h->fe_binx) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a row");
+  if (pitch_bytes == 0) pitch_bytes = es * h->W * h->fe_binx;
+  DEVICE_SCOPE(h);
+  int rc;
+  Route r;
+  if ((rc = choose_route_of(h, true, dtype, (uintptr_t)d_frames, pitch_bytes, 0, 0, FDOCT_LAYOUT_ROWMAJOR_HxD, nframes, &r))) return rc;
+  if (r.family != FDOCT_KERNEL_WAVE_JIT && r.family != FDOCT_KERNEL_GENERIC) return fail(h, FDOCT_ERR_DEVICE, "internal: the complex A-scan routed to a kernel that does not write it");
+  if (!d_out) return FDOCT_OK;
+  Call c;
+  c.st = h->stream;
+  c.nframes = nframes;
+  c.G = nframes;
+  c.in_rows = c.out_rows = (long long)nframes * h->H;
+  c.es = es;
+  c.kframes = d_frames;
+  c.k_cx = d_out;
+  h->rec_first = h->rec_last = true;
+  h->record_now = h->async_timing;  // (event records cost stream time: as fdoct_process_async, only where fdoct_set_timing asked)
+  if (h->record_now) HIP_TRY(h, hipEventRecord(h->ev[0], c.st));
+  if ((rc = run_passes_in_front(h, r, c, d_frames, dtype, pitch_bytes))) return rc;
+  if (r.need_minmax) {
+    const size_t mm_elems = (size_t)nframes + (size_t)minmax_partial_count(nframes);
+    if ((rc = h->d_minmax.reserve(h, mm_elems * sizeof(float2)))) return rc;
+    HIP_TRY(h, launch_minmax(c.kframes, r.kdt, (long long)r.kpitch, h->W, h->H, nframes, h->d_yd, h->yd.rows > 1, h->d_minmax, h->d_minmax + nframes, c.st));
+  }
+  return r.family == FDOCT_KERNEL_GENERIC ? launch_family_generic(h, r, c) : launch_family_wave(h, r, c);
 }
 
 // The whole path for device-resident frames.  The reference's own layout (bscan is D x H, main:1220) is produced by the

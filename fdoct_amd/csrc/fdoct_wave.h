@@ -135,6 +135,8 @@ constexpr bool wave_resident_tables(int W, int M, int N) {
 #define FDOCT_WAVE_OPT_CPLX 64       // dispersion phase (fdoct_set_dispersion_phase; wangOCTrec4.m:130-131, 169): data_ylin[q] times a unit phasor, then the
                                      // FULL numfftpoints-point complex transform (no real-input untangle), any numdisplaypoints <= numfftpoints
 #define FDOCT_WAVE_OPT_DEEP 128      // real rows displayed beyond numfftpoints / 2: bins above it mirror (|X[b]| = |X[N - b]|), bin N/2 from Z[0]
+#define FDOCT_WAVE_OPT_CXOUT 256     // the complex A-scan instead of its magnitude (include/fdoct_complex.h): X[b] = (re, im) to WaveArgs::out_cx, averages 1; no
+                                     // average, epsilon or dB.  Only ever compiled at run time: no built-in instantiation has it
 // the final transform's length in complex points: the whole row for complex rows, half of it for real ones
 constexpr int wave_final_points(int N, int opt) { return (opt & FDOCT_WAVE_OPT_CPLX) ? N : N / 2; }
 
@@ -180,6 +182,7 @@ struct WaveArgs {
   const void* minmax;  // float2 (min, max) per input frame, OPT & FDOCT_WAVE_OPT_FRAMENORM
   const float2* phase;  // [N] (cos, sin), OPT & FDOCT_WAVE_OPT_CPLX
   unsigned long long* probe;  // measurement builds (-DFDOCT_WAVE_PROBE): cycles per phase of one wave; null otherwise
+  float2* out_cx;  // [total_out_rows * D] (re, im), 8-byte aligned, OPT & FDOCT_WAVE_OPT_CXOUT (then out_mag / out_db are not written)
 };
 
 #ifndef __HIPCC_RTC__

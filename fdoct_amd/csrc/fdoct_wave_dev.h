@@ -282,11 +282,12 @@ struct wave_select<false, A, B> { typedef B type; };
 // normalisation (main:1126-1129; BscanFFTsim.cpp:845 always normalises).  The library's own instantiations are
 // OPT = 0; a handle that uses an option gets its kernel from the run-time compiler (fdoct_jit.cpp).
 // FDOCT_WAVE_OPT_CPLX: the dispersion phase (complex rows: full-length final transform, no untangle); FDOCT_WAVE_OPT_DEEP: real
-// rows displayed beyond numfftpoints / 2.
+// rows displayed beyond numfftpoints / 2.  FDOCT_WAVE_OPT_CXOUT: the untangle keeps X[b] itself and the epilogue stores (re, im)
+// pairs to out_cx -- no magnitude, average, epsilon or dB (include/fdoct_complex.h; run-time compiled only).
 // DKP: numdisplaypoints <= DKP is guaranteed by the launch (0: no bound beyond 64 TD; wave_depth_bound)
 template <int W, int M, int N, typename IN_T, int TD, int OPT = 0, int DKP = 0>
 __global__ __launch_bounds__(wave_block_of(W, M, N, OPT)) void wave_kernel(const WaveArgs a) {
-  constexpr bool CPLX = (OPT & FDOCT_WAVE_OPT_CPLX) != 0, DEEP = (OPT & FDOCT_WAVE_OPT_DEEP) != 0;
+  constexpr bool CPLX = (OPT & FDOCT_WAVE_OPT_CPLX) != 0, DEEP = (OPT & FDOCT_WAVE_OPT_DEEP) != 0, CXOUT = (OPT & FDOCT_WAVE_OPT_CXOUT) != 0;
   static_assert(!(CPLX && DEEP), "complex rows take any depth as they are");
   constexpr int MW = M * W, NC = wave_final_points(N, OPT), WH = W / 2, LH = MW / 2;
   constexpr int SPL = (MW + 63) / 64;   // upsampled samples per lane in the slope step (contiguous; the last lanes own fewer, or none, when 64 does not divide M W)
@@ -445,6 +446,7 @@ __global__ __launch_bounds__(wave_block_of(W, M, N, OPT)) void wave_kernel(const
     float acc[TD];
 #pragma unroll
     for (int t = 0; t < TD; t++) acc[t] = 0.f;
+    [[maybe_unused]] v2f cx[CXOUT ? TD : 1];   // FDOCT_WAVE_OPT_CXOUT: the bins themselves (averages is 1: the host refuses anything else)
 
     for (int ai = 0; ai < a.A; ai++) {
 #ifdef FDOCT_WAVE_PROBE
@@ -820,7 +822,10 @@ __global__ __launch_bounds__(wave_block_of(W, M, N, OPT)) void wave_kernel(const
         if constexpr (CPLX) {
           if (b < D) {
             const v2f z = buf[b];
-            acc[t] += fast_sqrt(fmaf(z.x, z.x, z.y * z.y));   // main:1190
+            if constexpr (CXOUT)
+              cx[t] = z;
+            else
+              acc[t] += fast_sqrt(fmaf(z.x, z.x, z.y * z.y));   // main:1190
           }
         } else if (b < D) {
           // (DEEP: bins above N/2 mirror, |X[b]| = |X[N - b]|; bin N/2 pairs Z[0] with itself)
@@ -831,7 +836,10 @@ __global__ __launch_bounds__(wave_block_of(W, M, N, OPT)) void wave_kernel(const
           const float ax = zkk.x + zpp.x, ay = zkk.y - zpp.y, bx = zkk.x - zpp.x, by = zkk.y + zpp.y;
           const float qx = fmaf(-w.y, by, w.x * bx), qy = fmaf(w.y, bx, w.x * by);
           const float xr = ax + qy, xi = ay - qx;
-          acc[t] += 0.5f * fast_sqrt(fmaf(xr, xr, xi * xi));
+          if constexpr (CXOUT)
+            cx[t] = mk(0.5f * xr, (DEEP && b > NC) ? -0.5f * xi : 0.5f * xi);   // (DEEP: X[b] = conj(X[N - b]) above N/2)
+          else
+            acc[t] += 0.5f * fast_sqrt(fmaf(xr, xr, xi * xi));
         }
       }
       wave_fence();
@@ -841,6 +849,17 @@ __global__ __launch_bounds__(wave_block_of(W, M, N, OPT)) void wave_kernel(const
     pr_t = __builtin_readcyclecounter();
 #endif
 
+    // FDOCT_WAVE_OPT_CXOUT: the row's bins as they are, one 8-byte store per bin, lane-consecutive (512 bytes per wave instruction)
+    if constexpr (CXOUT) {
+      v2f* oc = reinterpret_cast<v2f*>(a.out_cx) + (size_t)o * D;
+#pragma unroll
+      for (int t = 0; t < TD; t++) {
+        const int b = lane + 64 * t;
+        if (b < D) __builtin_nontemporal_store(cx[t], oc + b);
+      }
+      FDOCT_PR(8);
+      continue;
+    }
     // ---- A9/A10: average, epsilon, dB (2.303), DC mask; bins lane + 64 t: coalesced stores
     float* om = a.out_mag ? a.out_mag + (size_t)o * D : nullptr;
     float* od = a.out_db ? a.out_db + (size_t)o * D : nullptr;
