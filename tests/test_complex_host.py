@@ -2,7 +2,8 @@
 and the other two libraries none of them, the entry point is a function-try-block, the header compiles as C99 next to fdoct.h,
 a NULL handle is refused with the output untouched, the binding checks its arguments, and the wave-per-row kernel's device source
 compiles for gfx950 with the option bit that makes it write (re, im) pairs -- alone, with complex rows and with the mirror above
-numfftpoints / 2 -- on the three shapes the GPU tests run it on."""
+numfftpoints / 2 -- on the shapes the GPU tests run it on, and with the option masks, sample types and depth classes that
+tests/test_gpu_complex_options.py adds on that route."""
 import os
 import re
 import subprocess
@@ -15,7 +16,7 @@ from fdoct_amd import capi
 from test_capture_host import _declared, _definitions
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OPT_PI, OPT_DARK, OPT_FRAMENORM, OPT_CPLX, OPT_DEEP, OPT_CXOUT = 1, 2, 16, 64, 128, 256   # FDOCT_WAVE_OPT_* (fdoct_wave.h)
+OPT_PI, OPT_DARK, OPT_BANDPASS, OPT_ROWNORM, OPT_FRAMENORM, OPT_CPLX, OPT_DEEP, OPT_CXOUT = 1, 2, 4, 8, 16, 64, 128, 256   # FDOCT_WAVE_OPT_* (fdoct_wave.h)
 
 
 def _exports(path):
@@ -108,6 +109,18 @@ JIT_CASES = [
     ("2048 -> 2048, D 1024, complex rows", 2048, 1, 2048, 1024, capi.DTYPE_U16, OPT_CPLX),
     ("640 -> 640, D 640, mirror", 640, 1, 640, 640, capi.DTYPE_U8, OPT_DEEP),
     ("200 x4 -> 2560, D 320, pi + dark + whole-frame normalisation", 200, 4, 2560, 320, capi.DTYPE_U16, OPT_PI | OPT_DARK | OPT_FRAMENORM),
+    # ... and the option masks and shapes tests/test_gpu_complex_options.py adds on that route
+    ("200 x4 -> 2560, D 320, band-pass", 200, 4, 2560, 320, capi.DTYPE_U16, OPT_BANDPASS),
+    ("200 x4 -> 2560, D 320, row-wise normalisation", 200, 4, 2560, 320, capi.DTYPE_U16, OPT_ROWNORM),
+    ("200 x4 -> 2560, D 320, band-pass + row-wise normalisation + pi + dark", 200, 4, 2560, 320, capi.DTYPE_U16, OPT_BANDPASS | OPT_ROWNORM | OPT_PI | OPT_DARK),
+    ("160 x4 -> 2560, D 320, complex rows", 160, 4, 2560, 320, capi.DTYPE_U16, OPT_CPLX),
+    ("640 -> 640, D 640, complex rows", 640, 1, 640, 640, capi.DTYPE_U16, OPT_CPLX),
+    ("1280 x4 -> 2560, D 320", 1280, 4, 2560, 320, capi.DTYPE_U16, 0),
+    ("640 x4 -> 2560, D 320", 640, 4, 2560, 320, capi.DTYPE_U16, 0),
+    ("200 x4 -> 2560, D 320, f32 frames", 200, 4, 2560, 320, capi.DTYPE_F32, 0),
+    ("640 -> 640, D 1", 640, 1, 640, 1, capi.DTYPE_U16, 0),
+    ("640 -> 640, D 321, mirror (bin N/2 alone)", 640, 1, 640, 321, capi.DTYPE_U16, OPT_DEEP),
+    ("200 x4 -> 2560, D 2560, mirror", 200, 4, 2560, 2560, capi.DTYPE_U16, OPT_DEEP),
 ]
 
 
