@@ -1,4 +1,4 @@
-// fdoct_big_plan.h -- what the long-row path (fdoct_big.hip, run_big in fdoct_route.cpp) decides on the host, as values made before
+// fdoct_big_plan.h -- what the long-row path (fdoct_big.hip, run_big in fdoct_big_host.cpp) decides on the host, as values made before
 // anything is enqueued: how the passes of an n-point transform are dealt to grouped launches, the radices of the one-launch-per-pass
 // form, the length of the power-of-two transforms a chirp (Bluestein) transform runs around, and how a batch is cut into chunks of
 // whole averaging groups that fit the workspace budget.  Plain C++ without HIP: tests/native/bigplan_check.cpp asserts the

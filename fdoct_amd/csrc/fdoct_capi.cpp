@@ -523,8 +523,9 @@ int fdoct_prepare(fdoct_handle h, fdoct_dtype dtype, fdoct_layout layout) try {
   DEVICE_SCOPE(h);
   // the call fdoct_process* will see: aligned device frames, packed rows, one averaging group, both images asked for
   Route r;
-  const int rc = choose_route(h, dtype, 0, es * (size_t)h->W * h->fe_binx, 0, 0, layout, h->A, &r);
-  if (rc) return rc;
+  RouteInputs in = route_inputs(h, dtype, 0, es * (size_t)h->W * h->fe_binx, h->A);
+  in.layout = layout;
+  if (int rc = choose_route(h, in, &r)) return rc;
   return r.family;
 } FDOCT_CATCH(h)
 

@@ -1,8 +1,10 @@
 // fdoct_ctx.h -- what the translation units of the C-ABI layer share: the handle (fdoct_ctx), the error / device-scope /
 // device-memory helpers, and the declarations of
 //   fdoct_state.cpp   the handle's plan (fdoct_plan.h) and everything a handle uploads to its device (tables, planes, twiddles)
-//   fdoct_route.cpp   the dispatch: choose_route (with fdoct_launch.h's launch value), the passes in front of the chain, one launcher
-//                     per kernel family, enqueue
+//   fdoct_route.cpp   the dispatch: choose_route (which carries out fdoct_route_value.h's route value), the passes in front of the
+//                     chain, one launcher per kernel family, enqueue
+//   fdoct_route_value.cpp the route of a call as a value, decided before anything is enqueued (make_route; plain C++ like the planner)
+//   fdoct_big_host.cpp the long-row path's host side: the plans and tables of its transforms, their grouped launches, run_big
 //   fdoct_capi.cpp    the extern "C" entry points of include/fdoct.h
 //   fdoct_hostcall.h  what fdoct_process* decide on the host before anything is enqueued, as a value (make_host_call)
 //   fdoct_pipeline.cpp fdoct_process's three-stream pipeline for host buffers on both sides, and its copy threads
@@ -39,6 +41,7 @@
 #include "fdoct_host.h"
 #include "fdoct_kernels.h"
 #include "fdoct_launch.h"
+#include "fdoct_route_value.h"
 #include "fdoct_hostcall.h"
 #include "fdoct_stage.h"
 #include "fdoct_wave.h"
@@ -157,7 +160,6 @@ struct fdoct_ctx {
   // wave-per-row kernels (fdoct_wave.hip)
   DevBuf<uint32_t> d_wave_gidx;
   DevBuf<float2> d_wave_tw;
-  int wave_tw_count = 0, wave_off[6] = {0, 0, 0, 0, 0, 0};
   DevBuf<float2> d_twg_n, d_twg_nh, d_twg_w, d_twg_mw, d_twg_wh, d_twg_mwh;
   // long-row path (fdoct_big.hip): rows in HBM, one DFT plan per length
   using BigGroupPlan = fdoct::BigGroupPlan;  // one launch: a group of the transform's passes with the data in LDS (fdoct_big_plan.h)
@@ -337,8 +339,7 @@ inline int stage_finish(fdoct_ctx* h, const StagePlan& p) {
 inline void builtin_jet(unsigned char* bgr) { build_opencv_jet(bgr); }
 
 // ---- fdoct_state.cpp ------------------------------------------------------------------------------------------------------
-// Each family's device tables, built by its ensure_*_tables when they do not match the host state.
-enum : unsigned { TABLES_FUSED = 1, TABLES_GENERIC = 2, TABLES_WAVE = 4 };
+// Each family's device tables (TABLES_*, fdoct_route_value.h), built by its ensure_*_tables when they do not match the host state.
 inline void invalidate(fdoct_ctx* h) { h->tables_ok = 0; }
 
 // Waits for everything the handle has enqueued: nothing is left in flight that still points at the caller's buffers or the
@@ -380,7 +381,6 @@ inline int caught(fdoct_ctx* h) noexcept {
 #define FDOCT_CATCH_RETURN(h, value) catch (...) { (void)caught(h); return value; }
 #define FDOCT_CATCH_VOID(h) catch (...) { (void)caught(h); }
 
-size_t dtype_size(int dt);
 int copy_ref_frame(fdoct_ctx* h, RefFrame& dst, const void* data, fdoct_dtype dtype, int rows, size_t pitch);
 PlanInputs plan_inputs(const fdoct_ctx* h);
 int adopt_plan(fdoct_ctx* h, const PlanInputs& in);
@@ -399,30 +399,9 @@ int ensure_wave_tables(fdoct_ctx* h);
 // and that family's launch -- instantiation, block, LDS, grid.  A function of the handle's state and of the call's geometry only
 // (pointers enter through their alignment), so that fdoct_prepare makes the same decisions -- pays for a run-time compile, meets
 // the same refusals -- without frames.  The launchers fill argument blocks from handle and route and launch; they decide nothing.
-enum class PrePass {  // the pass that produces what the chain's kernel reads
-  None,               // the caller's frames (or the front end's output) as they are
-  F64Split,           // data_y doubles split once into two f32 planes, hi + lo (main:987)
-  MovAvg,             // smoothmovavg (main:990-991), one f32 plane
-  MovAvgF64,          // ... of doubles: the tap sums in double, two planes
-  MovAvgF32Wide,      // ... of FLOAT frames likewise (their samples need not be integers)
-};
-struct Route {
-  int family = FDOCT_KERNEL_NONE;   // fdoct_kernel: who runs the chain
-  bool frontend = false;            // medianBlur + binning pass over the raw frames first (main:953-958)
-  bool colour = false;              // the colour stage first (webcam:1015-1038), median / binning included: the rest is routed as its output is
-  PrePass pre = PrePass::None;
-  int kdt = -1;                     // sample type the chain's kernel reads (FDOCT_K_*)
-  size_t kpitch = 0;                // ... and its row pitch
-  bool need_minmax = false;         // whole-frame min / max pre-pass (main:1128)
-  bool transpose_pass = false;      // a transpose pass makes the D x H layout (the fused chain does not write it itself: fused.tro)
+// The decision is a value made without HIP (make_route, fdoct_route_value.h); a Route is that value with what choose_route adds.
+struct Route : RouteDecision {
   hipFunction_t jit_fn = nullptr;   // FDOCT_KERNEL_WAVE_JIT: the kernel compiled for this handle
-  bool bin2_in_kernel = false;      // ... with the 2 x 2 software binning inside its loads (the raw frames go to it as they are)
-  int wave_opt = 0;                 // FDOCT_WAVE_OPT_* of that kernel
-  FusedLaunch fused;                // the fused families: the launch (fdoct_launch.h)
-  int waves = 0;                    // the wave-per-row families: waves per workgroup ...
-  size_t lds = 0;                   // ... and, for the generic family too, dynamic LDS ...
-  long long grid = 0;               // ... and workgroups
-  bool frames_lo() const { return pre == PrePass::F64Split || pre == PrePass::MovAvgF64 || pre == PrePass::MovAvgF32Wide; }  // a plane of low words goes along
 };
 
 // Quantities of one call that every family's launch needs.
@@ -438,7 +417,6 @@ struct Call {
   hipStream_t st = nullptr;
 };
 
-int kernel_dtype(int dt);
 // Bytes per pixel of the frames a call takes: the sample's size, or 3 for the 8-bit frames of a colour handle.
 inline size_t frame_pixel_bytes(const fdoct_ctx* h, int dtype) { return h->colour >= 0 && dtype == FDOCT_U8 ? 3 : dtype_size(dtype); }
 // What a colour stage can do, checked before anything is enqueued (`who` prefixes the message): 8-bit frames only, no median in
@@ -453,8 +431,9 @@ int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_
                  int binx, int biny, void** out, size_t* out_pitch);
 float chain_eps(const fdoct_ctx* h);  // the epsilon under the chain's log (sim:949 / main:1222)
 float kernel_eps(const fdoct_ctx* h);  // what the chain's kernels are handed for it: chain_eps, or 0 with fdoct_set_raw_magnitudes
-int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
-                 uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r);
+// The inputs of make_route: the handle's part, and a row-major call of `nframes` frames without outputs; the caller adds the rest.
+RouteInputs route_inputs(const fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, int nframes);
+int choose_route(fdoct_ctx* h, const RouteInputs& in, Route* r);
 // What refuses a call without a route and without its frames: no background, no output, a bad dtype, a pitch below a row.  First in
 // enqueue_one; fdoct_process* make it ahead of their own copies.
 int check_call(fdoct_ctx* h, fdoct_dtype dtype, size_t pitch_bytes, const float* out_bscan, const float* out_db);
@@ -463,6 +442,11 @@ int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, 
 // The complex A-scan of device-resident frames, row-major [nframes H D] (re, im) pairs (include/fdoct_complex.h: the add-on library's
 // entry point calls it).  d_out null: the checks and the route only -- nothing is enqueued.
 int enqueue_complex(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes, float2* d_out);
+
+// ---- fdoct_big_host.cpp ---------------------------------------------------------------------------------------------------
+// The whole chain for device-resident frames on the long-row path (fdoct_big.hip), chunk by chunk of whole averaging groups.
+int run_big(fdoct_ctx* h, const void* kframes, const float* kframes_lo, int kdt, size_t kpitch, int nframes, bool need_minmax, float* k_mag, float* k_db,
+            hipStream_t st);
 
 // ---- fdoct_pipeline.cpp ---------------------------------------------------------------------------------------------------
 bool host_pointer_is_pinned(const void* p);

@@ -181,6 +181,7 @@ int make_plan(const PlanInputs& in, Plan* out, std::string* why) {
   p.cplx = in.phase;
   p.NC = p.cplx ? in.N : in.N / 2;
   p.gen.rc = plan_generic(in, p.gen, &p.gen.why);
+  p.wave_tw = wave_tw_layout(in.W, in.M, in.N, in.D, in.phase);
   const bool special_ok = is_pow2(in.N) && in.M == 1 && (in.W % 8) == 0 && (p.cplx || in.D <= in.N / 2) && in.plan_override > -2;
   // preference order for equal NC: the override, then the measured-fastest plan ids
   static const int pref[] = {5, 2, 3, 0, 1, 7, 6, 8, 4};  // per NC: fastest first; equal plans: smallest chunk count that holds W

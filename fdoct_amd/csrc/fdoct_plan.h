@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "fdoct_wave_rules.h"
+
 namespace fdoct {
 
 constexpr int GENERIC_MAX_PASSES = 16;  // Stockham passes of one transform of the generic kernel (GenericArgs)
@@ -58,6 +60,7 @@ struct Plan {
   int NC = 0;                      // points of the final transform: N, or N/2 for real rows
   int split = 0, scratch_bytes = 0, tw_count = 0;  // of the fused plan
   GenericPlan gen;                 // always made: a call the fused kernels cannot take (misaligned frames) runs on it
+  WaveTwLayout wave_tw;            // the wave-per-row kernels' twiddle blob for this geometry (fdoct_wave_rules.h): its tables are filled and its LDS sized by it
 };
 
 // The plan for `in`: FDOCT_OK, or an error code with the reason in *why.  Reads nothing but its arguments and the measurement

@@ -1,23 +1,12 @@
 // fdoct_route.cpp -- the dispatch of a call: choose_route decides everything before anything is enqueued -- the
 // passes in front of the chain, the kernel family and its launch (the fused family's from fdoct_launch.h) --, the passes run, one
-// launcher per kernel family fills its argument block from handle and route, finish_launch is the one epilogue; plus the long-row
-// path's host side (plans, grouped launches) and the front end.  Part of the C-ABI layer (fdoct_ctx.h).
+// launcher per kernel family fills its argument block from handle and route, finish_launch is the one epilogue; plus the front end.
+// The decision itself is a value (make_route, fdoct_route_value.h): choose_route builds its inputs and carries it out.  The long-row
+// path's host side is fdoct_big_host.cpp.  Part of the C-ABI layer (fdoct_ctx.h).
 #include "fdoct_ctx.h"
 #include "fdoct_colour_kernels.h"
 
 namespace fdoct_impl {
-
-int kernel_dtype(int dt) {
-  switch (dt) {
-    case FDOCT_U8: return FDOCT_K_U8;
-    case FDOCT_U16: return FDOCT_K_U16;
-    case FDOCT_F32: return FDOCT_K_F32;
-    default: return -1;
-  }
-}
-
-// rows of the front end's workspaces: packed, 16-byte-pitched
-static size_t frontend_pitch(int w, size_t es) { return packed_pitch((size_t)w * es); }
 
 // medianBlur + INTER_AREA binning of device-resident raw frames into a packed, 16-byte-pitched buffer.
 // Returns the binned frames in *out / *out_pitch (library workspace).  d_raw null: the checks and the workspaces only.
@@ -51,14 +40,9 @@ int run_frontend(fdoct_ctx* h, const void* d_raw, int kdt, int nframes, int raw_
 }
 
 int colour_check(fdoct_ctx* h, const char* who, int channelnum, fdoct_dtype dtype, int mediann) {
-  const std::string w = std::string(who) + ": ";
-  if (channelnum < 0 || channelnum > 3) return fail(h, FDOCT_ERR_INVALID, w + "channelnum must be 0, 1, 2 (B, G, R) or 3 (their sum)");
-  if (dtype != FDOCT_U8)
-    return fail(h, FDOCT_ERR_UNSUPPORTED, w + "colour input takes 8-bit interleaved B,G,R frames (what cv::VideoCapture::read delivers), no other sample type");
-  if (mediann != 0 && mediann != 3 && mediann != 5 && mediann != 7) return fail(h, FDOCT_ERR_INVALID, w + "mediann must be 0, 3, 5 or 7");
-  if (channelnum == 3 && mediann > 0)
-    return fail(h, FDOCT_ERR_UNSUPPORTED, w + "the channel sum is a frame of doubles and cv::medianBlur rejects CV_64F: no median with channelnum 3");
-  return FDOCT_OK;
+  std::string why;
+  const int rc = colour_refusal(who, channelnum, dtype, mediann, &why);
+  return rc ? fail(h, rc, why) : FDOCT_OK;
 }
 
 // webcam:1015-1038 and the block behind it.  Sum: one kernel, the binning in it.  Select without a median: likewise, into the
@@ -99,432 +83,60 @@ int run_colour(fdoct_ctx* h, const void* d_bgr, int nframes, int raw_w, int raw_
   return FDOCT_OK;
 }
 
-// ---- long-row path (fdoct_big.hip) ----------------------------------------------------------------------------------
-// (the plans of its transforms and the chunks of a batch are values: fdoct_big_plan.h)
-// DFT plan of one length: Stockham radices when it factors into 2, 3, 5, else Bluestein around a power of two >= 2n - 1.
-int big_plan_get(fdoct_ctx* h, int n, fdoct_ctx::BigPlan** out) {
-  auto it = h->big_plans.find(n);
-  if (it != h->big_plans.end()) {
-    *out = &it->second;
-    return FDOCT_OK;
-  }
-  fdoct_ctx::BigPlan p;
-  static const bool per_pass = [] { const char* e = std::getenv("FDOCT_BIG_PER_PASS"); return e && std::atoi(e) != 0; }();  // measurement: round 3's form
-  BigTransform t = make_big_transform(n, per_pass);
-  p.rad = std::move(t.rad);
-  p.groups = std::move(t.groups);
-  p.mb = t.mb;
-  const int tn = t.tn;
-  if (p.mb) {
-    std::vector<float2> chirp, bhat;
-    build_bluestein_tables(n, p.mb, chirp, bhat);
-    int rc;
-    if ((rc = upload(h, p.d_chirp, chirp))) return rc;
-    if ((rc = upload(h, p.d_bhat, bhat))) return rc;
-  }
-  std::vector<float2> tw(tn);
-  for (int j = 0; j < tn; j++) {
-    const double a = 2.0 * kPi * (double)j / (double)tn;
-    tw[j] = make_float2((float)std::cos(a), (float)std::sin(a));
-  }
-  int rc;
-  if ((rc = upload(h, p.d_tw, tw))) return rc;
-  *out = &h->big_plans.emplace(n, std::move(p)).first->second;
-  return FDOCT_OK;
-}
-
-// What stands in front of a transform, fused into the loads of its first launch (or run as a kernel of its own where the
-// transform is not one of grouped launches): the row of floats read as complex (A4's first transform), the W-point spectrum
-// re-packed into the M W-point one (A4), the slope step and lambda -> k gather with the phase (A5 / A6 / A6').
-struct BigLoader {
-  int load = BIG_LOAD_CPLX;
-  const float* yr = nullptr;
-  const float2* yc = nullptr;
-  const float2* spec = nullptr;
-  int ylen = 0, W = 0, bandpass = 0;
-  const int32_t* idx = nullptr;
-  const float* g = nullptr;
-  const float2* phase = nullptr;
-};
-
-// X = IDFT_n (+i exponent, unscaled) of `rows` rows; x holds them (ld == null) or is free and the loader supplies them;
-// `other` is the second buffer (both hold rows * max(n, mb) values).  *result = the buffer that holds the rows * n result;
-// out_limit > 0: only the first out_limit values of each result row are needed (and, with grouped launches, written).
-int big_idft(fdoct_ctx* h, float2* x, float2* other, long long rows, int n, float2** result, hipStream_t st, const BigLoader* ld = nullptr,
-             int out_limit = 0) {
-  fdoct_ctx::BigPlan* p = nullptr;
-  int rc;
-  if ((rc = big_plan_get(h, n, &p))) return rc;
-  auto materialise = [&]() -> int {  // the loader as a kernel of its own, into x
-    if (!ld) return FDOCT_OK;
-    switch (ld->load) {
-      case BIG_LOAD_REAL: HIP_TRY(h, big_launch_real_to_complex(ld->yr, rows * n, x, st)); break;
-      case BIG_LOAD_PAD: HIP_TRY(h, big_launch_pad(ld->spec, rows, ld->W, n, ld->bandpass, x, st)); break;
-      case BIG_LOAD_RESAMPLE: HIP_TRY(h, big_launch_resample(ld->yr, ld->yc, rows, ld->ylen, n, ld->idx, ld->g, ld->phase, x, st)); break;
-      default: break;
-    }
-    return FDOCT_OK;
-  };
-  // the passes of one len-point transform over src -> ... -> *last (ping-pong between the two buffers)
-  auto passes = [&](float2*& src, float2*& dst, int len, const BigLoader* first_ld, int limit) -> int {
-    if (!p->groups.empty()) {
-      for (size_t gi = 0; gi < p->groups.size(); gi++) {
-        const auto& gp = p->groups[gi];
-        BigGroup g{};
-        g.src = src; g.dst = dst; g.rows = rows; g.n = len;
-        g.P = gp.P; g.Q = gp.Q; g.F = gp.F; g.log2ts = gp.log2ts;
-        g.npass = (int)gp.rad.size();
-        for (int i = 0; i < g.npass; i++) g.rad[i] = gp.rad[i];
-        g.out_limit = (gi + 1 == p->groups.size() && limit > 0) ? limit : len;
-        g.tw = p->d_tw;
-        g.load = BIG_LOAD_CPLX;
-        if (gi == 0 && first_ld) {
-          g.load = first_ld->load;
-          g.yr = first_ld->yr; g.yc = first_ld->yc; g.ylen = first_ld->ylen;
-          g.idx = first_ld->idx; g.g = first_ld->g; g.phase = first_ld->phase;
-          g.W = first_ld->W; g.bandpass = first_ld->bandpass;
-          if (first_ld->load == BIG_LOAD_PAD) g.src = first_ld->spec;
-        }
-        HIP_TRY(h, big_launch_fft_group(g, st));
-        std::swap(src, dst);
-      }
-      return FDOCT_OK;
-    }
-    int Ns = 1;
-    for (int R : p->rad) {
-      HIP_TRY(h, big_launch_fft_pass(src, dst, rows, len, R, Ns, p->d_tw, st));
-      std::swap(src, dst);
-      Ns *= R;
-    }
-    return FDOCT_OK;
-  };
-  float2 *src = x, *dst = other;
-  if (!p->mb) {
-    const bool fused = ld && !p->groups.empty();
-    if (!fused && (rc = materialise())) return rc;
-    if ((rc = passes(src, dst, n, fused ? ld : nullptr, out_limit))) return rc;
-    *result = src;
-    return FDOCT_OK;
-  }
-  // Bluestein: u = conj(x c) zero-padded; conj(IDFT u) = DFT(x c); times bhat; IDFT; times c
-  if ((rc = materialise())) return rc;
-  HIP_TRY(h, big_launch_chirp_in(x, rows, n, p->mb, p->d_chirp, other, st));
-  src = other;
-  dst = x;
-  if ((rc = passes(src, dst, p->mb, nullptr, 0))) return rc;
-  HIP_TRY(h, big_launch_conj_mul(src, rows, p->mb, p->d_bhat, st));
-  if ((rc = passes(src, dst, p->mb, nullptr, 0))) return rc;
-  HIP_TRY(h, big_launch_chirp_out(src, rows, n, p->mb, p->d_chirp, dst, st));
-  *result = dst;
-  return FDOCT_OK;
-}
-
-// The whole chain for device-resident frames on the long-row path, chunk by chunk of whole averaging groups.
-int run_big(fdoct_ctx* h, const void* kframes, const float* kframes_lo, int kdt, size_t kpitch, int nframes, bool need_minmax, float* k_mag, float* k_db,
-            hipStream_t st) {
-  const int W = h->W, H = h->H, N = h->N, D = h->D, M = h->M, A = h->A;
-  // the padded spectrum / upsampled row: W + 2 floor((M W - W) / 2) points (main:229) -- M W, or M W - 1 for an odd width under an
-  // even multiplier
-  const int MW = W + 2 * ((W * M - W) / 2);
-  int rc;
-  size_t lmax = (size_t)std::max(N, M > 1 ? MW : 0);
-  for (int n : {N, M > 1 ? W : 0, M > 1 ? MW : 0}) {
-    if (!n) continue;
-    fdoct_ctx::BigPlan* p = nullptr;
-    if ((rc = big_plan_get(h, n, &p))) return rc;
-    lmax = std::max(lmax, (size_t)std::max(n, p->mb));
-  }
-  const int G = nframes / A;
-  long long chunk_mb = 0;
-  if (const char* e = std::getenv("FDOCT_BIG_CHUNK_MB")) chunk_mb = std::atoll(e);  // read per call, like FDOCT_HOST_CHUNK_MB: the tests cut small batches with it
-  const BigChunks ch = make_big_chunks(W, H, A, G, lmax, big_chunk_budget(chunk_mb));
-  const long long cg = ch.cg;
-  const size_t crow = ch.rows;
-  if ((rc = h->ws_big_y.reserve(h, crow * W * 4))) return rc;
-  if ((rc = h->ws_big_a.reserve(h, crow * lmax * sizeof(float2)))) return rc;
-  if ((rc = h->ws_big_b.reserve(h, crow * lmax * sizeof(float2)))) return rc;
-  for (long long g0 = 0; g0 < G; g0 += cg) {
-    const long long ng = std::min<long long>(cg, G - g0);
-    BigArgs a{};
-    a.frames = static_cast<const unsigned char*>(kframes) + (size_t)g0 * A * H * kpitch;
-    a.frames_lo = kframes_lo ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(kframes_lo) + (size_t)g0 * A * H * kpitch) : nullptr;
-    a.pitch_bytes = (long long)kpitch;
-    a.in_rows = ng * A * H;
-    a.out_rows = ng * H;
-    a.dtype = kdt;
-    a.W = W; a.H = H; a.N = N; a.D = D; a.M = M; a.A = A;
-    a.ib = h->yb.rows == 1 ? h->d_ib : h->d_ib2d;
-    a.il = h->yb.rows == 1 ? h->d_il : h->d_il2d;
-    a.ib_2d = h->yb.rows > 1;
-    a.yp = h->d_yp; a.yp_2d = h->yp.rows > 1;
-    a.yd = h->d_yd; a.yd_2d = h->yd.rows > 1;
-    a.win = h->d_win_g;
-    a.minmax = need_minmax ? h->d_minmax + (size_t)g0 * A : nullptr;
-    a.rowwisenormalize = h->cfg.rowwisenormalize;
-    a.dcmask = h->cfg.dc_mask;
-    a.inv_A = (float)(1.0 / (double)A);
-    a.eps = kernel_eps(h);
-    a.db_scale = (float)(20.0 / 2.303 * 0.6931471805599453);
-    HIP_TRY(h, big_launch_pre(a, h->ws_big_y, st));
-    // Buffer discipline of big_idft with a loader: the first launch reads the loader's source and writes `other`, the next one
-    // writes `x`, and so on; so the source may live in x (it is dead once the first launch is through) but never in `other`.
-    // A transform that cannot fuse its loader (one launch per pass, Bluestein) materialises the rows into x first: there the
-    // source must not live in x.
-    float2 *bufa = h->ws_big_a, *bufb = h->ws_big_b, *res = nullptr;
-    auto fuses = [&](int n, bool* yes) -> int {
-      fdoct_ctx::BigPlan* p = nullptr;
-      if (int rc2 = big_plan_get(h, n, &p)) return rc2;
-      *yes = !p->mb && !p->groups.empty();
-      return FDOCT_OK;
-    };
-    BigLoader rs;                 // A5 / A6 / A6': what the final transform reads
-    rs.load = BIG_LOAD_RESAMPLE;
-    rs.yr = h->ws_big_y;
-    rs.ylen = W;
-    rs.idx = h->d_idx_g;
-    rs.g = h->d_g_g;
-    rs.phase = h->d_phase;
-    float2* held = nullptr;       // the buffer the final transform's source rows live in (null: the float rows)
-    if (M > 1) {  // A4
-      BigLoader l1;
-      l1.load = BIG_LOAD_REAL;
-      l1.yr = h->ws_big_y;
-      if ((rc = big_idft(h, bufa, bufb, a.in_rows, W, &res, st, &l1))) return rc;
-      BigLoader l2;
-      l2.load = BIG_LOAD_PAD;
-      l2.spec = res;
-      l2.W = W;
-      l2.bandpass = h->bandpass ? 1 : 0;
-      float2* spare = (res == bufa) ? bufb : bufa;
-      bool f = false;
-      if ((rc = fuses(MW, &f))) return rc;
-      if ((rc = f ? big_idft(h, res, spare, a.in_rows, MW, &res, st, &l2) : big_idft(h, spare, res, a.in_rows, MW, &res, st, &l2))) return rc;
-      rs.yr = nullptr;
-      rs.yc = res;
-      rs.ylen = MW;
-      held = res;
-    }
-    {  // A5 / A6 / A7; only the first numdisplaypoints bins of the result are needed
-      float2* spare = held ? (held == bufa ? bufb : bufa) : bufb;
-      float2* mine = held ? held : bufa;
-      bool f = false;
-      if ((rc = fuses(N, &f))) return rc;
-      if ((rc = f ? big_idft(h, mine, spare, a.in_rows, N, &res, st, &rs, D) : big_idft(h, held ? spare : mine, held ? mine : spare, a.in_rows, N, &res, st, &rs, D)))
-        return rc;
-    }
-    HIP_TRY(h, big_launch_post(res, a, k_mag ? k_mag + (size_t)g0 * H * D : nullptr, k_db ? k_db + (size_t)g0 * H * D : nullptr, st));
-  }
-  return FDOCT_OK;
-}
-
-// What make_fused_launch reads of the handle and of a call of `nframes` frames whose kernel reads samples of type kdt.
-static FusedLaunchInputs fused_launch_inputs(const fdoct_ctx* h, int kdt, int nframes, bool need_minmax, bool frames_lo, bool want_tro) {
+// What make_route reads: the handle's part, and a row-major call of `nframes` frames without outputs (fdoct_prepare: an aligned,
+// packed set-up); the entry points add their outputs, layout and whether the call is the complex one.
+RouteInputs route_inputs(const fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, int nframes) {
   static const unsigned ring_cap = [] { const char* e = std::getenv("FDOCT_TRO_RING"); return e ? (unsigned)std::atoi(e) : 0u; }();  // measurement: at most this many slots
-  FusedLaunchInputs in;
-  in.W = h->W; in.H = h->H; in.D = h->D; in.A = h->A;
-  in.kdt = kdt;
+  RouteInputs in;
+  in.W = h->W; in.H = h->H; in.N = h->N; in.D = h->D; in.M = h->M; in.A = h->A;
+  in.plan = &h->plan;
   in.bg_rows = h->yb.rows; in.pi = h->yp.rows > 0; in.dark = h->yd.rows > 0;
-  in.rowwisenormalize = h->cfg.rowwisenormalize != 0; in.minmax = need_minmax; in.frames_lo = frames_lo;
-  in.precise_div = h->precise_div; in.staged = h->staged; in.force_general = h->force_general;
-  in.block_override = h->block_override; in.grid_override = h->grid_override; in.num_cu = h->num_cu;
-  in.groups = nframes / h->A; in.in_rows = (long long)nframes * h->H; in.out_rows = in.groups * h->H;
-  in.want_tro = want_tro; in.ring_cap = ring_cap;
+  in.bandpass = h->bandpass; in.rowwisenormalize = h->cfg.rowwisenormalize != 0;
+  in.normalize = (h->cfg.variant == FDOCT_VARIANT_SIM) || !h->cfg.donotnormalize;
+  in.phase = !h->phase.empty(); in.movavgn = h->cfg.movavgn;
+  in.fe_median = h->fe_median; in.fe_binx = h->fe_binx; in.fe_biny = h->fe_biny; in.colour = h->colour;
+  in.jit = h->jit; in.staged = h->staged;
+  in.plan_override = h->plan_override; in.block_override = h->block_override; in.grid_override = h->grid_override; in.num_cu = h->num_cu;
+  in.precise_div = h->precise_div; in.force_general = h->force_general; in.tro_enabled = h->tro_enabled; in.ring_cap = ring_cap;
+  in.dtype = dtype; in.frames_addr = frames_addr; in.pitch_bytes = pitch_bytes; in.nframes = nframes;
   return in;
 }
 
-// May the chain write the reference's D x H layout itself, as far as the CALL says (whether the configuration has such a kernel and
-// its launch fits is make_fused_launch's part)?  8/16-bit frames that go to the kernel as they are, 16-byte aligned outputs, and
-// offsets the write-out can address.
-static bool transposed_store_callable(const fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
-                                      uintptr_t out_db_addr, int nframes) {
-  if (!h->tro_enabled || !h->plan.fused || !h->yb.rows) return false;
-  if (dtype != FDOCT_U8 && dtype != FDOCT_U16) return false;
-  if (h->fe_median > 0 || h->fe_binx > 1 || h->fe_biny > 1 || h->cfg.movavgn > 0) return false;
-  const size_t valign = dtype == FDOCT_U8 ? 8 : 16;
-  if ((frames_addr % valign) || (pitch_bytes % valign)) return false;
-  if ((out_bscan_addr % 16) || (out_db_addr % 16)) return false;
-  if ((long long)(nframes / h->A) * h->H >= 0x7fffffffLL) return false;
-  // the write-out addresses one B-scan with 32-bit byte offsets inside a buffer descriptor of 0x7ffffff0 bytes
-  return (size_t)h->D * (size_t)h->H * 4 < 0x7ffffff0u;
-}
+// make_route's question to the run-time compiler, and what the compiler's last answer left: the kernel and the reason.
+struct JitAsk {
+  const fdoct_ctx* h;
+  bool asked = false;
+  hipFunction_t fn = nullptr;
+  std::string why;
+  static bool can_compile(void* p, int kdt, int wave_opt) {
+    JitAsk& a = *static_cast<JitAsk*>(p);
+    a.asked = true;
+    a.fn = nullptr;
+    return wave_jit_get(a.h->W, a.h->M, a.h->N, kdt, a.h->D, wave_opt, a.h->device, &a.fn, &a.why) == hipSuccess;
+  }
+};
 
-// Decides the route of a call.  frames_addr / pitch_bytes / out addresses: as the caller gave them (fdoct_prepare: an aligned,
-// packed set-up).  May rebuild device tables and compile (hipRTC) -- never launches.
-// cx: the route of the complex A-scan (enqueue_complex): the same checks and passes in front of the chain, the family restricted to the
-// two whose kernels write it -- the wave-per-row kernel compiled at run time with FDOCT_WAVE_OPT_CXOUT for every shape it takes, the
-// workgroup-per-row kernel for the rest -- whatever the handle's plan; rows only the long-row path takes are refused.  Reads the handle's
-// adopted plan and changes none of it.
-static int choose_route_of(fdoct_ctx* h, bool cx, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
-                           uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r) {
-  int rc;
-  if (cx && h->plan.gen.use_big)
-    return fail(h, FDOCT_ERR_UNSUPPORTED, "the complex A-scan is not written by the long-row path (rows that do not fit a compute unit's LDS)");
-  if ((rc = (h->plan.fused && !cx) ? ensure_fused_tables(h) : ensure_generic_tables(h))) return rc;
-  if (h->D > h->N) return fail(h, FDOCT_ERR_INVALID, "numdisplaypoints > numfftpoints");
-  const int W = h->W, H = h->H, D = h->D, A = h->A;
-  const long long out_rows = (long long)(nframes / A) * H;
-  *r = Route{};
-  // A colour handle: the colour stage runs first and takes the median / binning with it; from here on the call is routed as
-  // what that stage leaves -- the front end's bytes in a library workspace (channelnum 0-2), or packed doubles (3).
-  const bool colour = h->colour >= 0;
-  if (colour) {
-    if ((rc = colour_check(h, "colour input", h->colour, dtype, h->fe_median))) return rc;
-    if (pitch_bytes < 3 * (size_t)W * h->fe_binx) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a row of B,G,R pixels");
-    r->colour = true;
-    frames_addr = 0;
-    if (h->colour == 3) {
-      dtype = FDOCT_F64;
-      pitch_bytes = frontend_pitch(W, 8);
-    } else {
-      pitch_bytes = frontend_pitch(W * h->fe_binx, 1);  // (the unbinned channel: what a kernel that bins in its own loads would read)
-    }
-  }
-  const size_t es = dtype_size(dtype);
-  h->jit_note.clear();   // (the note describes THIS call's route: a refused run-time compile, or the long-row path)
-  int kdt = kernel_dtype(dtype);
-  const bool normalize = (h->cfg.variant == FDOCT_VARIANT_SIM) || !h->cfg.donotnormalize;
-  // with row-wise normalisation on, every non-degenerate row already spans [0,1] and the whole-frame pass (main:1128) is the identity
-  r->need_minmax = normalize && !h->cfg.rowwisenormalize;
-  // pi / dark frames, the band-pass and the normalisations are compile-time options of the wave-per-row kernel: the library's own
-  // instantiations are the plain set-up, a handle that uses one of them gets its kernel from the run-time compiler
-  // ... and so are the dispersion phase (complex rows, a full-length final transform) and a display beyond numfftpoints / 2
-  const int wave_opt = (h->yp.rows ? FDOCT_WAVE_OPT_PI : 0) | (h->yd.rows ? FDOCT_WAVE_OPT_DARK : 0) |
-                       (h->bandpass && h->M > 1 ? FDOCT_WAVE_OPT_BANDPASS : 0) | (h->cfg.rowwisenormalize ? FDOCT_WAVE_OPT_ROWNORM : 0) |
-                       (r->need_minmax ? FDOCT_WAVE_OPT_FRAMENORM : 0) | (!h->phase.empty() ? FDOCT_WAVE_OPT_CPLX : 0) |
-                       (h->phase.empty() && D > h->N / 2 ? FDOCT_WAVE_OPT_DEEP : 0) | (cx ? FDOCT_WAVE_OPT_CXOUT : 0);
-  // The wave-per-row kernel's launch, where its tables leave room for at least one wave's buffers: as many waves as LDS and
-  // the shape's register budget allow, at most one workgroup per CU.
-  auto wave_fits = [&](int opt) {
-    const size_t shared = wave_shared_lds_bytes(h->wave_tw_count, W, h->M, h->N, h->yb.rows > 1, opt);
-    const size_t priv = wave_private_lds_bytes(W, h->M, h->N, opt);
-    if (shared + priv > 160 * 1024 - 64) return false;
-    int waves = (int)((160 * 1024 - 64 - shared) / priv);
-    if (waves > wave_max_waves(W, h->M, h->N, opt)) waves = wave_max_waves(W, h->M, h->N, opt);
-    if (h->block_override && h->block_override / 64 >= 1 && h->block_override / 64 <= waves) waves = h->block_override / 64;
-    r->waves = waves;
-    r->lds = shared + (size_t)waves * priv;
-    r->grid = std::min<long long>(h->grid_override > 0 ? h->grid_override : h->num_cu, (out_rows + waves - 1) / waves);   // (a wave takes one row at a time)
-    return true;
-  };
-  // 2 x 2 binning with nothing else in front of the chain, on a configuration the wave-per-row kernel takes: the kernel compiled
-  // for the handle does the binning in its own loads (FDOCT_WAVE_OPT_BIN2) and the pass over the raw frames is skipped.
-  // (Measured on the shipped shapes, tools/bench_generic.py with and without FDOCT_JIT=0: + 4.5 % on 160-sample 8-bit rows, + 5 % on
-  // 640-sample 16-bit rows, - 1 % on 640-sample 8-bit rows -- twenty 2-byte loads per lane cost what the pass saves: those keep the pass.)
-  if (!cx && h->fe_median == 0 && h->fe_binx == 2 && h->fe_biny == 2 && (dtype == FDOCT_U16 || (dtype == FDOCT_U8 && W <= 320)) && h->cfg.movavgn == 0 &&
-      h->jit && !h->plan.fused && !h->plan.gen.use_big && h->plan_override > -2 && h->phase.empty() && D <= h->N / 2 && !r->need_minmax &&
-      (frames_addr % 4 == 0) && (pitch_bytes % 4 == 0) && pitch_bytes >= es * 2 * (size_t)W && out_rows < 0x7fffffffLL &&
-      wave_jit_shape_ok(W, h->M, h->N, D)) {
-    if ((rc = ensure_wave_tables(h))) return rc;
-    std::string why;
-    hipFunction_t fn = nullptr;
-    if (!wave_fits(wave_opt | FDOCT_WAVE_OPT_BIN2)) {
-      // no room for even one wave: the ordinary path (binning pass, then whichever kernel fits)
-    } else if (wave_jit_get(W, h->M, h->N, kdt, D, wave_opt | FDOCT_WAVE_OPT_BIN2, h->device, &fn, &why) == hipSuccess) {
-      r->bin2_in_kernel = true;
-      r->jit_fn = fn;
-      r->wave_opt = wave_opt | FDOCT_WAVE_OPT_BIN2;
-    }
-    h->jit_note = why;
-  }
-  // ---- passes in front of the chain, and what they leave for its kernel to read
-  uintptr_t kaddr = frames_addr;
-  size_t kpitch = pitch_bytes;
-  if (colour) {
-    if (h->colour != 3 && !r->bin2_in_kernel) kpitch = frontend_pitch(W, 1);
-  } else if (!r->bin2_in_kernel && (h->fe_median > 0 || h->fe_binx > 1 || h->fe_biny > 1)) {
-    if (dtype != FDOCT_U8 && dtype != FDOCT_U16)
-      return fail(h, FDOCT_ERR_UNSUPPORTED, "the front end (median / binning) takes the camera's 8- or 16-bit frames");
-    if (pitch_bytes < es * (size_t)W * h->fe_binx) return fail(h, FDOCT_ERR_INVALID, "pitch smaller than a raw camera row");
-    r->frontend = true;
-    kaddr = 0;                                                  // a library workspace: aligned
-    kpitch = frontend_pitch(W, es);
-  }
-  if (dtype == FDOCT_F64) {
-    if (pitch_bytes % 8) return fail(h, FDOCT_ERR_INVALID, "f64 pitch must be a multiple of 8");
-    r->pre = PrePass::F64Split;
-    kaddr = 0;
-    kpitch = (size_t)W * 4;
-    kdt = FDOCT_K_F32;
-  }
-  if (h->cfg.movavgn > 0) {
-    // (float frames: the tap sums of non-integer samples go on as two planes, like the doubles' -- round 6: a float sum rounds at
-    // the size of the DC level, 0.87 x the tolerance from the chain in double under fringes of 1e-3 of it in the sweeps)
-    const bool wide = dtype == FDOCT_F32 && !r->frontend && (pitch_bytes % 4 == 0) && (frames_addr % 4 == 0);
-    r->pre = dtype == FDOCT_F64 ? PrePass::MovAvgF64 : wide ? PrePass::MovAvgF32Wide : PrePass::MovAvg;
-    kaddr = 0;
-    kpitch = (size_t)W * 4;
-    kdt = FDOCT_K_F32;
-  }
-  r->kdt = kdt;
-  r->kpitch = kpitch;
-  // the specialised kernels read 16-byte vectors; anything else goes through the generic kernel
-  const size_t valign = (kdt == FDOCT_K_U8) ? 8 : 16;
-  const bool misaligned = (kaddr % valign) || (kpitch % valign);
-  const bool run_generic = cx || !h->plan.fused || misaligned;
-  if (run_generic && (rc = ensure_generic_tables(h))) return rc;
-  if (run_generic && h->staged) return fail(h, FDOCT_ERR_UNSUPPORTED, "staged mode needs a specialised kernel for this configuration");
-
-  const bool transposed = layout == FDOCT_LAYOUT_TRANSPOSED_DxH;
-  if (!run_generic) {  // the fused family: its whole launch, or why it cannot run
-    const bool want_tro = transposed && !r->frontend && r->pre == PrePass::None &&
-                          transposed_store_callable(h, dtype, frames_addr, pitch_bytes, out_bscan_addr, out_db_addr, nframes);
-    std::string why;
-    if ((rc = make_fused_launch(h->plan, fused_launch_inputs(h, kdt, nframes, r->need_minmax, r->frames_lo(), want_tro), &r->fused, &why))) return fail(h, rc, why);
-  }
-  r->transpose_pass = !cx && transposed && !r->fused.tro;   // (the complex call's D x H layout is made by its own entry point)
-
-  // the acquisition configurations the reference ships: one wave per A-scan (fdoct_wave.hip) instead of one workgroup
-  // (frames handed over as doubles carry a low word per sample: the fused any-option, workgroup-per-row and long-row kernels take it)
-  const bool wave_scope = run_generic && !h->plan.gen.use_big && h->plan_override > -2 && kdt >= 0 && !r->frames_lo() &&
-                          (kaddr % 4 == 0) && (kpitch % 4 == 0) && out_rows < 0x7fffffffLL;
-  if (r->bin2_in_kernel && !wave_scope) return fail(h, FDOCT_ERR_DEVICE, "internal: binning left to a kernel that does not run");
-  bool run_wave = r->bin2_in_kernel;
-  bool wave_builtin = false;
-  if (wave_scope && !run_wave) {
-    wave_builtin = wave_opt == 0 && wave_kernel_available(W, h->M, h->N, kdt, D);   // (never the complex call's: its option bit is set)
-    // any other shape the template can take: compiled for this handle's geometry at run time (fdoct_set_jit); the first call
-    // (or fdoct_prepare) pays the compile, a refusal falls back to the workgroup-per-row kernel
-    if (!wave_builtin && h->jit && wave_jit_shape_ok(W, h->M, h->N, D, wave_opt)) {
-      std::string why;
-      hipFunction_t fn = nullptr;
-      if (wave_jit_get(W, h->M, h->N, kdt, D, wave_opt, h->device, &fn, &why) == hipSuccess) {
-        r->jit_fn = fn;
-        r->wave_opt = wave_opt;
-      }
-      h->jit_note = why;
-    }
-    run_wave = wave_builtin || r->jit_fn;
-  }
-  if (run_wave && !r->bin2_in_kernel) {  // (the kernel that bins is known to fit)
-    if ((rc = ensure_wave_tables(h))) return rc;
-    if (!wave_fits(r->wave_opt)) {  // not even one wave's buffer next to the tables
-      run_wave = false;
-      r->jit_fn = nullptr;
-    }
-  }
-  if (run_wave)
-    r->family = r->jit_fn ? FDOCT_KERNEL_WAVE_JIT : FDOCT_KERNEL_WAVE;
-  else if (run_generic) {
-    r->family = h->plan.gen.use_big ? FDOCT_KERNEL_LONG_ROWS : FDOCT_KERNEL_GENERIC;
-    if (!h->plan.gen.use_big) {
-      r->lds = generic_lds_bytes(plan_inputs(h), h->plan.gen);
-      // generic_kernel is compiled for 6 waves per SIMD = 6 workgroups of 4 waves per CU
-      const int per_cu = std::clamp((int)((160 * 1024 - 1024) / r->lds), 1, 6);
-      r->grid = std::min<long long>((long long)h->num_cu * per_cu, out_rows);
-    }
-    // the cliff an integrator should see: rows in HBM run an order of magnitude below their LDS-resident neighbours
-    if (h->plan.gen.use_big)
-      h->jit_note = "this geometry runs on the long-row path (rows in HBM, fdoct_big.hip: one launch per group of DFT passes): its transforms do not fit "
-                    "the 160 KB of LDS of a compute unit; expect 1e6 ... 1e7 A-scans/s where LDS-resident rows reach 1e8";
-  }
+// Decides the route of a call (make_route) and carries out what the decision asks of the handle: the device tables it names, and
+// fdoct_jit_note -- the reason of the route's last compile attempt (empty after a successful one), or the decision's own note.  May
+// compile (hipRTC) and rebuild device tables -- never launches.  Reads the handle's adopted plan and changes none of it.
+int choose_route(fdoct_ctx* h, const RouteInputs& in, Route* r) {
+  JitAsk jit{h};
+  RouteDecision d;
+  std::string why;
+  if (int rc = route_precheck(in, &why)) return fail(h, rc, why);   // (no route: the note stays the last route's)
+  int rc = make_route(in, JitAsk::can_compile, &jit, &d, &why);
+  if (rc) fail(h, rc, why);
+  if (!rc && (d.tables & TABLES_FUSED)) rc = ensure_fused_tables(h);
+  if (!rc && (d.tables & (TABLES_GENERIC | TABLES_WAVE))) rc = (d.tables & TABLES_WAVE) ? ensure_wave_tables(h) : ensure_generic_tables(h);
+  if (d.note)
+    h->jit_note = d.note;
+  else if (jit.asked)
+    h->jit_note = jit.why;
   else
-    r->family = h->staged ? FDOCT_KERNEL_FUSED_STAGED : (r->fused.tro ? FDOCT_KERNEL_FUSED_TRANSPOSED : FDOCT_KERNEL_FUSED);
+    h->jit_note.clear();
+  if (rc) return rc;
+  *r = Route{d, d.family == FDOCT_KERNEL_WAVE_JIT ? jit.fn : nullptr};
   return FDOCT_OK;
-}
-
-int choose_route(fdoct_ctx* h, fdoct_dtype dtype, uintptr_t frames_addr, size_t pitch_bytes, uintptr_t out_bscan_addr,
-                 uintptr_t out_db_addr, fdoct_layout layout, int nframes, Route* r) {
-  return choose_route_of(h, false, dtype, frames_addr, pitch_bytes, out_bscan_addr, out_db_addr, layout, nframes, r);
 }
 
 // After the chain's kernel(s) of any family: end-of-kernel event, the transpose pass where the chain did not write D x H itself,
@@ -567,9 +179,9 @@ int launch_family_wave(fdoct_ctx* h, const Route& r, const Call& c) {
   wa.g = h->d_g_g;
   wa.gidx = h->d_wave_gidx;
   wa.tw = h->d_wave_tw;
-  wa.tw_count = h->wave_tw_count;
-  wa.off_nc = h->wave_off[0]; wa.off_lh = h->wave_off[1]; wa.off_wh = h->wave_off[2];
-  wa.off_tww = h->wave_off[3]; wa.off_twmw = h->wave_off[4]; wa.off_twn = h->wave_off[5];
+  wa.tw_count = h->plan.wave_tw.count;
+  wa.off_nc = h->plan.wave_tw.off[0]; wa.off_lh = h->plan.wave_tw.off[1]; wa.off_wh = h->plan.wave_tw.off[2];
+  wa.off_tww = h->plan.wave_tw.off[3]; wa.off_twmw = h->plan.wave_tw.off[4]; wa.off_twn = h->plan.wave_tw.off[5];
   wa.dcmask = h->cfg.dc_mask;
   wa.inv_A = (float)(1.0 / (double)A);
   wa.eps = kernel_eps(h);
@@ -939,6 +551,28 @@ int check_call(fdoct_ctx* h, fdoct_dtype dtype, size_t pitch_bytes, const float*
   return FDOCT_OK;
 }
 
+// What both entry points enqueue between the route and the chain's kernel: the call's quantities, the first event, the passes in
+// front of the chain and the whole-frame min / max pass.  Where the chain writes is the entry point's to add.
+static int begin_call(fdoct_ctx* h, const Route& r, const void* d_frames, fdoct_dtype dtype, int nframes, size_t es, size_t pitch_bytes, Call* c) {
+  c->st = h->stream;
+  c->nframes = nframes;
+  c->G = nframes / h->A;
+  c->in_rows = (long long)nframes * h->H;
+  c->out_rows = (long long)c->G * h->H;
+  c->es = es;
+  c->kframes = d_frames;
+  if (h->record_now && h->rec_first) HIP_TRY(h, hipEventRecord(h->ev[0], c->st));
+  if (int rc = run_passes_in_front(h, r, *c, d_frames, dtype, pitch_bytes)) return rc;
+  if (r.need_minmax) {
+    // [nframes] results followed by the fast kernel's per-workgroup partials
+    const size_t mm_elems = (size_t)nframes + (size_t)minmax_partial_count(nframes);
+    if (int rc = h->d_minmax.reserve(h, mm_elems * sizeof(float2))) return rc;
+    HIP_TRY(h, launch_minmax(c->kframes, r.kdt, (long long)r.kpitch, h->W, h->H, nframes, h->d_yd, h->yd.rows > 1, h->d_minmax,
+                             h->d_minmax + nframes, c->st));
+  }
+  return FDOCT_OK;
+}
+
 // Enqueue the whole path for device-resident frames.  d_out_* are row-major or
 // transposed per `layout`.
 int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, size_t pitch_bytes,
@@ -952,36 +586,23 @@ int enqueue_one(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nfram
   DEVICE_SCOPE(h);
   int rc;
   Route r;
-  if ((rc = choose_route(h, dtype, (uintptr_t)d_frames, pitch_bytes, (uintptr_t)d_out_bscan, (uintptr_t)d_out_db, layout, nframes, &r))) return rc;
-  const int W = h->W, H = h->H, D = h->D, A = h->A;
+  RouteInputs in = route_inputs(h, dtype, (uintptr_t)d_frames, pitch_bytes, nframes);
+  in.out_bscan_addr = (uintptr_t)d_out_bscan;
+  in.out_db_addr = (uintptr_t)d_out_db;
+  in.layout = layout;
+  if ((rc = choose_route(h, in, &r))) return rc;
   Call c;
-  c.st = h->stream;
-  c.nframes = nframes;
-  c.G = nframes / A;
-  c.in_rows = (long long)nframes * H;
-  c.out_rows = (long long)c.G * H;
-  c.es = es;
   c.d_out_bscan = d_out_bscan;
   c.d_out_db = d_out_db;
-  c.kframes = d_frames;
-  hipStream_t st = c.st;
-  if (h->record_now && h->rec_first) HIP_TRY(h, hipEventRecord(h->ev[0], st));
-  if ((rc = run_passes_in_front(h, r, c, d_frames, dtype, pitch_bytes))) return rc;
-  if (r.need_minmax) {
-    // [nframes] results followed by the fast kernel's per-workgroup partials
-    const size_t mm_elems = (size_t)nframes + (size_t)minmax_partial_count(nframes);
-    if ((rc = h->d_minmax.reserve(h, mm_elems * sizeof(float2)))) return rc;
-    HIP_TRY(h, launch_minmax(c.kframes, r.kdt, (long long)r.kpitch, W, H, nframes, h->d_yd, h->yd.rows > 1, h->d_minmax,
-                             h->d_minmax + nframes, st));
-  }
+  if ((rc = begin_call(h, r, d_frames, dtype, nframes, es, pitch_bytes, &c))) return rc;
   // ---- where the chain writes: the caller's arrays, or the transpose pass's input
   c.k_mag = d_out_bscan;
   c.k_db = d_out_db;
   if (r.transpose_pass) {
-    const size_t bytes = (size_t)c.out_rows * D * 4;
+    const size_t bytes = (size_t)c.out_rows * h->D * 4;
     if ((rc = h->ws_tr.reserve(h, bytes * 2))) return rc;
     if (d_out_bscan) c.k_mag = h->ws_tr;
-    if (d_out_db) c.k_db = h->ws_tr + (size_t)c.out_rows * D;
+    if (d_out_db) c.k_db = h->ws_tr + (size_t)c.out_rows * h->D;
   }
   switch (r.family) {
     case FDOCT_KERNEL_WAVE:
@@ -1009,26 +630,16 @@ int enqueue_complex(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int n
   DEVICE_SCOPE(h);
   int rc;
   Route r;
-  if ((rc = choose_route_of(h, true, dtype, (uintptr_t)d_frames, pitch_bytes, 0, 0, FDOCT_LAYOUT_ROWMAJOR_HxD, nframes, &r))) return rc;
+  RouteInputs in = route_inputs(h, dtype, (uintptr_t)d_frames, pitch_bytes, nframes);
+  in.cx = true;
+  if ((rc = choose_route(h, in, &r))) return rc;
   if (r.family != FDOCT_KERNEL_WAVE_JIT && r.family != FDOCT_KERNEL_GENERIC) return fail(h, FDOCT_ERR_DEVICE, "internal: the complex A-scan routed to a kernel that does not write it");
   if (!d_out) return FDOCT_OK;
-  Call c;
-  c.st = h->stream;
-  c.nframes = nframes;
-  c.G = nframes;
-  c.in_rows = c.out_rows = (long long)nframes * h->H;
-  c.es = es;
-  c.kframes = d_frames;
-  c.k_cx = d_out;
   h->rec_first = h->rec_last = true;
   h->record_now = h->async_timing;  // (event records cost stream time: as fdoct_process_async, only where fdoct_set_timing asked)
-  if (h->record_now) HIP_TRY(h, hipEventRecord(h->ev[0], c.st));
-  if ((rc = run_passes_in_front(h, r, c, d_frames, dtype, pitch_bytes))) return rc;
-  if (r.need_minmax) {
-    const size_t mm_elems = (size_t)nframes + (size_t)minmax_partial_count(nframes);
-    if ((rc = h->d_minmax.reserve(h, mm_elems * sizeof(float2)))) return rc;
-    HIP_TRY(h, launch_minmax(c.kframes, r.kdt, (long long)r.kpitch, h->W, h->H, nframes, h->d_yd, h->yd.rows > 1, h->d_minmax, h->d_minmax + nframes, c.st));
-  }
+  Call c;
+  c.k_cx = d_out;
+  if ((rc = begin_call(h, r, d_frames, dtype, nframes, es, pitch_bytes, &c))) return rc;
   return r.family == FDOCT_KERNEL_GENERIC ? launch_family_generic(h, r, c) : launch_family_wave(h, r, c);
 }
 
@@ -1057,7 +668,11 @@ int enqueue(fdoct_ctx* h, const void* d_frames, fdoct_dtype dtype, int nframes, 
   {  // the whole call's route: where the chain writes D x H itself there is no intermediate at all, and nothing to cut
     DEVICE_SCOPE(h);
     Route whole;
-    if (h->yb.rows && choose_route(h, dtype, (uintptr_t)d_frames, pitch, (uintptr_t)d_out_bscan, (uintptr_t)d_out_db, layout, nframes, &whole) == FDOCT_OK && whole.fused.tro)
+    RouteInputs in = route_inputs(h, dtype, (uintptr_t)d_frames, pitch, nframes);
+    in.out_bscan_addr = (uintptr_t)d_out_bscan;
+    in.out_db_addr = (uintptr_t)d_out_db;
+    in.layout = layout;
+    if (h->yb.rows && choose_route(h, in, &whole) == FDOCT_OK && whole.fused.tro)
       return enqueue_one(h, d_frames, dtype, nframes, pitch_bytes, d_out_bscan, d_out_db, layout);
   }
   const size_t frame_stride = pitch * (size_t)h->H * h->fe_biny;  // raw camera rows when a front end is set

@@ -6,16 +6,6 @@
 
 namespace fdoct_impl {
 
-size_t dtype_size(int dt) {
-  switch (dt) {
-    case FDOCT_U8: return 1;
-    case FDOCT_U16: return 2;
-    case FDOCT_F32: return 4;
-    case FDOCT_F64: return 8;
-    default: return 0;
-  }
-}
-
 int copy_ref_frame(fdoct_ctx* h, RefFrame& dst, const void* data, fdoct_dtype dtype, int rows, size_t pitch) {
   if (!data) {
     dst.v.clear();
@@ -437,7 +427,7 @@ int ensure_generic_tables(fdoct_ctx* h) {
   return FDOCT_OK;
 }
 
-// Tables of the wave-per-row kernels: packed gather sources and the twiddle blob
+// Tables of the wave-per-row kernels: packed gather sources and the twiddle blob, laid out by wave_tw_layout (fdoct_wave_rules.h)
 // [N/2 passes][M W/2 passes][W/2 passes][e^(2 pi i k/W), k < W/2][e^(2 pi i k/(M W)), k < W/2][e^(2 pi i k/N), k < D];
 // with the generic path's, whose device copies of the window and the resample table they read.
 int ensure_wave_tables(fdoct_ctx* h) {
@@ -446,38 +436,31 @@ int ensure_wave_tables(fdoct_ctx* h) {
   if (h->tables_ok & TABLES_WAVE) return FDOCT_OK;
   // complex rows (dispersion phase): the final transform runs over the whole row, one gather source per point
   const bool cplx = !h->phase.empty();
-  const int W = h->W, M = h->M, N = h->N, MW = W * M, NC = cplx ? N : N / 2, D = h->D;
+  const int W = h->W, M = h->M, N = h->N, MW = W * M, NC = cplx ? N : N / 2;
   std::vector<uint32_t> gi(NC);
   auto src = [&](int q) -> uint32_t { return (q <= 0 || q >= N - 1) ? (uint32_t)MW : (uint32_t)h->idx[q]; };  // main:1164
   for (int n = 0; n < NC; n++) gi[n] = cplx ? src(n) : (src(2 * n) | (src(2 * n + 1) << 16));
-  std::vector<float2> tw;
+  const WaveTwLayout& lay = h->plan.wave_tw;
+  std::vector<float2> tw(lay.count);
   auto unit = [&](double num, double den) {
     const double ang = 2.0 * kPi * num / den;
     return make_float2((float)std::cos(ang), (float)std::sin(ang));
   };
-  auto pass_tables = [&](int n) {
+  auto pass_tables = [&](int at, int n) {
     const WavePlan p = wave_plan(n);
     for (int i = 0; i < p.npass; i++)
       if (p.Ns[i] > 1)
-        for (int k = 0; k < p.Ns[i]; k++) tw.push_back(unit((double)k, (double)p.Ns[i] * p.R[i]));
+        for (int k = 0; k < p.Ns[i]; k++) tw[at++] = unit((double)k, (double)p.Ns[i] * p.R[i]);
   };
-  h->wave_off[0] = (int)tw.size();
-  pass_tables(NC);
-  h->wave_off[1] = (int)tw.size();
-  if (M > 1) pass_tables(MW / 2);
-  h->wave_off[2] = (int)tw.size();
-  if (M > 1) pass_tables(W / 2);
-  h->wave_off[3] = (int)tw.size();
-  if (M > 1)
-    for (int k = 0; k < W / 2; k++) tw.push_back(unit((double)k, (double)W));
-  h->wave_off[4] = (int)tw.size();
-  if (M > 1)
-    for (int k = 0; k < W / 2; k++) tw.push_back(unit((double)k, (double)MW));
-  h->wave_off[5] = (int)tw.size();
+  pass_tables(lay.off[0], NC);
+  if (M > 1) {
+    pass_tables(lay.off[1], MW / 2);
+    pass_tables(lay.off[2], W / 2);
+    for (int k = 0; k < W / 2; k++) tw[lay.off[3] + k] = unit((double)k, (double)W);
+    for (int k = 0; k < W / 2; k++) tw[lay.off[4] + k] = unit((double)k, (double)MW);
+  }
   // untangle factors of the real rows: bins below numdisplaypoints, or (displayed beyond N/2: the upper bins mirror) up to N/2
-  if (!cplx)
-    for (int k = 0; k < (D > N / 2 ? N / 2 + 1 : D); k++) tw.push_back(unit((double)k, (double)N));
-  h->wave_tw_count = (int)tw.size();
+  for (int k = 0; lay.off[5] + k < lay.count; k++) tw[lay.off[5] + k] = unit((double)k, (double)N);
   if ((rc = upload(h, h->d_wave_gidx, gi))) return rc;
   if ((rc = upload(h, h->d_wave_tw, tw))) return rc;
   h->tables_ok |= TABLES_WAVE;

@@ -33,47 +33,6 @@
 namespace fdoct {
 
 // ---------------------------------------------------------------- dispatch --
-#ifndef FDOCT_WAVE_EXTRA_TU
-int wave_max_waves(int W, int M, int N, int opt) { return wave_block_of(W, M, N, opt) / 64; }
-
-bool wave_shape_compiled(int W, int M, int N) {
-#define FDOCT_WAVE_HAS(W_, M_, N_) \
-  if (W == W_ && M == M_ && N == N_) return true;
-  FDOCT_WAVE_SHAPES(FDOCT_WAVE_HAS)
-#undef FDOCT_WAVE_HAS
-  return false;
-}
-
-static bool wave_shape_extra(int W, int M, int N) {
-#define FDOCT_WAVE_HAS(W_, M_, N_) \
-  if (W == W_ && M == M_ && N == N_) return true;
-  FDOCT_WAVE_SHAPES_EXTRA(FDOCT_WAVE_HAS)
-#undef FDOCT_WAVE_HAS
-  return false;
-}
-
-bool wave_kernel_available(int W, int M, int N, int dtype, int D) {
-  if (wave_shape_compiled(W, M, N)) return D <= N / 2;
-  return wave_shape_extra(W, M, N) && (dtype == FDOCT_K_U8 || dtype == FDOCT_K_U16) && D <= 512 && D <= N / 2;
-}
-#endif  // !FDOCT_WAVE_EXTRA_TU
-
-#ifndef FDOCT_WAVE_EXTRA_TU
-size_t wave_private_lds_bytes(int W, int M, int N, int opt) {
-  const int L = imax(imax(wave_fft_extent(wave_final_points(N, opt)), (M * W + 64 * wave_row_pad_floats(W, M)) / 2), M > 1 ? wave_fft_extent(M * W / 2) : 0);   // as the kernel's L
-  return (size_t)wave_private_bytes(L, M * W);
-}
-
-size_t wave_shared_lds_bytes(int tw_count, int W, int M, int N, bool ib_2d, int opt) {
-  const size_t words = (size_t)tw_count * 2 + wave_final_points(N, opt) + (size_t)M * W + 64 * wave_row_pad_floats(W, M) + W + (ib_2d ? 0 : 2 * W) +
-                       ((opt & FDOCT_WAVE_OPT_CPLX) ? 2 * (size_t)N : 0);  // as the kernel lays them out
-  return (words * 4 + 15) & ~(size_t)15;
-}
-
-// EXTRA shapes (FDOCT_WAVE_SHAPES_EXTRA) are compiled for the cameras' integer samples and numdisplaypoints <= 512 only: two
-// kernels per shape instead of six.
-#endif  // !FDOCT_WAVE_EXTRA_TU
-
 // One LdsGrant per KERNEL (the kernel is a non-type template argument: every instantiation has its own static; the kernels of
 // a shape share one function-pointer type, so a generic lambda over `auto k` would share one table -- ADVICE r4).
 template <auto K>

@@ -5,27 +5,11 @@
 #pragma once
 #include "fdoct_fft_reg.h"
 #include "fdoct_wave.h"
+#include "fdoct_wave_rules.h"
 
 namespace fdoct {
 
 namespace {
-
-// Register budget per shape (measured both ways on every shape, `tools/bench_generic.py`): rows whose upsampled length
-// reaches 2560 samples (40 samples per lane in the slope step, two 1280- or 1440-point transforms) spill at 168
-// registers and run faster with 8 waves per workgroup and 256 registers; the short rows (160 / 320 x4, 640 x1) are
-// faster with 12 waves at 168.
-// (The short zero-padded rows use 139-143 registers: 14 waves would still fit the LDS, but a workgroup of 14 puts four waves on
-// two of the SIMDs, i.e. a 128-register budget, and the spills cost more than the extra waves give: 2.9e8 against 3.0e8 on
-// BscanFFT.ini.  The webcam shape -- no zero-pad stage, 102 registers, a 2.6 KB buffer -- runs 16 waves: +3 %.)
-// (Complex rows gather a whole numfftpoints-point transform into registers -- twice the real rows' -- and their buffers are
-// twice as large, so the LDS holds few of them anyway: 8 waves, 256 registers.)
-#ifndef FDOCT_WAVE_BLOCK_SHORT
-#define FDOCT_WAVE_BLOCK_SHORT 768   // threads per workgroup of the short zero-padded rows (160 / 320 x 4 ...)
-#endif
-constexpr int wave_block_of(int w, int m, int n, int opt = 0) {
-  // (the band-pass forms the row and a few of its spectral bins in double: 44 spilled registers at 168 on the 160 x 4 shape)
-  return ((opt & (FDOCT_WAVE_OPT_CPLX | FDOCT_WAVE_OPT_BANDPASS)) || (w * m >= 2560 && m > 1)) ? 512 : (m == 1 ? 1024 : FDOCT_WAVE_BLOCK_SHORT);
-}
 
 __device__ __forceinline__ void wave_fence() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

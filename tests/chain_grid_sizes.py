@@ -16,8 +16,8 @@ MINMAX_THREADS = 1024    # minmax_kernel: i += 1024                             
 FINISH_BLOCK = 256       # frames per workgroup of minmax_finish_kernel                              fdoct_prepass_kernels.inc:93, fdoct_prepass_launch.inc:22
 SLICE = 65535            # frames of one minmax_fast_kernel launch (gridDim.y), groups of one transpose launch (gridDim.z)
 #                          fdoct_prepass_launch.inc:12, :40, :46
-GEN_MAX_PER_CU = 6       # generic_kernel: grid = min(CUs x per_cu, out_rows), 1 <= per_cu <= 6       fdoct_route.cpp:504-507
-GEN_TICKET_WORDS = 64    # row counters used in turn, gen_ticket_seq++ % 64                          fdoct_route.cpp:692-702
+GEN_MAX_PER_CU = 6       # generic_kernel: grid = min(CUs x per_cu, out_rows), 1 <= per_cu <= 6       fdoct_route_value.cpp, make_route
+GEN_TICKET_WORDS = 64    # row counters used in turn, gen_ticket_seq++ % 64                          fdoct_route.cpp, launch_family_generic
 LDS_BYTES = 160 * 1024
 
 
@@ -37,7 +37,7 @@ def generic_lds(W, M, N, D, buffers=2):
 
 
 def generic_per_cu(lds):
-    """Workgroups per CU that the route's grid counts (fdoct_route.cpp:506)."""
+    """Workgroups per CU that the route's grid counts (fdoct_route_value.cpp, make_route)."""
     return max(1, min(GEN_MAX_PER_CU, (LDS_BYTES - 1024) // lds))
 
 

@@ -51,7 +51,7 @@ def _non_integer(frames, rng, dtype):
 # kind: the option; route: 'wave' | 'generic', the kernel form the SHAPE reaches; family: the form the case runs.  They differ
 # where the pass in front of the chain hands the samples over as two float planes, a high and a low word -- doubles
 # (PrePass::F64Split, MovAvgF64: f64 frames, the colour sum) and the tap sums of non-integer floats (MovAvgF32Wide): the
-# wave-per-row kernel does not take the low plane (fdoct_route.cpp: wave_scope), so on its shape those cases run generic_kernel
+# wave-per-row kernel does not take the low plane (fdoct_route_value.cpp: wave_scope), so on its shape those cases run generic_kernel
 # on the zero-padded 200 x 4 row, a third geometry of the CX form.
 Option = collections.namedtuple("Option", "name route family shape kind")
 LOW_WORD_KINDS = ("movavgn 3, f32 non-integer frames", "movavgn 3, f64 non-integer frames", "colour handle, channel 3")

@@ -190,7 +190,7 @@ def family(name):
 
 
 def wave_option(case):
-    """Whether the case turns on one of the wave-per-row kernel's compile-time options (fdoct_route.cpp: wave_opt)."""
+    """Whether the case turns on one of the wave-per-row kernel's compile-time options (fdoct_route_value.cpp: wave_opt)."""
     return case.opt != "plain" or case.extra is not None
 
 

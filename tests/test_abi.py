@@ -153,6 +153,24 @@ def test_fused_launch_decisions_match_the_recorded_table(tmp_path):
     assert not diff, "%d launches differ, first: %s" % (len(diff), diff[0])
 
 
+def test_route_decisions_match_the_recorded_table(tmp_path):
+    """make_route (fdoct_amd/csrc/fdoct_route_value.h) decides, for every handle and call of tests/native/route_check.cpp's grid --
+    a shape of every kind of plan_check.cpp (fused, each built-in wave shape, an EXTRA one, a smooth one off both lists, an odd
+    width, a Bluestein length, long rows), three of them crossed with every sample type, reference frame, normalisation, phase, deep display,
+    moving average, median, binning (and the in-kernel binning's edges), colour channel, address and pitch off the vector grids,
+    layout, staged mode, plan / block / grid override, averaging, one B-scan, jit off, the compiler answering yes and no, and the
+    complex call, the others with the options whose launch depends on the shape --, exactly what route_check.expected recorded: the passes in front of the chain, the family, what its kernel
+    reads, waves / LDS / grid or the whole fused launch, the table sets, the note, every question put to the run-time compiler
+    -- or the refusal and its text, with a line for every pair of refusals that could both apply.  The table was recorded from
+    the arithmetic moved as it stood in choose_route_of, before the route became a value.  The program makes no HIP call."""
+    got, want = _native_table(tmp_path, "route_check")
+    assert len(got) == len(want) and len(want) > 450
+    diff = [(w, g) for w, g in zip(want, got) if w != g]
+    assert not diff, "%d routes differ, first: %s" % (len(diff), diff[0])
+    texts = {l.split(": rc=", 1)[1].split(" |")[0] for l in want if ": rc=" in l}
+    assert len(texts) == 13, sorted(texts)   # every refusal of make_route (and one of make_fused_launch's passing through)
+
+
 def test_plan_decisions_match_the_recorded_table(tmp_path):
     """make_plan (fdoct_amd/csrc/fdoct_plan.h) decides, for every configuration of tests/native/plan_check.cpp's grid -- the
     BASELINE shapes, the shipped ini shapes, odd widths, Bluestein lengths, in-place half lengths, rows beyond the LDS, with and

@@ -31,7 +31,7 @@ pytestmark = pytest.mark.gpu
 ROW, TR = capi.LAYOUT_ROWMAJOR, capi.LAYOUT_TRANSPOSED
 WAVE, GENERIC = capi.KERNEL_WAVE_JIT, capi.KERNEL_GENERIC
 H, NF = 12, 2
-WAVE_MAX_WAVES = 16   # waves of one workgroup of wave_kernel at most (1024 threads: wave_block_of, fdoct_wave_dev.h)
+WAVE_MAX_WAVES = 16   # waves of one workgroup of wave_kernel at most (1024 threads: wave_block_of, fdoct_wave_rules.h)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -239,7 +239,7 @@ def _cus():
 
 def wave_tall(rows, cus):
     """More than one pass of the wave-per-row kernel's grid whatever it is: the grid is at most one workgroup per CU and a workgroup
-    holds at most WAVE_MAX_WAVES waves, one row each at a time (fdoct_route.cpp, wave_fits) -- so one and a half passes of the
+    holds at most WAVE_MAX_WAVES waves, one row each at a time (fdoct_route_value.cpp, wave_launch) -- so one and a half passes of the
     largest launch, and a partial last pass for every number of waves."""
     return 2 * rows >= 3 * WAVE_MAX_WAVES * cus and all(rows % (k * cus) != 0 for k in range(1, WAVE_MAX_WAVES + 1))
 

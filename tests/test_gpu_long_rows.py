@@ -1,4 +1,4 @@
-"""The long-row path (fdoct_big.hip; big_idft and run_big in fdoct_route.cpp) where the rest of the suite does not reach: transforms
+"""The long-row path (fdoct_big.hip; big_idft and run_big in fdoct_big_host.cpp) where the rest of the suite does not reach: transforms
 of three grouped launches -- the middle launch is the only one with P > 1 and F > 1, where a tile of 16 sub-problems crosses a
 multiple of P and the store k1 + P (a Q + e) and the twiddle index (k1 + P k) twstep are non-trivial together --, every pairing of
 {even launches, odd launches, chirp} of the last two transforms of the chain (which of the two buffers each transform may
