@@ -117,6 +117,11 @@ CALIBRATE_ABI_SYMBOLS = ["fdoct_normalize_rows_minmax", "fdoct_calibrate_capture
 # every symbol include/fdoct_complex.h declares: the complex A-scan (re, im) of the chain.  It lives in libfdoct_complex.so, a second
 # add-on library over libfdoct_hip.so; load_library attaches it likewise
 COMPLEX_ABI_SYMBOLS = ["fdoct_process_complex"]
+# every symbol include/fdoct_doppler.h declares: phase-resolved Doppler from complex A-scans.  They live in libfdoct_doppler.so, a
+# third add-on library over libfdoct_hip.so; load_library attaches them likewise
+DOPPLER_ABI_SYMBOLS = ["fdoct_doppler_size", "fdoct_doppler", "fdoct_process_doppler"]
+# fdoct_doppler_axis (include/fdoct_doppler.h)
+DOPPLER_ASCANS, DOPPLER_FRAMES = 0, 1
 # fdoct_cal_slot (include/fdoct_calibrate.h)
 CAL_DARK, CAL_REFERENCE, CAL_SAMPLE = range(3)
 # fdoct_manualavg_mode (include/fdoct_manualavg.h)
@@ -153,6 +158,17 @@ def calibrate_library_path():
 def complex_library_path():
     """The add-on library of include/fdoct_complex.h, in the package next to the in-tree core library it is linked against."""
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfdoct_complex.so")
+
+
+def doppler_library_path():
+    """The add-on library of include/fdoct_doppler.h, in the package next to the in-tree core library it is linked against."""
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfdoct_doppler.so")
+
+
+class _CDopplerParams(C.Structure):
+    """fdoct_doppler_params (include/fdoct_doppler.h)."""
+    _fields_ = [("axis", C.c_int), ("lag", C.c_int), ("win_ascans", C.c_int), ("win_depths", C.c_int), ("bulk", C.c_int),
+                ("bulk_first", C.c_int), ("bulk_count", C.c_int), ("scale", C.c_double), ("min_power", C.c_double)]
 
 
 def load_library():
@@ -298,6 +314,18 @@ def load_library():
     for name in COMPLEX_ABI_SYMBOLS:
         setattr(lib, name, getattr(cx, name))
     lib.fdoct_process_complex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
+    # include/fdoct_doppler.h: likewise
+    dop_path = doppler_library_path()
+    if not os.path.exists(dop_path):
+        raise FdoctError(-3, "%s not found: build it with `make -C fdoct_amd/csrc` (or __graft_entry__.build())" % dop_path)
+    dop = C.CDLL(dop_path)
+    for name in DOPPLER_ABI_SYMBOLS:
+        setattr(lib, name, getattr(dop, name))
+    lib.fdoct_doppler_size.argtypes = [C.POINTER(_CDopplerParams), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.fdoct_doppler.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_CDopplerParams), C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int]
+    lib.fdoct_process_doppler.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(_CDopplerParams),
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     _lib = lib
     return lib
 
@@ -405,6 +433,49 @@ def manualavg_plan(manualaverages, mode, accumulated, nbscans):
     if rc:
         raise FdoctError(rc, "fdoct_manualavg_plan: manualaverages < 1, a bad mode, accumulated outside 0..manualaverages or nbscans < 0")
     return e.value, a.value
+
+
+def doppler_params(axis, lag, win=(1, 1), bulk=None, scale=1.0, min_power=0.0):
+    """fdoct_doppler_params from the binding's arguments.  bulk: None or False (no bulk-motion correction), True (every depth), or
+    (first, count) depths of the bulk sum, count 0 meaning all from `first` on."""
+    try:
+        wa, wd = (int(w) for w in win)
+    except (TypeError, ValueError):
+        raise FdoctError(-1, "win is (win_ascans, win_depths)")
+    if bulk is None or bulk is False:
+        on, first, count = 0, 0, 0
+    elif bulk is True:
+        on, first, count = 1, 0, 0
+    else:
+        try:
+            first, count = (int(b) for b in bulk)
+        except (TypeError, ValueError):
+            raise FdoctError(-1, "bulk is None, True or (first, count)")
+        on = 1
+    return _CDopplerParams(int(axis), int(lag), wa, wd, on, first, count, float(scale), float(min_power))
+
+
+def doppler_size(axis, lag, nframes, ascans, depths, win=(1, 1), bulk=None, scale=1.0, min_power=0.0):
+    """fdoct_doppler_size: (pair_images, pair_rows) of the pair images, or FdoctError where the parameters are refused.  Needs no GPU."""
+    p = doppler_params(axis, lag, win, bulk, scale, min_power)
+    pi, pr = C.c_int(), C.c_int()
+    rc = load_library().fdoct_doppler_size(C.byref(p), int(nframes), int(ascans), int(depths), C.byref(pi), C.byref(pr))
+    if rc:
+        raise FdoctError(rc, "fdoct_doppler_size: a window outside 1..32, a lag that leaves no pair, a bulk range outside the depths, "
+                             "or a scale or min_power that is not finite")
+    return pi.value, pr.value
+
+
+_DOPPLER_WANTS = ("phase", "corr", "power")
+
+
+def _doppler_outputs(want, shape):
+    """The requested result arrays of a Doppler call, in the order (phase, corr, power); None where not requested."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in _DOPPLER_WANTS for w in want) or len(set(want)) != len(want):
+        raise FdoctError(-1, "want names one or more of 'phase', 'corr', 'power', each once")
+    outs = {w: np.empty(shape, np.complex64 if w == "corr" else np.float32) for w in want}
+    return want, outs
 
 
 def _frame_batch(frames):
@@ -1063,6 +1134,58 @@ class Reconstructor:
         to 8 bytes).  Enqueues on the handle's stream."""
         self._check(self.lib.fdoct_process_complex(self.h, d_frames_ptr, dtype, MEM_DEVICE, int(nframes), int(pitch_bytes), d_out_ptr,
                                                    MEM_DEVICE, layout))
+
+    def doppler(self, X, axis, lag, win=(1, 1), bulk=None, scale=1.0, min_power=0.0, want=("phase", "corr", "power")):
+        """Phase-resolved Doppler of complex A-scans (include/fdoct_doppler.h): X is complex64 (n, H, D) on the host, row-major as
+        process_complex returns it; axis DOPPLER_ASCANS or DOPPLER_FRAMES; win = (win_ascans, win_depths).  Returns the arrays `want`
+        names, in its order (one name: that array alone): phase and power float32, corr complex64, all (pair_images, pair_rows, D).
+        Synchronous."""
+        a = np.asarray(X)
+        if a.dtype != np.complex64 or a.ndim != 3:
+            raise FdoctError(-1, "X must be complex64 of shape (nframes, ascans, depths)")
+        a = np.ascontiguousarray(a)
+        n, rows, d = a.shape
+        p = doppler_params(axis, lag, win, bulk, scale, min_power)
+        pi, pr = doppler_size(axis, lag, n, rows, d, win, bulk, scale, min_power)
+        names, outs = _doppler_outputs(want, (pi, pr, d))
+        ptr = lambda w: outs[w].ctypes.data if w in outs else None   # noqa: E731
+        self._check(self.lib.fdoct_doppler(self.h, a.ctypes.data, MEM_HOST, n, rows, d, C.byref(p), ptr("phase"), ptr("corr"), ptr("power"),
+                                           MEM_HOST))
+        return outs[names[0]] if isinstance(want, str) else tuple(outs[w] for w in names)
+
+    def doppler_device(self, d_re_im_ptr, nframes, ascans, depths, axis, lag, d_phase_ptr, d_corr_ptr, d_power_ptr, win=(1, 1), bulk=None,
+                       scale=1.0, min_power=0.0):
+        """... on device-resident pairs into device memory (raw addresses; any output may be None, d_corr_ptr aligned to 8 bytes).
+        Enqueues on the handle's stream."""
+        p = doppler_params(axis, lag, win, bulk, scale, min_power)
+        self._check(self.lib.fdoct_doppler(self.h, d_re_im_ptr, MEM_DEVICE, int(nframes), int(ascans), int(depths), C.byref(p), d_phase_ptr,
+                                           d_corr_ptr, d_power_ptr, MEM_DEVICE))
+
+    def process_doppler(self, frames, axis, lag, win=(1, 1), bulk=None, scale=1.0, min_power=0.0, want=("phase", "corr", "power")):
+        """fdoct_process_doppler: process_complex's chain on `frames` (numpy, as process() takes them) followed by doppler() on the card;
+        the complex A-scans never reach the host.  `averages` must be 1.  Returns what doppler() returns.  Synchronous."""
+        a = np.ascontiguousarray(frames)
+        if a.ndim == 2:
+            a = a[None]
+        if a.dtype not in _NP2DT:
+            raise FdoctError(-1, "unsupported frame dtype %s" % a.dtype)
+        if a.ndim == 4 and (a.shape[3] != 3 or a.dtype != np.uint8):
+            raise FdoctError(-1, "colour frames are (nframes, rows, cols, 3) uint8")
+        n, h, d = a.shape[0], self.cfg.height, self.cfg.numdisplaypoints
+        p = doppler_params(axis, lag, win, bulk, scale, min_power)
+        pi, pr = doppler_size(axis, lag, n, h, d, win, bulk, scale, min_power)
+        names, outs = _doppler_outputs(want, (pi, pr, d))
+        ptr = lambda w: outs[w].ctypes.data if w in outs else None   # noqa: E731
+        self._check(self.lib.fdoct_process_doppler(self.h, a.ctypes.data, _NP2DT[a.dtype], MEM_HOST, n, a.strides[1], C.byref(p), ptr("phase"),
+                                                   ptr("corr"), ptr("power"), MEM_HOST))
+        return outs[names[0]] if isinstance(want, str) else tuple(outs[w] for w in names)
+
+    def process_doppler_device(self, d_frames_ptr, dtype, nframes, pitch_bytes, axis, lag, d_phase_ptr, d_corr_ptr, d_power_ptr, win=(1, 1),
+                               bulk=None, scale=1.0, min_power=0.0):
+        """... on device-resident frames into device memory (raw addresses; any output may be None).  Enqueues on the handle's stream."""
+        p = doppler_params(axis, lag, win, bulk, scale, min_power)
+        self._check(self.lib.fdoct_process_doppler(self.h, d_frames_ptr, dtype, MEM_DEVICE, int(nframes), int(pitch_bytes), C.byref(p),
+                                                   d_phase_ptr, d_corr_ptr, d_power_ptr, MEM_DEVICE))
 
     def set_timing(self, on=True):
         """Device-side timing events for process_device() (process() always has them); see fdoct_set_timing."""
