@@ -597,6 +597,8 @@ class Reconstructor:
         return w
 
     def set_stream(self, hip_stream_ptr):
+        """All later work of this handle goes to that HIP stream (None: the handle's own), behind everything the handle has
+        enqueued so far: an event is recorded on the stream it leaves, so that stream must still exist when this is called."""
         self._check(self.lib.fdoct_set_stream(self.h, hip_stream_ptr))
 
     def set_launch(self, threads_per_block=0, blocks=0):
@@ -698,6 +700,11 @@ class Reconstructor:
         out = np.empty_like(b)
         self._check(self.lib.fdoct_lockin_db(self.h, b.ctypes.data, j.ctypes.data, MEM_HOST, n, j.size, out.ctypes.data))
         return out
+
+    def lockin_db_device(self, d_bscan_ptr, d_jscan_ptr, nbscans, count, d_out_ptr):
+        """... on device-resident B-scans of `count` floats each against one jscan (raw device addresses).  Enqueues on the handle's
+        stream."""
+        self._check(self.lib.fdoct_lockin_db(self.h, d_bscan_ptr, d_jscan_ptr, MEM_DEVICE, int(nbscans), int(count), d_out_ptr))
 
     def set_averages(self, averages):
         """Frames averaged per output B-scan from the next call on (the reference's averagestoggle)."""

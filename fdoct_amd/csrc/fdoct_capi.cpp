@@ -88,6 +88,7 @@ int fdoct_create(const fdoct_config* cfg, fdoct_handle* out) try {
   h->stream = h->own_stream;
   for (auto& ev : h->ev)
     if (hipEventCreate(&ev) != hipSuccess) return fail(nullptr, FDOCT_ERR_DEVICE, "hipEventCreate failed");
+  if (hipEventCreateWithFlags(&h->ev_order, hipEventDisableTiming) != hipSuccess) return fail(nullptr, FDOCT_ERR_DEVICE, "hipEventCreate failed");
 
   build_resample_table(h->W, h->M, h->N, cfg->lambdamin, cfg->lambdamax, h->idx, h->frac);
   build_barthann(h->W, h->win);
@@ -114,6 +115,7 @@ int fdoct_destroy(fdoct_handle h) try {
   h->copy_pool.reset();  // (its threads stop before anything else goes)
   for (auto& ev : h->ev)
     if (ev) (void)hipEventDestroy(ev);
+  if (h->ev_order) (void)hipEventDestroy(h->ev_order);
   for (int b = 0; b < 2; b++)
     for (hipEvent_t e : {h->pe_in[b], h->pe_k[b], h->pe_out[b]})
       if (e) (void)hipEventDestroy(e);
@@ -126,7 +128,14 @@ int fdoct_destroy(fdoct_handle h) try {
 
 int fdoct_set_stream(fdoct_handle h, void* hip_stream) try {
   if (!h) return FDOCT_ERR_INVALID;
-  h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
+  const hipStream_t next = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
+  if (next == h->stream) return FDOCT_OK;
+  // The handle carries device state from call to call (tables, workspaces, the manual-averaging accumulator, the peak holds):
+  // what it enqueues on the new stream runs behind everything it has enqueued on the old one.  No host wait.
+  DEVICE_SCOPE(h);
+  HIP_TRY(h, hipEventRecord(h->ev_order, h->stream));
+  HIP_TRY(h, hipStreamWaitEvent(next, h->ev_order, 0));
+  h->stream = next;
   return FDOCT_OK;
 } FDOCT_CATCH(h)
 

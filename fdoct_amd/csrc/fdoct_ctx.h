@@ -62,10 +62,13 @@ struct RefFrame {  // a caller-supplied reference frame (background / pi / dark)
 };
 
 inline int fail(fdoct_ctx* h, int code, const std::string& msg);
+inline void drain(fdoct_ctx* h);
 
 // Memory a handle owns: device memory (hipMalloc) or, Pinned, page-locked host memory (hipHostMalloc with the given flags).
 // Freed when the buffer dies; reads as the T* it holds, so that launch code fills its argument blocks from it directly.
 // Move-only (a BigPlan moves into the handle's map).
+// Stream order: reserve and assign replace a buffer that calls still in flight may read or write, so they drain the handle's streams
+// before they let go of it (retire) -- the wait hipFree happens to make, stated here so that it stays when the free does not.
 template <typename T, bool Pinned>
 class Buffer {
  public:
@@ -84,7 +87,7 @@ class Buffer {
   // at least `bytes`, grown only (the old contents are not kept)
   int reserve(fdoct_ctx* h, size_t bytes) {
     if (bytes_ >= bytes && p_) return FDOCT_OK;
-    release();
+    retire(h);
     void* q = nullptr;
     const hipError_t e = Pinned ? hipHostMalloc(&q, bytes, flags_) : hipMalloc(&q, bytes);
     if (e != hipSuccess) return fail(h, FDOCT_ERR_NOMEM, std::string(Pinned ? "hipHostMalloc: " : "hipMalloc: ") + hipGetErrorString(e));
@@ -93,12 +96,21 @@ class Buffer {
     return FDOCT_OK;
   }
   // exactly `count` elements; 0 releases the buffer
-  int assign(fdoct_ctx* h, size_t count) {
-    release();
+  // (drained: the caller has waited for the handle's streams itself -- a table rebuild does so once for all its tables)
+  int assign(fdoct_ctx* h, size_t count, bool drained = false) {
+    if (drained)
+      release();
+    else
+      retire(h);
     return count ? reserve(h, count * sizeof(T)) : FDOCT_OK;
   }
 
  private:
+  // release() once nothing the handle has enqueued can still use the memory
+  void retire(fdoct_ctx* h) {
+    if (p_ && h) drain(h);
+    release();
+  }
   T* p_ = nullptr;
   size_t bytes_ = 0;
   unsigned flags_ = hipHostMallocDefault;
@@ -258,6 +270,7 @@ struct fdoct_ctx {
   bool jit = true;                                // fdoct_set_jit / FDOCT_JIT=0: compile the wave-per-row kernel for shapes off the built-in list
   std::string jit_note;                           // why the last run-time compile was refused (the call itself fell back and succeeded)
   int last_kernel = FDOCT_KERNEL_NONE;            // fdoct_last_kernel
+  hipEvent_t ev_order = nullptr;                  // fdoct_set_stream: recorded on the stream the handle leaves, waited for on the one it moves to
 };
 
 namespace fdoct_impl {
@@ -301,9 +314,13 @@ struct DeviceScope {
   if (device_scope_.err != hipSuccess)                                                                      \
   return fail(h, FDOCT_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(device_scope_.err))
 
+// A device table built from host state.  Stream order: a rebuild waits for the handle's streams ONCE, at its head, before any of its
+// tables goes (fdoct_state.cpp: upload_shared, ensure_wave_tables), so a call enqueued before the setter that caused the rebuild has
+// finished with them; the tables of a new long-row plan go into buffers nothing has used.  The copy is synchronous, so the call
+// that follows finds the new table whichever stream it runs on.
 template <typename T>
 int upload(fdoct_ctx* h, DevBuf<T>& d, const std::vector<T>& v) {
-  if (int rc = d.assign(h, v.size())) return rc;
+  if (int rc = d.assign(h, v.size(), /*drained=*/true)) return rc;
   if (!v.empty()) HIP_TRY(h, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return FDOCT_OK;
 }

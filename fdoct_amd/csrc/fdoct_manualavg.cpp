@@ -13,6 +13,7 @@ namespace {
 bool valid_mode(int mode) { return mode == FDOCT_MANUALAVG_REFERENCE || mode == FDOCT_MANUALAVG_KEEP_ALL; }
 
 void forget(fdoct_ctx* h) {
+  if (h->d_mavg) drain(h);  // the adds still in flight use the accumulator
   h->d_mavg.release();
   h->mavg_count = 0;
   h->mavg_m = h->mavg_mode = h->mavg_accumulated = 0;
@@ -38,7 +39,7 @@ int fdoct_manualavg_begin(fdoct_handle h, int manualaverages, size_t count, int 
     return fail(h, FDOCT_ERR_INVALID, "fdoct_manualavg_begin: bad arguments");
   if (!h) return FDOCT_ERR_INVALID;
   DEVICE_SCOPE(h);
-  forget(h);  // (hipFree waits for the kernels that still use the old accumulator)
+  forget(h);  // (waits for the kernels that still use the old accumulator)
   if (int rc = h->d_mavg.assign(h, count)) return rc;
   const hipError_t e = hipMemsetAsync(h->d_mavg, 0, count * sizeof(double), h->stream);  // main:933
   if (e != hipSuccess) {

@@ -316,7 +316,10 @@ int launch_family_generic(fdoct_ctx* h, const Route& r, const Call& c) {
   ga.out_cx = c.k_cx;
   {
     // the launch's row counter: one of 64 words used in turn, zeroed on the stream in front of the launch (no host
-    // synchronisation; 64 launches of one handle are never in flight together)
+    // synchronisation).  A word comes round again after 64 launches, with any number of them still queued: what keeps it safe is
+    // stream order alone -- a handle's launches run one after the other on its stream (fdoct_set_stream puts the new stream behind
+    // the old), so the memset that re-zeroes a word runs after the launch that used it last has finished
+    // (tests/test_gpu_stream_order.py: 130 launches behind a stalled stream)
     constexpr unsigned kGenTickets = 64;
     static const bool no_tickets = [] { const char* e = std::getenv("FDOCT_GENERIC_TICKETS"); return e && std::atoi(e) == 0; }();  // measurement: the static stride
     if (h->d_gen_tickets && !no_tickets) {   // (allocated with the kernel's tables: ensure_generic_tables)

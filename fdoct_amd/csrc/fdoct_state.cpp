@@ -138,6 +138,7 @@ std::vector<double> scaled_copy(const std::vector<double>& v, double s) {
 // one-row background is uploaded as d_ib / d_il), the pi and dark frames with their second words, the phase.
 static int upload_shared(fdoct_ctx* h, std::vector<float>& ib, std::vector<float>& il) {
   int rc;
+  drain(h);  // the one wait of a rebuild (upload, fdoct_ctx.h): calls enqueued before the setter still read the tables that go
   reciprocal_words(scaled_copy(h->yb.v, plane_scales(h).yb), ib, il);
   if (h->yb.rows == 1) {
     if ((rc = upload(h, h->d_ib, ib))) return rc;
@@ -434,6 +435,7 @@ int ensure_wave_tables(fdoct_ctx* h) {
   int rc;
   if ((rc = ensure_generic_tables(h))) return rc;
   if (h->tables_ok & TABLES_WAVE) return FDOCT_OK;
+  if (h->d_wave_gidx) drain(h);  // (the generic rebuild above has waited when it ran; this holds where it did not)
   // complex rows (dispersion phase): the final transform runs over the whole row, one gather source per point
   const bool cplx = !h->phase.empty();
   const int W = h->W, M = h->M, N = h->N, MW = W * M, NC = cplx ? N : N / 2;

@@ -121,7 +121,14 @@ int fdoct_destroy(fdoct_handle h);
 const char* fdoct_last_error(fdoct_handle h); /* h may be NULL: last create error */
 
 /* Use an existing HIP stream (hipStream_t) for all work of this handle; NULL =
- * the handle's own stream. */
+ * the handle's own stream.  Stream order: work enqueued after the call runs after
+ * everything this handle enqueued before it -- the library records an event on the
+ * stream it leaves and makes the new stream wait for it; the host does not wait.
+ * The stream the handle leaves must therefore still exist when this is called.
+ * Calls of one handle run in call order whichever stream each was enqueued on; a
+ * setter (fdoct_set_*, fdoct_import_state) takes effect for later calls only, and
+ * the first call after one may wait for the handle's earlier work while the
+ * device tables are rebuilt. */
 int fdoct_set_stream(fdoct_handle h, void* hip_stream);
 
 /* data_yb, the 'b' key (main:1000-1075, sim:803-813): rows = 1 (one spectrum
