@@ -326,6 +326,9 @@ def load_library():
                                   C.c_void_p, C.c_void_p, C.c_int]
     lib.fdoct_process_doppler.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(_CDopplerParams),
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    # include/fdoct_dispersion.h: likewise; the binding is a module of its own (fdoct_amd/dispersion.py)
+    from . import dispersion
+    dispersion.attach(lib)
     _lib = lib
     return lib
 

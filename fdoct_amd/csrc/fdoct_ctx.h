@@ -18,6 +18,7 @@
 //   fdoct_calibrate.cpp those of include/fdoct_calibrate.h (BscanDark's calibration: device-side normalisations, held captures, composition)
 //   fdoct_complex.cpp that of include/fdoct_complex.h (the complex A-scan: the chain through fdoct_route.cpp's enqueue_complex, the D x H layout)
 //   fdoct_doppler.cpp those of include/fdoct_doppler.h (phase-resolved Doppler from complex A-scans: the stage alone, and behind enqueue_complex)
+//   fdoct_dispersion.cpp those of include/fdoct_dispersion.h (the dispersion search over (a2, a3): the stage alone, and behind enqueue_complex)
 //   fdoct_stage.h     the staging plan of host-memory arguments: the side entry points', fdoct_process's single shot (stage_reserve / stage_upload / stage_finish, below, commit it)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
@@ -256,6 +257,10 @@ struct fdoct_ctx {
   DevBuf<float2> ws_cx;
   // phase-resolved Doppler (fdoct_doppler.cpp): fdoct_process_doppler's pairs go through ws_cx; the bulk-motion phasors, one per pair row
   DevBuf<float2> ws_dop_bulk;
+  // the dispersion search (fdoct_dispersion.cpp): fdoct_process_dispersion_search's pairs go through ws_cx; the transform's twiddles
+  // and the two phasor tables (DispersionArgs::tab), and the winner on its way to host memory
+  DevBuf<float2> ws_disp_tab;
+  DevBuf<unsigned char> ws_disp_best;
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
