@@ -329,6 +329,9 @@ def load_library():
     # include/fdoct_dispersion.h: likewise; the binding is a module of its own (fdoct_amd/dispersion.py)
     from . import dispersion
     dispersion.attach(lib)
+    # include/fdoct_vibro.h: likewise (fdoct_amd/vibrometry.py)
+    from . import vibrometry
+    vibrometry.attach(lib)
     _lib = lib
     return lib
 

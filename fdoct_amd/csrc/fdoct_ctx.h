@@ -19,6 +19,7 @@
 //   fdoct_complex.cpp that of include/fdoct_complex.h (the complex A-scan: the chain through fdoct_route.cpp's enqueue_complex, the D x H layout)
 //   fdoct_doppler.cpp those of include/fdoct_doppler.h (phase-resolved Doppler from complex A-scans: the stage alone, and behind enqueue_complex)
 //   fdoct_dispersion.cpp those of include/fdoct_dispersion.h (the dispersion search over (a2, a3): the stage alone, and behind enqueue_complex)
+//   fdoct_vibro.cpp   those of include/fdoct_vibro.h (vibrometry from the phase over time: the stage alone, and behind enqueue_complex)
 //   fdoct_stage.h     the staging plan of host-memory arguments: the side entry points', fdoct_process's single shot (stage_reserve / stage_upload / stage_finish, below, commit it)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
@@ -261,6 +262,12 @@ struct fdoct_ctx {
   // and the two phasor tables (DispersionArgs::tab), and the winner on its way to host memory
   DevBuf<float2> ws_disp_tab;
   DevBuf<unsigned char> ws_disp_best;
+  // vibrometry (fdoct_vibro.cpp): fdoct_process_vibro's pairs go through ws_cx; the reference phasors, one per frame and A-scan; the
+  // chunk partials; the lock-in's tables and their sums (VibroArgs::tab, cst, head, glob); outputs on their way to host memory
+  DevBuf<float2> ws_vib_ref;
+  DevBuf<double> ws_vib_part;
+  DevBuf<double2> ws_vib_tab;
+  DevBuf<unsigned char> ws_vib_out;
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
