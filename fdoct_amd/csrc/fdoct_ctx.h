@@ -259,15 +259,13 @@ struct fdoct_ctx {
   // phase-resolved Doppler (fdoct_doppler.cpp): fdoct_process_doppler's pairs go through ws_cx; the bulk-motion phasors, one per pair row
   DevBuf<float2> ws_dop_bulk;
   // the dispersion search (fdoct_dispersion.cpp): fdoct_process_dispersion_search's pairs go through ws_cx; the transform's twiddles
-  // and the two phasor tables (DispersionArgs::tab), and the winner on its way to host memory
+  // and the two phasor tables (DispersionArgs::tab).  The outputs, the winner included, go through the staging plan
   DevBuf<float2> ws_disp_tab;
-  DevBuf<unsigned char> ws_disp_best;
   // vibrometry (fdoct_vibro.cpp): fdoct_process_vibro's pairs go through ws_cx; the reference phasors, one per frame and A-scan; the
-  // chunk partials; the lock-in's tables and their sums (VibroArgs::tab, cst, head, glob); outputs on their way to host memory
+  // chunk partials; the lock-in's tables and their sums (VibroArgs::tab, cst, head, glob).  The outputs go through the staging plan
   DevBuf<float2> ws_vib_ref;
   DevBuf<double> ws_vib_part;
   DevBuf<double2> ws_vib_tab;
-  DevBuf<unsigned char> ws_vib_out;
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
@@ -364,6 +362,15 @@ inline int stage_finish(fdoct_ctx* h, const StagePlan& p) {
   if (int rc = stage_copy(h, p, true)) return rc;
   if (p.sync) HIP_TRY(h, hipStreamSynchronize(h->stream));
   return FDOCT_OK;
+}
+// The refusal of fdoct_stage.h's overlaps(), in the words of the side entry points; `in_name` is what the message calls the input.
+inline int refuse_overlaps(fdoct_ctx* h, const std::string& fn, const char* in_name, const void* in, size_t in_bytes, const void* const* out,
+                           const size_t* bytes, int n) {
+  switch (overlaps(in, in_bytes, out, bytes, n)) {
+    case OVERLAP_INPUT: return fail(h, FDOCT_ERR_INVALID, fn + ": " + in_name + " and output buffers overlap");
+    case OVERLAP_OUTPUTS: return fail(h, FDOCT_ERR_INVALID, fn + ": the outputs overlap");
+    default: return FDOCT_OK;
+  }
 }
 
 // COLORMAP_JET as OpenCV builds it (fdoct_host.cpp::build_opencv_jet): dark blue (128,0,0 in B,G,R) at 0 through cyan and

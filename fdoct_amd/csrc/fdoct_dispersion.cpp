@@ -1,9 +1,9 @@
 // fdoct_dispersion.cpp -- the extern "C" entry points of include/fdoct_dispersion.h (libfdoct_dispersion.so): a numerical
 // dispersion search over (a2, a3) on complex A-scans.  The kernels are fdoct_dispersion.hip's; the chain in front of
-// fdoct_process_dispersion_search is the core library's (fdoct_route.cpp: enqueue_complex), called as fdoct_doppler.cpp calls it;
-// the transform's radices are the planner's (fdoct_plan.cpp: make_plan on a complex row of n points).  What is this file's own
-// is the calls' arguments: the grid's refusals, the call's geometry as a value (plan_search; fdoct_dispersion_plan reports it),
-// and pairs, frames and outputs in host or device memory planned as fdoct_doppler.cpp plans its.
+// fdoct_process_dispersion_search is the core library's (fdoct_route.cpp: enqueue_complex), called in the order
+// fdoct_capture_plan.h's ComplexFront keeps; the transform's radices are the planner's (fdoct_plan.cpp: make_plan on a complex row
+// of n points).  What is this file's own is the calls' arguments: the grid's refusals, the call's geometry as a value (plan_search;
+// fdoct_dispersion_plan reports it), and pairs, frames and all four outputs in host or device memory through the staging plan.
 #include "../../include/fdoct_dispersion.h"
 
 #include <cmath>
@@ -83,47 +83,29 @@ int check_outputs(fdoct_ctx* h, const char* fn, const OutBytes& b, const void* i
                   const fdoct_dispersion_best* out_best, const float* out_cos_sin) {
   const std::string f(fn);
   if (!out_sums && !out_row_sums && !out_best && !out_cos_sin) return fail(h, FDOCT_ERR_INVALID, f + ": no output");
-  const void* p[4] = {out_sums, out_row_sums, out_best, out_cos_sin};
+  const void* const p[4] = {out_sums, out_row_sums, out_best, out_cos_sin};
   const size_t nb[4] = {b.sums, b.row_sums, sizeof(fdoct_dispersion_best), b.table};
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < 4; i++)
     if (reinterpret_cast<uintptr_t>(p[i]) % 8) return fail(h, FDOCT_ERR_INVALID, f + ": every output must be aligned to 8 bytes");
-    if (overlap(in, in_bytes, p[i], nb[i])) return fail(h, FDOCT_ERR_INVALID, f + ": input and output buffers overlap");
-    for (int j = 0; j < i; j++)
-      if (overlap(p[i], nb[i], p[j], nb[j])) return fail(h, FDOCT_ERR_INVALID, f + ": the outputs overlap");
-  }
-  return FDOCT_OK;
+  return refuse_overlaps(h, f, "input", in, in_bytes, p, nb, 4);
 }
 
-// The call's workspaces and outputs: the three arrays through the staging plan (a null one is scratch the kernels write anyway),
-// the winner where the caller's memory is the device's, else in the handle's own buffer.  Reservations only.
-struct OutPlan {
-  int sums = 0, row_sums = 0, table = 0;
-  fdoct_dispersion_best* host_best = nullptr;   // out_best in host memory: copied down behind the kernels
-};
-
-int reserve_outputs(fdoct_ctx* h, StagePlan* sp, const OutBytes& b, double* out_sums, double* out_row_sums, fdoct_dispersion_best* out_best,
-                    float* out_cos_sin, fdoct_memspace out_space, OutPlan* o) {
-  o->sums = sp->out_or_scratch(out_sums, out_space, b.sums);
-  o->row_sums = sp->out_or_scratch(out_row_sums, out_space, b.row_sums);
-  o->table = sp->out(out_cos_sin, out_space, b.table);
-  if (int rc = stage_reserve(h, sp)) return rc;
+// What both entry points end with.  sp's item 0 is the input (the pairs, or with `front` the frames of its chain, whose pairs are
+// ws_cx's): the outputs join the plan -- a null array or winner is scratch the kernels write anyway, a null table a null pointer
+// they skip -- then every reservation, the copies up, the chain, the kernels, the copies down.
+int run_search(fdoct_ctx* h, StagePlan* sp, ComplexFront* front, fdoct::DispersionArgs a, const OutBytes& b, double* out_sums, double* out_row_sums,
+               fdoct_dispersion_best* out_best, float* out_cos_sin, fdoct_memspace out_space) {
+  DEVICE_SCOPE(h);
+  const int sums = sp->out_or_scratch(out_sums, out_space, b.sums), row_sums = sp->out_or_scratch(out_row_sums, out_space, b.row_sums);
+  const int best = sp->out_or_scratch(out_best, out_space, sizeof(fdoct::DispBest)), table = sp->out(out_cos_sin, out_space, b.table);
+  if (int rc = front ? reserve_complex_front(h, front) : stage_reserve(h, sp)) return rc;
   if (int rc = h->ws_disp_tab.reserve(h, b.tab)) return rc;
-  if (int rc = h->ws_disp_best.reserve(h, sizeof(fdoct::DispBest))) return rc;
-  if (out_best && out_space == FDOCT_MEM_HOST) o->host_best = out_best, sp->sync = true;
-  return FDOCT_OK;
-}
-
-void set_pointers(fdoct_ctx* h, const StagePlan& sp, const OutPlan& o, fdoct_dispersion_best* out_best, fdoct::DispersionArgs* a) {
-  a->tab = h->ws_disp_tab;
-  a->sums = sp.dev<double2>(o.sums), a->row_sums = sp.dev<double2>(o.row_sums), a->cos_sin = sp.dev<float2>(o.table);
-  a->best = (out_best && !o.host_best) ? reinterpret_cast<fdoct::DispBest*>(out_best) : reinterpret_cast<fdoct::DispBest*>((unsigned char*)h->ws_disp_best);
-}
-
-// The kernels, the winner's copy to host memory, the staged outputs' copies and the synchronise host memory asks for.
-int run_search(fdoct_ctx* h, const StagePlan& sp, const OutPlan& o, const fdoct::DispersionArgs& a) {
+  a.x = front ? static_cast<const float2*>(h->ws_cx) : sp->dev<const float2>(0);
+  a.tab = h->ws_disp_tab;
+  a.sums = sp->dev<double2>(sums), a.row_sums = sp->dev<double2>(row_sums), a.best = sp->dev<fdoct::DispBest>(best), a.cos_sin = sp->dev<float2>(table);
+  if (int rc = front ? run_complex_front(h, *front) : stage_upload(h, *sp)) return rc;
   HIP_TRY(h, fdoct::launch_dispersion(a, h->stream));
-  if (o.host_best) HIP_TRY(h, hipMemcpyAsync(o.host_best, a.best, sizeof(fdoct::DispBest), hipMemcpyDeviceToHost, h->stream));
-  return stage_finish(h, sp);
+  return stage_finish(h, *sp);
 }
 
 }  // namespace
@@ -165,16 +147,9 @@ int fdoct_dispersion_search(fdoct_handle h, const float* re_im, fdoct_memspace s
   const size_t in_bytes = (size_t)rows * (size_t)n * sizeof(float2);
   if (int rc = check_outputs(h, "fdoct_dispersion_search", b, space == out_space ? re_im : nullptr, in_bytes, out_sums, out_row_sums, out_best, out_cos_sin))
     return rc;
-  DEVICE_SCOPE(h);
-  // every reservation before anything is enqueued: the staged arguments, the tables, the winner's buffer
   StagePlan sp;
-  OutPlan o;
-  const int in = sp.in(re_im, space, in_bytes);
-  if (int rc = reserve_outputs(h, &sp, b, out_sums, out_row_sums, out_best, out_cos_sin, out_space, &o)) return rc;
-  a.x = sp.dev<const float2>(in);
-  set_pointers(h, sp, o, out_best, &a);
-  if (int rc = stage_upload(h, sp)) return rc;
-  return run_search(h, sp, o, a);
+  sp.in(re_im, space, in_bytes);
+  return run_search(h, &sp, nullptr, a, b, out_sums, out_row_sums, out_best, out_cos_sin, out_space);
 } FDOCT_CATCH(h)
 
 int fdoct_process_dispersion_search(fdoct_handle h, const void* frames, fdoct_dtype dtype, fdoct_memspace space, int nframes,
@@ -188,25 +163,12 @@ int fdoct_process_dispersion_search(fdoct_handle h, const void* frames, fdoct_dt
   fdoct::DispersionArgs a;
   if (int rc = plan_search(h, "fdoct_process_dispersion_search", grid, (long long)nframes * h->H, h->N, &a)) return rc;
   const OutBytes b = out_bytes(a);
-  FramePlan p;
-  if (int rc = plan_frames(h, "fdoct_process_dispersion_search", frames, dtype, space, nframes, pitch_bytes, &p)) return rc;
-  size_t in_span = 0;
-  if (__builtin_mul_overflow(p.pitch, (size_t)p.raw_h * (size_t)nframes, &in_span))
-    return fail(h, FDOCT_ERR_INVALID, "fdoct_process_dispersion_search: the batch is too large");
-  if (int rc = check_outputs(h, "fdoct_process_dispersion_search", b, space == out_space ? frames : nullptr, in_span, out_sums, out_row_sums, out_best, out_cos_sin))
+  ComplexFront front;
+  if (int rc = plan_complex_front(h, "fdoct_process_dispersion_search", frames, dtype, space, nframes, pitch_bytes, &front)) return rc;
+  if (int rc = check_outputs(h, "fdoct_process_dispersion_search", b, space == out_space ? frames : nullptr, front.in_span, out_sums, out_row_sums, out_best,
+                             out_cos_sin))
     return rc;
-  DEVICE_SCOPE(h);
-  // every refusal and reservation before anything is enqueued: the staged arguments, the chain's pairs, the tables, then the chain's
-  // own checks and its route on the frames where the kernels will read them (a run-time compile happens here)
-  OutPlan o;
-  if (int rc = reserve_outputs(h, &p.stage, b, out_sums, out_row_sums, out_best, out_cos_sin, out_space, &o)) return rc;
-  if (int rc = h->ws_cx.reserve(h, (size_t)a.rows * (size_t)a.n * sizeof(float2))) return rc;
-  if (int rc = enqueue_complex(h, p.stage.dev<const void>(0), dtype, nframes, p.stage.pitch(0), nullptr)) return rc;
-  a.x = h->ws_cx;
-  set_pointers(h, p.stage, o, out_best, &a);
-  if (int rc = stage_upload(h, p.stage)) return rc;
-  if (int rc = enqueue_complex(h, p.stage.dev<const void>(0), dtype, nframes, p.stage.pitch(0), h->ws_cx)) return rc;
-  return run_search(h, p.stage, o, a);
+  return run_search(h, &front.p.stage, &front, a, b, out_sums, out_row_sums, out_best, out_cos_sin, out_space);
 } FDOCT_CATCH(h)
 
 }  // extern "C"

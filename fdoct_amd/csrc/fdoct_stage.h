@@ -16,6 +16,17 @@ inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
   return a && b && x < y + nb && y < x + na;
 }
+// What a call with n outputs of bytes[i] bytes at out[i] (null: absent) and an input range (in null: none, or one in another memory
+// space) refuses: the input lying on an output, or two outputs on each other.
+enum Overlap { OVERLAP_NONE = 0, OVERLAP_INPUT, OVERLAP_OUTPUTS };
+inline Overlap overlaps(const void* in, size_t in_bytes, const void* const* out, const size_t* bytes, int n) {
+  for (int i = 0; i < n; i++) {
+    if (overlap(in, in_bytes, out[i], bytes[i])) return OVERLAP_INPUT;
+    for (int j = 0; j < i; j++)
+      if (overlap(out[i], bytes[i], out[j], bytes[j])) return OVERLAP_OUTPUTS;
+  }
+  return OVERLAP_NONE;
+}
 
 struct StageItem {
   void *ptr = nullptr, *dev = nullptr;  // the caller's pointer (null: scratch if staged, else an output nobody reads); what the kernel takes (stage_reserve)
@@ -27,9 +38,9 @@ struct StageItem {
 
 // Every adder returns its item's index.  The flat form is (p, mem, bytes); the 2-D form adds rows and the caller's pitch, and
 // staged rows are packed_pitch(row) apart.  Any memory space but host reads as device memory: the caller's pointer and pitch pass
-// through.  Arithmetic that would wrap size_t, or a fifth item, leaves rc set: the call is refused at reserve.
+// through.  Arithmetic that would wrap size_t, or one item past kMaxItems, leaves rc set: the call is refused at reserve.
 struct StagePlan {
-  static constexpr size_t kMaxItems = 4, kAlign = 256;  // every staged item starts at a multiple of kAlign, whatever the others' sizes
+  static constexpr size_t kMaxItems = 8, kAlign = 256;  // frames and up to seven further arguments; every staged item starts at a multiple of kAlign, whatever the others' sizes
   StageItem item[kMaxItems];
   int count = 0, rc = FDOCT_OK;
   size_t in_bytes = 0, out_bytes = 0;  // what the two workspaces must hold

@@ -1,10 +1,8 @@
 // fdoct_vibro.cpp -- the extern "C" entry points of include/fdoct_vibro.h (libfdoct_vibro.so): phase-sensitive vibrometry from
 // complex A-scans over time.  The kernels are fdoct_vibro.hip's; the chain in front of fdoct_process_vibro is the core library's
-// (fdoct_route.cpp: enqueue_complex), called as fdoct_dispersion.cpp calls it.  What is this file's own is the calls' arguments:
-// the parameters' refusals and the chunk rule (plan_vibro; fdoct_vibro_plan reports it), and pairs, frames and outputs in host or
-// device memory.  The pairs or frames go through the staging plan as fdoct_doppler.cpp's do.  A staging plan holds four items and
-// this stage has four outputs beside its input, so outputs in host memory go through one workspace of the stage's own (ws_vib_out)
-// and are copied down behind the kernels, as fdoct_dispersion.cpp copies its winner.
+// (fdoct_route.cpp: enqueue_complex), called in the order fdoct_capture_plan.h's ComplexFront keeps.  What is this file's own is the
+// calls' arguments: the parameters' refusals and the chunk rule (plan_vibro; fdoct_vibro_plan reports it), and pairs, frames and
+// all four outputs in host or device memory through the staging plan.
 #include "../../include/fdoct_vibro.h"
 
 #include <cmath>
@@ -81,38 +79,31 @@ int check_outputs(fdoct_ctx* h, const char* fn, const fdoct::VibroArgs& a, const
   if (!out_amp && !out_rms && !out_drift && !out_power) return fail(h, FDOCT_ERR_INVALID, f + ": no output");
   if (out_amp && a.nfreq == 0) return fail(h, FDOCT_ERR_INVALID, f + ": out_amp must be NULL with nfreq 0");
   if (reinterpret_cast<uintptr_t>(out_amp) % sizeof(float2)) return fail(h, FDOCT_ERR_INVALID, f + ": out_amp must be aligned to one (re, im) pair (8 bytes)");
-  const void* p[4] = {out_amp, out_rms, out_drift, out_power};
+  const void* const p[4] = {out_amp, out_rms, out_drift, out_power};
   const size_t nb[4] = {b.amp, b.floats, b.floats, b.floats};
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < 4; i++)
     if (reinterpret_cast<uintptr_t>(p[i]) % sizeof(float)) return fail(h, FDOCT_ERR_INVALID, f + ": out_rms, out_drift and out_power must be aligned to 4 bytes");
-    if (overlap(in, in_bytes, p[i], nb[i])) return fail(h, FDOCT_ERR_INVALID, f + ": input and output buffers overlap");
-    for (int j = 0; j < i; j++)
-      if (overlap(p[i], nb[i], p[j], nb[j])) return fail(h, FDOCT_ERR_INVALID, f + ": the outputs overlap");
-  }
-  return FDOCT_OK;
+  return refuse_overlaps(h, f, "input", in, in_bytes, p, nb, 4);
 }
 
-// Where the kernels write: the caller's device memory, or a section of ws_vib_out on its way to the caller's host memory.
-struct OutPlan {
-  void* host[4] = {nullptr, nullptr, nullptr, nullptr};   // the caller's host pointers, or null
-  size_t offset[4] = {0, 0, 0, 0}, bytes[4] = {0, 0, 0, 0};
-  size_t total = 0;
-};
+// Without out_amp the lock-in's sums have no reader: the kernels skip them, and the other outputs' bits do not depend on them.
+void drop_unread(fdoct::VibroArgs* a, VibBytes* b, const float* out_amp) {
+  if (out_amp || !a->nfreq) return;
+  a->nfreq = 0;
+  b->tab = b->tab_entries = b->cst_entries = 0;
+  b->part = a->chunks > 1 ? (size_t)a->chunks * (size_t)fdoct::vibro_sums(0) * (size_t)a->pixels * sizeof(double) : 0;
+}
 
-// Every reservation of the stage: the outputs' workspace, the reference phasors, the tables, the chunk partials.
-int reserve_stage(fdoct_ctx* h, StagePlan* sp, const fdoct::VibroArgs& a, const VibBytes& b, float* out_amp, float* out_rms, float* out_drift, float* out_power,
-                  fdoct_memspace out_space, OutPlan* o) {
-  if (out_space == FDOCT_MEM_HOST) {
-    void* p[4] = {out_amp, out_rms, out_drift, out_power};
-    const size_t nb[4] = {b.amp, b.floats, b.floats, b.floats};
-    for (int i = 0; i < 4; i++) {
-      if (!p[i]) continue;
-      o->host[i] = p[i], o->offset[i] = o->total, o->bytes[i] = nb[i];
-      o->total += (nb[i] + StagePlan::kAlign - 1) & ~(StagePlan::kAlign - 1);   // <= 2^30 + 3 2^26 + 4 kAlign
-    }
-    sp->sync = true;
-    if (int rc = h->ws_vib_out.reserve(h, o->total)) return rc;
-  }
+// What both entry points end with.  sp's item 0 is the input (the pairs, or with `front` the frames of its chain, whose pairs are
+// ws_cx's): the outputs join the plan (a null one is a null pointer the kernels skip), then every reservation -- the reference
+// phasors, the tables, the chunk partials -- the copies up, the chain, the kernels, the copies down.
+int run_stage(fdoct_ctx* h, StagePlan* sp, ComplexFront* front, fdoct::VibroArgs a, VibBytes b, float* out_amp, float* out_rms, float* out_drift,
+              float* out_power, fdoct_memspace out_space) {
+  drop_unread(&a, &b, out_amp);
+  DEVICE_SCOPE(h);
+  const int amp = sp->out(out_amp, out_space, b.amp), rms = sp->out(out_rms, out_space, b.floats);
+  const int drift = sp->out(out_drift, out_space, b.floats), power = sp->out(out_power, out_space, b.floats);
+  if (int rc = front ? reserve_complex_front(h, front) : stage_reserve(h, sp)) return rc;
   if (a.use_ref) {
     if (int rc = h->ws_vib_ref.reserve(h, b.ref)) return rc;
   }
@@ -122,39 +113,19 @@ int reserve_stage(fdoct_ctx* h, StagePlan* sp, const fdoct::VibroArgs& a, const 
   if (a.chunks > 1) {
     if (int rc = h->ws_vib_part.reserve(h, b.part)) return rc;
   }
-  return FDOCT_OK;
-}
-
-void set_pointers(fdoct_ctx* h, const VibBytes& b, const OutPlan& o, float* out_amp, float* out_rms, float* out_drift, float* out_power, fdoct::VibroArgs* a) {
-  unsigned char* const w = h->ws_vib_out;
-  a->out_amp = reinterpret_cast<float2*>(o.host[0] ? w + o.offset[0] : reinterpret_cast<unsigned char*>(out_amp));
-  a->out_rms = reinterpret_cast<float*>(o.host[1] ? w + o.offset[1] : reinterpret_cast<unsigned char*>(out_rms));
-  a->out_drift = reinterpret_cast<float*>(o.host[2] ? w + o.offset[2] : reinterpret_cast<unsigned char*>(out_drift));
-  a->out_power = reinterpret_cast<float*>(o.host[3] ? w + o.offset[3] : reinterpret_cast<unsigned char*>(out_power));
-  a->refph = h->ws_vib_ref, a->part = h->ws_vib_part;
-  if (a->nfreq) {
-    const size_t slots = (size_t)a->nfreq + 1;
-    a->tab = h->ws_vib_tab;
-    a->cst = a->tab + b.tab_entries;
-    a->head = a->cst + b.cst_entries;
-    a->glob = a->head + slots;
+  a.x = front ? static_cast<const float2*>(h->ws_cx) : sp->dev<const float2>(0);
+  a.out_amp = sp->dev<float2>(amp), a.out_rms = sp->dev<float>(rms), a.out_drift = sp->dev<float>(drift), a.out_power = sp->dev<float>(power);
+  a.refph = h->ws_vib_ref, a.part = h->ws_vib_part;
+  if (a.nfreq) {
+    const size_t slots = (size_t)a.nfreq + 1;
+    a.tab = h->ws_vib_tab;
+    a.cst = a.tab + b.tab_entries;
+    a.head = a.cst + b.cst_entries;
+    a.glob = a.head + slots;
   }
-}
-
-// The kernels, the outputs' copies to host memory, the staged copies and the synchronise host memory asks for.
-int run_stage(fdoct_ctx* h, const StagePlan& sp, const OutPlan& o, const fdoct::VibroArgs& a) {
+  if (int rc = front ? run_complex_front(h, *front) : stage_upload(h, *sp)) return rc;
   HIP_TRY(h, fdoct::launch_vibro(a, h->stream));
-  for (int i = 0; i < 4; i++)
-    if (o.host[i]) HIP_TRY(h, hipMemcpyAsync(o.host[i], (unsigned char*)h->ws_vib_out + o.offset[i], o.bytes[i], hipMemcpyDeviceToHost, h->stream));
-  return stage_finish(h, sp);
-}
-
-// Without out_amp the lock-in's sums have no reader: the kernels skip them, and the other outputs' bits do not depend on them.
-void drop_unread(fdoct::VibroArgs* a, VibBytes* b, const float* out_amp) {
-  if (out_amp || !a->nfreq) return;
-  a->nfreq = 0;
-  b->tab = b->tab_entries = b->cst_entries = 0;
-  b->part = a->chunks > 1 ? (size_t)a->chunks * (size_t)fdoct::vibro_sums(0) * (size_t)a->pixels * sizeof(double) : 0;
+  return stage_finish(h, *sp);
 }
 
 }  // namespace
@@ -183,18 +154,9 @@ int fdoct_vibro(fdoct_handle h, const float* re_im, fdoct_memspace space, int nf
   if (int rc = plan_vibro(h, "fdoct_vibro", params, nframes, ascans, depths, &a, &b)) return rc;
   const size_t in_bytes = (size_t)nframes * (size_t)a.pixels * sizeof(float2);   // <= 2^16 2^24 8
   if (int rc = check_outputs(h, "fdoct_vibro", a, b, space == out_space ? re_im : nullptr, in_bytes, out_amp, out_rms, out_drift, out_power)) return rc;
-  drop_unread(&a, &b, out_amp);
-  DEVICE_SCOPE(h);
-  // every reservation before anything is enqueued: the staged pairs, the outputs' workspace, the stage's own
   StagePlan sp;
-  OutPlan o;
-  const int in = sp.in(re_im, space, in_bytes);
-  if (int rc = stage_reserve(h, &sp)) return rc;
-  if (int rc = reserve_stage(h, &sp, a, b, out_amp, out_rms, out_drift, out_power, out_space, &o)) return rc;
-  a.x = sp.dev<const float2>(in);
-  set_pointers(h, b, o, out_amp, out_rms, out_drift, out_power, &a);
-  if (int rc = stage_upload(h, sp)) return rc;
-  return run_stage(h, sp, o, a);
+  sp.in(re_im, space, in_bytes);
+  return run_stage(h, &sp, nullptr, a, b, out_amp, out_rms, out_drift, out_power, out_space);
 } FDOCT_CATCH(h)
 
 int fdoct_process_vibro(fdoct_handle h, const void* frames, fdoct_dtype dtype, fdoct_memspace space, int nframes, size_t pitch_bytes,
@@ -205,28 +167,11 @@ int fdoct_process_vibro(fdoct_handle h, const void* frames, fdoct_dtype dtype, f
   fdoct::VibroArgs a;
   VibBytes b;
   if (int rc = plan_vibro(h, "fdoct_process_vibro", params, nframes, h->H, h->D, &a, &b)) return rc;
-  FramePlan p;
-  if (int rc = plan_frames(h, "fdoct_process_vibro", frames, dtype, space, nframes, pitch_bytes, &p)) return rc;
-  size_t in_span = 0;
-  if (__builtin_mul_overflow(p.pitch, (size_t)p.raw_h * (size_t)nframes, &in_span))
-    return fail(h, FDOCT_ERR_INVALID, "fdoct_process_vibro: the batch is too large");
-  if (int rc = check_outputs(h, "fdoct_process_vibro", a, b, space == out_space ? frames : nullptr, in_span, out_amp, out_rms, out_drift, out_power))
+  ComplexFront front;
+  if (int rc = plan_complex_front(h, "fdoct_process_vibro", frames, dtype, space, nframes, pitch_bytes, &front)) return rc;
+  if (int rc = check_outputs(h, "fdoct_process_vibro", a, b, space == out_space ? frames : nullptr, front.in_span, out_amp, out_rms, out_drift, out_power))
     return rc;
-  drop_unread(&a, &b, out_amp);
-  DEVICE_SCOPE(h);
-  // every refusal and reservation before anything is enqueued: the staged frames, the outputs' workspace, the stage's own, the
-  // chain's pairs, then the chain's own checks and its route on the frames where the kernels will read them (a run-time compile
-  // happens here)
-  OutPlan o;
-  if (int rc = stage_reserve(h, &p.stage)) return rc;
-  if (int rc = reserve_stage(h, &p.stage, a, b, out_amp, out_rms, out_drift, out_power, out_space, &o)) return rc;
-  if (int rc = h->ws_cx.reserve(h, (size_t)nframes * (size_t)a.pixels * sizeof(float2))) return rc;
-  if (int rc = enqueue_complex(h, p.stage.dev<const void>(0), dtype, nframes, p.stage.pitch(0), nullptr)) return rc;
-  a.x = h->ws_cx;
-  set_pointers(h, b, o, out_amp, out_rms, out_drift, out_power, &a);
-  if (int rc = stage_upload(h, p.stage)) return rc;
-  if (int rc = enqueue_complex(h, p.stage.dev<const void>(0), dtype, nframes, p.stage.pitch(0), h->ws_cx)) return rc;
-  return run_stage(h, p.stage, o, a);
+  return run_stage(h, &front.p.stage, &front, a, b, out_amp, out_rms, out_drift, out_power, out_space);
 } FDOCT_CATCH(h)
 
 }  // extern "C"

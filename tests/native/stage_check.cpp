@@ -1,6 +1,7 @@
 // stage_check.cpp -- the staging plan of the side entry points (fdoct_amd/csrc/fdoct_stage.h) over the plan type alone: where
 // host-memory items land in the two workspaces, what device-memory items keep, scratch, the in-place pair, the packed pitch, the
-// synchronise flag and the refusal of sizes that would wrap.  tests/test_abi.py builds it with g++ and expects "ok".
+// synchronise flag, the refusal of sizes that would wrap, the vibrometry and dispersion calls' layouts and the overlap check the
+// stages share.  tests/test_abi.py builds it with g++ and expects "ok".
 #include <cstdio>
 #include <initializer_list>
 
@@ -129,16 +130,63 @@ int main() {
     StagePlan s;
     s.out(a, FDOCT_MEM_HOST, SIZE_MAX - 3, 1, SIZE_MAX - 3);
     CHECK(s.rc == FDOCT_ERR_INVALID);
-    StagePlan t;  // ... and so is a fifth item
-    for (int k = 0; k < 4; k++) t.in(a, FDOCT_MEM_DEVICE, 1);
+    StagePlan t;  // ... and so is a ninth item
+    for (int k = 0; k < 8; k++) t.in(a, FDOCT_MEM_DEVICE, 1);
     CHECK(t.rc == FDOCT_OK);
     t.in(a, FDOCT_MEM_DEVICE, 1);
-    CHECK(t.rc == FDOCT_ERR_INVALID && t.count == 4);
+    CHECK(t.rc == FDOCT_ERR_INVALID && t.count == 8);
+  }
+  {  // vibrometry's shape: 4 x 3 x 5 pairs and the four outputs, all in host memory
+    StagePlan p;
+    const int in = p.in(a, FDOCT_MEM_HOST, 4 * 3 * 5 * 8);
+    const int o[4] = {p.out(a, FDOCT_MEM_HOST, 120), p.out(b, FDOCT_MEM_HOST, 60), p.out(c, FDOCT_MEM_HOST, 60), p.out(d, FDOCT_MEM_HOST, 60)};
+    CHECK(p.rc == FDOCT_OK && p.count == 5 && p.sync && p.item[in].staged && p.item[in].offset == 0 && p.in_bytes == 512);
+    for (int k = 0; k < 4; k++) CHECK(p.item[o[k]].staged && p.item[o[k]].output && p.item[o[k]].offset == 256u * k);
+    CHECK(p.out_bytes == 1024);
+    check_layout(p);
+  }
+  {  // the dispersion search's shape: 2 x 16 pairs; sums, row sums and the winner (scratch where null), the table
+    const size_t pairs = 2 * 16 * 8;
+    StagePlan p;  // host memory
+    p.in(a, FDOCT_MEM_HOST, pairs);
+    const int o[4] = {p.out_or_scratch(a, FDOCT_MEM_HOST, 48), p.out_or_scratch(b, FDOCT_MEM_HOST, 96), p.out_or_scratch(c, FDOCT_MEM_HOST, 40),
+                      p.out(d, FDOCT_MEM_HOST, 128)};
+    CHECK(p.rc == FDOCT_OK && p.count == 5 && p.sync && p.item[0].staged && p.in_bytes == 256);
+    for (int k = 0; k < 4; k++) CHECK(p.item[o[k]].staged && p.item[o[k]].offset == 256u * k);
+    CHECK(p.item[o[2]].ptr == c && p.item[o[2]].row == 40 && p.out_bytes == 1024);
+    check_layout(p);
+    StagePlan q;  // device memory, no winner asked for: the winner alone is staged, as scratch
+    q.in(a, FDOCT_MEM_DEVICE, pairs);
+    const int qs = q.out_or_scratch(a, FDOCT_MEM_DEVICE, 48), qr = q.out_or_scratch(b, FDOCT_MEM_DEVICE, 96);
+    const int qb = q.out_or_scratch(nullptr, FDOCT_MEM_DEVICE, 40), qt = q.out(d, FDOCT_MEM_DEVICE, 128);
+    CHECK(q.rc == FDOCT_OK && !q.sync && q.in_bytes == 0 && q.out_bytes == 256);
+    CHECK(!q.item[0].staged && !q.item[qs].staged && !q.item[qr].staged && !q.item[qt].staged && q.item[qt].ptr == d);
+    CHECK(q.item[qb].staged && !q.item[qb].ptr && q.item[qb].offset == 0);
+    check_layout(q);
+    StagePlan r;  // host pairs, device outputs: the pairs alone are staged
+    r.in(a, FDOCT_MEM_HOST, pairs);
+    const int ro[4] = {r.out_or_scratch(a, FDOCT_MEM_DEVICE, 48), r.out_or_scratch(b, FDOCT_MEM_DEVICE, 96), r.out_or_scratch(c, FDOCT_MEM_DEVICE, 40),
+                       r.out(d, FDOCT_MEM_DEVICE, 128)};
+    CHECK(r.rc == FDOCT_OK && r.sync && r.item[0].staged && r.in_bytes == 256 && r.out_bytes == 0);
+    for (int k : ro) CHECK(!r.item[k].staged);
+    CHECK(r.item[ro[2]].ptr == c);
+    check_layout(r);
   }
   {  // the checks the entry points share
     CHECK(valid_mem(FDOCT_MEM_HOST) && valid_mem(FDOCT_MEM_DEVICE) && !valid_mem((fdoct_memspace)7));
     CHECK(valid_layout(FDOCT_LAYOUT_ROWMAJOR_HxD) && valid_layout(FDOCT_LAYOUT_TRANSPOSED_DxH) && !valid_layout((fdoct_layout)9));
     CHECK(overlap(a, 17, b, 4) && !overlap(a, 16, b, 4) && !overlap(nullptr, 64, a, 4) && overlap(b, 4, a, 64));
+    // ... and overlaps() over a call's outputs and its input: disjoint, the input on an output, two outputs, nulls left out
+    const void* const out[3] = {b, c, d};
+    const size_t n16[3] = {16, 16, 16}, n17[3] = {16, 17, 16};
+    CHECK(overlaps(a, 16, out, n16, 3) == OVERLAP_NONE && overlaps(nullptr, 0, out, n16, 3) == OVERLAP_NONE);
+    CHECK(overlaps(a, 17, out, n16, 3) == OVERLAP_INPUT && overlaps(d, 1, out, n16, 3) == OVERLAP_INPUT);
+    CHECK(overlaps(a, 16, out, n17, 3) == OVERLAP_OUTPUTS && overlaps(nullptr, 64, out, n17, 3) == OVERLAP_OUTPUTS);
+    const void* const same[3] = {b, nullptr, b};
+    CHECK(overlaps(nullptr, 0, same, n16, 3) == OVERLAP_OUTPUTS);
+    const void* const gaps[3] = {nullptr, c, nullptr};
+    CHECK(overlaps(a, 64, gaps, n17, 3) == OVERLAP_INPUT && overlaps(a, 32, gaps, n17, 3) == OVERLAP_NONE && overlaps(nullptr, 64, gaps, n17, 3) == OVERLAP_NONE);
+    CHECK(overlaps(a, 64, gaps, n17, 0) == OVERLAP_NONE);
   }
   if (failures) {
     std::printf("%d checks failed\n", failures);
