@@ -332,6 +332,9 @@ def load_library():
     # include/fdoct_vibro.h: likewise (fdoct_amd/vibrometry.py)
     from . import vibrometry
     vibrometry.attach(lib)
+    # include/fdoct_angio.h: likewise (fdoct_amd/angiography.py)
+    from . import angiography
+    angiography.attach(lib)
     _lib = lib
     return lib
 

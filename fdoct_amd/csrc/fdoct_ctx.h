@@ -266,6 +266,9 @@ struct fdoct_ctx {
   DevBuf<float2> ws_vib_ref;
   DevBuf<double> ws_vib_part;
   DevBuf<double2> ws_vib_tab;
+  // angiography (fdoct_angio.cpp): fdoct_process_angio's pairs go through ws_cx; the bulk-motion phasors, one per group, pair and
+  // A-scan.  State like ws_dop_bulk: neither fdoct_clone_to_device nor the state blob carries it
+  DevBuf<float2> ws_ang_bulk;
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
