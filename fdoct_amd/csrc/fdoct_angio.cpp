@@ -35,16 +35,15 @@ int plan_angio(fdoct_ctx* h, const char* fn, const fdoct_angio_params* p, int nf
   if (p->win_ascans < 1 || p->win_ascans > fdoct::kAngMaxWin || p->win_depths < 1 || p->win_depths > fdoct::kAngMaxWin)
     return fail(h, FDOCT_ERR_INVALID, f + ": win_ascans and win_depths must be 1..16");
   if (p->bulk != 0 && p->bulk != 1) return fail(h, FDOCT_ERR_INVALID, f + ": bulk must be 0 or 1");
-  if (p->bulk) {
-    if (p->bulk_first < 0 || p->bulk_first >= depths || p->bulk_count < 0 || p->bulk_count > depths - p->bulk_first)
-      return fail(h, FDOCT_ERR_INVALID, f + ": the bulk range must lie in [0, depths)");
-  }
+  int bulk_count = 0;
+  if (p->bulk && !depth_range(p->bulk_first, p->bulk_count, depths, &bulk_count))
+    return fail(h, FDOCT_ERR_INVALID, f + ": the bulk range must lie in [0, depths)");
   if (!std::isfinite(p->min_power) || p->min_power < 0.0) return fail(h, FDOCT_ERR_INVALID, f + ": min_power must be finite and not negative");
   a->groups = nframes / p->repeats, a->repeats = p->repeats, a->ascans = ascans, a->depths = depths;
   a->wa = p->win_ascans, a->wd = p->win_depths;
   a->use_bulk = p->bulk;
   a->bulk_first = p->bulk ? p->bulk_first : 0;
-  a->bulk_count = !p->bulk ? 0 : p->bulk_count ? p->bulk_count : depths - p->bulk_first;
+  a->bulk_count = bulk_count;
   a->min_power = (float)p->min_power;
   fdoct::angio_plan_launch(a, h ? h->num_cu : 0);
   const size_t pixels = (size_t)ascans * (size_t)depths;                // <= 2^24

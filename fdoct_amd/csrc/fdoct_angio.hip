@@ -2,30 +2,25 @@
 // decorrelation, complex decorrelation with bulk-motion correction, and the mean power (the header states the quantity;
 // tests/angio_model.py restates it in numpy).
 //
-// angio_kernel.  One workgroup of 256 threads takes one tile of 16 A-scans x 64 depth bins of one group at a time and loops over
-// tiles (the grid is capped, fdoct_grid.h).  The tile is staged with its halo, sr x sw = (16 + wa - 1) x (64 + wd - 1) pixels, and
-// staged pixel i belongs to thread i mod 256 for the whole tile: at most K = 10 of them a thread (K = 4 or 6 where the halo tile holds
-// no more than 1024 or 1536 pixels; the three instantiations do the same arithmetic).  Per staged pixel the thread keeps in registers
+// The tile, the window pass and the bulk sum are fdoct_boxtile.h's; what is this file's own:
+//
+// angio_kernel.  Per tile of 16 A-scans x 64 depth bins of one group, staged pixel i of the halo tile belongs to thread i mod 256
+// for the whole tile: at most K = 10 of them a thread (K = 4 or 6 where the halo tile holds no more than 1024 or 1536 pixels; the
+// three instantiations do the same arithmetic).  Per staged pixel the thread keeps in registers
 //     the previous frame's pair, sum_n T'[n] (re, im), sum_n (I_n + I_{n+1}) / 2, sum_n I_n, and Welford's (mean, M2) of I,
 // so every frame of the tile is loaded once -- 8-byte loads, consecutive lanes on consecutive depths of the staged row -- and frame
-// n + 2 is requested before pair n's window passes.  Pixels of the halo outside the image are not loaded: their terms are zeros,
-// which change no sum.
-//   per pair n   (out_decorr only) A_n A_{n+1} and (I_n + I_{n+1}) / 2 go to two planes of LDS; the window pass below gives their
-//                box sums at the thread's four output pixels, whose ratio Q_n is added into a register of the output pixel.
+// n + 2 is requested before pair n's window passes.  Pixels of the halo outside the image are not loaded.
+//   per pair n   (out_decorr only) A_n A_{n+1} and (I_n + I_{n+1}) / 2 go to two planes of LDS; the window pass gives their box
+//                sums at the thread's four output pixels, whose ratio Q_n is added into a register of the output pixel.
 //   at the end   the running sums go through the same two planes -- (T' re, T' im), then (the half sums, sum I), then M2 / N --
-//                one window pass each, then cnt (the window's overlap with the image, from the indices), the mask, the stores:
-//                4 bytes a lane, consecutive lanes on consecutive depths.
-//   window pass  depth: for every staged row and each of the tile's 64 bins, the wd terms along depth in increasing depth; rows: for
-//                every output, the wa depth sums down the column in increasing row.  Two planes at a time.  With the 1 x 1 window
-//                the staged tile is the output tile and a thread's staged pixels are its output pixels: no plane, no barrier.
-// LDS holds planes of floats with a wave's 64 lanes along depth in both phases, so every LDS access of a wave is 64 consecutive
-// words: no padding, no swizzle (fdoct_doppler.hip's header has the argument).  Two staged planes and two planes of depth sums are
-// all of it: 35 KiB at the 16 x 16 window.  Every sum's order depends on the window and the pixel's indices only, what nothing reads
-// is skipped by branches the whole grid takes alike, and a group's tiles read that group's frames only.
+//                one window pass each, then cnt, the mask, the stores: 4 bytes a lane, consecutive lanes on consecutive depths.
+//   1 x 1        the staged tile is the output tile and a thread's staged pixels are its output pixels: no plane, no barrier.
+// Two staged planes and two planes of depth sums are all of the LDS: 35 KiB at the 16 x 16 window.  What nothing reads is skipped by
+// branches the whole grid takes alike, and a group's tiles read that group's frames only.
 //
 // angio_bulk_kernel, in front of it where bulk is set and out_cdecorr is asked for: one workgroup per (group, pair, A-scan) -- a
-// capped grid looping over them -- sums X[n + 1] conj(X[n]) over the bulk range (a strided partial per thread, then a tree in LDS;
-// no atomics, a fixed order) and leaves conj(B) / |B| (1 where B is 0) for the stage to turn T by.
+// capped grid looping over them -- leaves conj(B) / |B| (1 where B is 0), B the sum of X[n + 1] conj(X[n]) over the bulk range, for
+// the stage to turn T by.
 #include "fdoct_angio_kernels.h"
 #include "fdoct_kernels.h"
 
@@ -35,8 +30,8 @@ namespace {
 
 __device__ __forceinline__ float ang_power(float2 x) { return x.x * x.x + x.y * x.y; }
 
-__global__ __launch_bounds__(kAngBulkBlock) void angio_bulk_kernel(const AngioArgs a) {
-  __shared__ float2 part[kAngBulkBlock];
+__global__ __launch_bounds__(kBoxBulkBlock) void angio_bulk_kernel(const AngioArgs a) {
+  __shared__ float2 part[kBoxBulkBlock];
   const int pairs = a.repeats - 1;
   const long long rows = (long long)a.groups * pairs * a.ascans;
   const long long pixels = (long long)a.ascans * a.depths;
@@ -45,105 +40,51 @@ __global__ __launch_bounds__(kAngBulkBlock) void angio_bulk_kernel(const AngioAr
     const int r = (int)(row - gn * a.ascans);
     const int g = (int)(gn / pairs), n = (int)(gn - (long long)g * pairs);
     const float2* x1 = a.x + ((long long)g * a.repeats + n) * pixels + (long long)r * a.depths + a.bulk_first;
-    const float2* x2 = x1 + pixels;
-    float2 s = make_float2(0.f, 0.f);
-    for (int b = threadIdx.x; b < a.bulk_count; b += kAngBulkBlock) {
-      const float2 u = x1[b], v = x2[b];
-      s.x += v.x * u.x + v.y * u.y, s.y += v.y * u.x - v.x * u.y;
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int half = kAngBulkBlock / 2; half > 0; half >>= 1) {
-      if ((int)threadIdx.x < half) {
-        const float2 o = part[threadIdx.x + half];
-        part[threadIdx.x].x += o.x, part[threadIdx.x].y += o.y;
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {  // what the stage multiplies by: conj(B) / |B|, or 1 where B is 0
-      const float2 B = part[0];
-      const float m = hypotf(B.x, B.y);
-      a.bulk[row] = m > 0.f ? make_float2(B.x / m, -(B.y / m)) : make_float2(1.f, 0.f);
-    }
-    __syncthreads();  // part is the next row's
+    const float2 B = box_bulk_sum(x1, x1 + pixels, a.bulk_count, part);
+    if (threadIdx.x == 0) a.bulk[row] = box_phasor(B, true);   // what the stage multiplies by
   }
 }
 
-// The box sums of the planes p0 (and, with `two`, p1) at the thread's four output pixels: o0, o1.  Barriers in front (the planes
-// are written), between the phases and behind (the planes are the next pass's).
-__device__ __forceinline__ void ang_window(const float* p0, const float* p1, float* d0, float* d1, int sr, int sw, int wa, int wd, bool two,
-                                           float (&o0)[kAngOwn], float (&o1)[kAngOwn]) {
-  __syncthreads();
-  for (int i = threadIdx.x; i < sr * kAngTileDepths; i += kAngBlock) {
-    const int at = (i >> 6) * sw + (i & 63);
-    float s0 = 0.f, s1 = 0.f;
-    for (int j = 0; j < wd; j++) {
-      s0 += p0[at + j];
-      if (two) s1 += p1[at + j];
-    }
-    d0[i] = s0;
-    if (two) d1[i] = s1;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kAngOwn; j++) {
-    const int at = (((int)threadIdx.x >> 6) + (kAngBlock / 64) * j) * kAngTileDepths + ((int)threadIdx.x & 63);
-    float s0 = 0.f, s1 = 0.f;
-    for (int w = 0; w < wa; w++) {
-      s0 += d0[at + w * kAngTileDepths];
-      if (two) s1 += d1[at + w * kAngTileDepths];
-    }
-    o0[j] = s0, o1[j] = s1;
-  }
-  __syncthreads();
-}
-
-// The box sums of a thread's staged values v0 (and, with `two`, v1) at its four output pixels.  Through the planes and ang_window --
-// or, with the 1 x 1 window (`unit`), where the staged tile is the output tile and staged pixel k of a thread is its output pixel k,
-// without them: the same two additions from 0 a one-term depth sum and a one-term row sum make.
+// The box sums of a thread's staged values v0 (and, with `two`, v1) at its four output pixels: o[0], o[1].  Through the planes and
+// the window pass -- or, with the 1 x 1 window (`unit`), where the staged tile is the output tile and staged pixel k of a thread
+// is its output pixel k, without them: the same two additions from 0 a one-term depth sum and a one-term row sum make.
 template <int K>
-__device__ __forceinline__ void ang_box(bool unit, const float (&v0)[K], const float (&v1)[K], float* p0, float* p1, float* d0, float* d1, int sr, int sw, int wa,
-                                        int wd, bool two, float (&o0)[kAngOwn], float (&o1)[kAngOwn]) {
-  static_assert(K >= kAngOwn, "the 1 x 1 window's four output pixels are the first four staged ones");
+__device__ __forceinline__ void ang_box(bool unit, const float (&v0)[K], const float (&v1)[K], float* planes, float* sums, int sr, int sw, int wa, int wd,
+                                        bool two, float (&o)[kAngPlanes][kBoxOwn]) {
+  static_assert(K >= kBoxOwn, "the 1 x 1 window's four output pixels are the first four staged ones");
   if (unit) {
 #pragma unroll
-    for (int j = 0; j < kAngOwn; j++) o0[j] = 0.f + (0.f + v0[j]), o1[j] = two ? 0.f + (0.f + v1[j]) : 0.f;
+    for (int j = 0; j < kBoxOwn; j++) o[0][j] = 0.f + (0.f + v0[j]), o[1][j] = two ? 0.f + (0.f + v1[j]) : 0.f;
     return;
   }
   const int ns = sr * sw;
 #pragma unroll
   for (int k = 0; k < K; k++) {
-    const int i = (int)threadIdx.x + k * kAngBlock;
+    const int i = (int)threadIdx.x + k * kBoxBlock;
     if (i < ns) {
-      p0[i] = v0[k];
-      if (two) p1[i] = v1[k];
+      planes[i] = v0[k];
+      if (two) planes[ns + i] = v1[k];
     }
   }
-  ang_window(p0, p1, d0, d1, sr, sw, wa, wd, two, o0, o1);
+  box_window<kAngPlanes>(planes, sums, sr, sw, wa, wd, two ? 2 : 1, o);
 }
 
 template <int K>
-__global__ __launch_bounds__(kAngBlock) void angio_kernel(const AngioArgs a) {
+__global__ __launch_bounds__(kBoxBlock) void angio_kernel(const AngioArgs a) {
   extern __shared__ __align__(16) float ang_lds[];
-  const int sr = kAngTileRows + a.wa - 1, sw = kAngTileDepths + a.wd - 1, ns = sr * sw;
-  float* const p0 = ang_lds;                   // two planes of the staged tile: sr x sw
-  float* const p1 = p0 + ns;
-  float* const d0 = p1 + ns;                   // their depth sums: sr x 64
-  float* const d1 = d0 + sr * kAngTileDepths;
-  const int back_r = (a.wa - 1) / 2, back_d = (a.wd - 1) / 2;
+  const int sr = box_staged_rows(a.wa), sw = box_staged_depths(a.wd), ns = sr * sw;
+  float* const planes = ang_lds;                  // two planes of the staged tile: sr x sw each
+  float* const sums = planes + kAngPlanes * ns;   // their depth sums: sr x 64 each
   const int N = a.repeats, tid = (int)threadIdx.x;
   const long long pixels = (long long)a.ascans * a.depths;
-  const long long per_group = (long long)a.tiles_r * a.tiles_d;
   const bool need_var = a.out_var != nullptr, need_dec = a.out_decorr != nullptr, need_cd = a.out_cdecorr != nullptr;
   const bool need_pow = a.out_power != nullptr || a.min_power > 0.f;
   const bool turn = need_cd && a.use_bulk;
   const bool unit = a.wa == 1 && a.wd == 1;    // the staged tile is the output tile: 16 x 64, staged pixel tid + 256 k is output pixel k
 
   for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-    const int g = (int)(tile / per_group);
-    const int t = (int)(tile - (long long)g * per_group);
-    const int tr = t / a.tiles_d, td = t - tr * a.tiles_d;
-    const int row0 = tr * kAngTileRows - back_r, dep0 = td * kAngTileDepths - back_d;   // the staged tile's first row and depth
+    const BoxTile t = box_tile(tile, a.tiles_r, a.tiles_d, a.wa, a.wd);
+    const int g = t.image;
     const float2* const xg = a.x + (long long)g * N * pixels;                            // the group's first frame
     const long long ug = (long long)g * (N - 1) * a.ascans;                              // ... and its first phasor
 
@@ -152,13 +93,10 @@ __global__ __launch_bounds__(kAngBlock) void angio_kernel(const AngioArgs a) {
     float t_re[K], t_im[K], half[K], sum_i[K], mean[K], m2[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
-      const int i = tid + k * kAngBlock;
+      const int i = tid + k * kBoxBlock;
+      int r, b;
       off[k] = -1, brow[k] = 0;
-      if (i < ns) {
-        const int lr = i / sw, lc = i - lr * sw;
-        const int r = row0 + lr, b = dep0 + lc;
-        if (r >= 0 && r < a.ascans && b >= 0 && b < a.depths) off[k] = r * a.depths + b, brow[k] = r;
-      }
+      if (i < ns && box_staged(t, i, sw, a.ascans, a.depths, &r, &b)) off[k] = r * a.depths + b, brow[k] = r;
       prev[k] = cur[k] = make_float2(0.f, 0.f);
       t_re[k] = t_im[k] = half[k] = sum_i[k] = mean[k] = m2[k] = 0.f;
     }
@@ -177,7 +115,7 @@ __global__ __launch_bounds__(kAngBlock) void angio_kernel(const AngioArgs a) {
         }
       }
     }
-    float q[kAngOwn] = {0.f, 0.f, 0.f, 0.f};
+    float q[kBoxOwn] = {0.f, 0.f, 0.f, 0.f};
 
     for (int n = 0; n + 1 < N; n++) {
       float aa_v[K], hh_v[K];
@@ -215,37 +153,35 @@ __global__ __launch_bounds__(kAngBlock) void angio_kernel(const AngioArgs a) {
           if (off[k] >= 0) cur[k] = xn[off[k]];
       }
       if (need_dec) {
-        float num[kAngOwn], den[kAngOwn];
-        ang_box<K>(unit, aa_v, hh_v, p0, p1, d0, d1, sr, sw, a.wa, a.wd, true, num, den);
+        float nd[kAngPlanes][kBoxOwn];           // numerator, denominator
+        ang_box<K>(unit, aa_v, hh_v, planes, sums, sr, sw, a.wa, a.wd, true, nd);
 #pragma unroll
-        for (int j = 0; j < kAngOwn; j++) q[j] += den[j] == 0.f ? 1.f : num[j] / den[j];
+        for (int j = 0; j < kBoxOwn; j++) q[j] += nd[1][j] == 0.f ? 1.f : nd[0][j] / nd[1][j];
       }
     }
 
-    float w_re[kAngOwn] = {}, w_im[kAngOwn] = {}, w_half[kAngOwn] = {}, w_i[kAngOwn] = {}, w_var[kAngOwn] = {}, none[kAngOwn];
-    if (need_cd) ang_box<K>(unit, t_re, t_im, p0, p1, d0, d1, sr, sw, a.wa, a.wd, true, w_re, w_im);
-    if (need_cd || need_pow) ang_box<K>(unit, half, sum_i, p0, p1, d0, d1, sr, sw, a.wa, a.wd, true, w_half, w_i);
+    float w_t[kAngPlanes][kBoxOwn] = {}, w_hi[kAngPlanes][kBoxOwn] = {}, w_var[kAngPlanes][kBoxOwn] = {};   // (T' re, T' im), (half sums, sum I), (V, -)
+    if (need_cd) ang_box<K>(unit, t_re, t_im, planes, sums, sr, sw, a.wa, a.wd, true, w_t);
+    if (need_cd || need_pow) ang_box<K>(unit, half, sum_i, planes, sums, sr, sw, a.wa, a.wd, true, w_hi);
     if (need_var) {
 #pragma unroll
       for (int k = 0; k < K; k++) m2[k] = m2[k] / (float)N;   // V
-      ang_box<K>(unit, m2, m2, p0, p1, d0, d1, sr, sw, a.wa, a.wd, false, w_var, none);
+      ang_box<K>(unit, m2, m2, planes, sums, sr, sw, a.wa, a.wd, false, w_var);
     }
 
 #pragma unroll
-    for (int j = 0; j < kAngOwn; j++) {
-      const int r = tr * kAngTileRows + (tid >> 6) + (kAngBlock / 64) * j, b = td * kAngTileDepths + (tid & 63);
-      if (r >= a.ascans || b >= a.depths) continue;
-      const int r_lo = max(r - back_r, 0), r_hi = min(r + a.wa / 2, a.ascans - 1);
-      const int b_lo = max(b - back_d, 0), b_hi = min(b + a.wd / 2, a.depths - 1);
-      const int terms = (r_hi - r_lo + 1) * (b_hi - b_lo + 1);
+    for (int j = 0; j < kBoxOwn; j++) {
+      int r, b;
+      if (!box_owned(t, j, a.ascans, a.depths, &r, &b)) continue;
+      const int terms = box_terms(r, b, a.ascans, a.depths, a.wa, a.wd);
       const float cnt = (float)terms;
-      const float power = w_i[j] / (float)(N * terms);
+      const float power = w_hi[1][j] / (float)(N * terms);
       const bool masked = a.min_power > 0.f && power < a.min_power;
       const long long o = ((long long)g * a.ascans + r) * (long long)a.depths + b;
       if (a.out_power) a.out_power[o] = power;
-      if (a.out_var) a.out_var[o] = masked ? 0.f : w_var[j] / cnt;
+      if (a.out_var) a.out_var[o] = masked ? 0.f : w_var[0][j] / cnt;
       if (a.out_decorr) a.out_decorr[o] = masked ? 0.f : 1.f - q[j] / (float)(N - 1);
-      if (a.out_cdecorr) a.out_cdecorr[o] = (masked || w_half[j] == 0.f) ? 0.f : 1.f - hypotf(w_re[j], w_im[j]) / w_half[j];
+      if (a.out_cdecorr) a.out_cdecorr[o] = (masked || w_hi[0][j] == 0.f) ? 0.f : 1.f - hypotf(w_t[0][j], w_t[1][j]) / w_hi[0][j];
     }
   }
 }
@@ -254,7 +190,7 @@ template <int K>
 hipError_t launch_stage(const AngioArgs& a, hipStream_t st) {
   static LdsGrant grant;   // one per instantiation
   if (hipError_t e = grant.ensure(angio_kernel<K>, a.lds_bytes); e != hipSuccess) return e;
-  hipLaunchKernelGGL(angio_kernel<K>, dim3((unsigned)a.blocks), dim3(kAngBlock), a.lds_bytes, st, a);
+  hipLaunchKernelGGL(angio_kernel<K>, dim3((unsigned)a.blocks), dim3(kBoxBlock), a.lds_bytes, st, a);
   return hipGetLastError();
 }
 
@@ -262,13 +198,13 @@ hipError_t launch_stage(const AngioArgs& a, hipStream_t st) {
 
 hipError_t launch_angio(const AngioArgs& a, hipStream_t st) {
   if (!a.x || a.blocks < 1 || a.tiles < 1 || a.repeats < kAngMinRepeats || a.groups < 1) return hipErrorInvalidValue;
-  if (a.wa < 1 || a.wa > kAngMaxWin || a.wd < 1 || a.wd > kAngMaxWin || a.lds_bytes != angio_lds_bytes(a.wa, a.wd)) return hipErrorInvalidValue;
+  if (a.wa < 1 || a.wa > kAngMaxWin || a.wd < 1 || a.wd > kAngMaxWin || a.lds_bytes != box_lds_bytes(kAngPlanes, a.wa, a.wd)) return hipErrorInvalidValue;
   if (!a.out_var && !a.out_decorr && !a.out_cdecorr && !a.out_power) return hipErrorInvalidValue;
   if (a.use_bulk && (a.bulk_blocks < 1 || !a.bulk || a.bulk_count < 1)) return hipErrorInvalidValue;
   if (a.keep != kAngKeepSmall && a.keep != kAngKeepMid && a.keep != kAngKeepLarge) return hipErrorInvalidValue;
-  if ((kAngTileRows + a.wa - 1) * (kAngTileDepths + a.wd - 1) > a.keep * kAngBlock) return hipErrorInvalidValue;   // every staged pixel has its thread
+  if (box_staged_rows(a.wa) * box_staged_depths(a.wd) > a.keep * kBoxBlock) return hipErrorInvalidValue;   // every staged pixel has its thread
   if (a.use_bulk) {
-    hipLaunchKernelGGL(angio_bulk_kernel, dim3((unsigned)a.bulk_blocks), dim3(kAngBulkBlock), 0, st, a);
+    hipLaunchKernelGGL(angio_bulk_kernel, dim3((unsigned)a.bulk_blocks), dim3(kBoxBulkBlock), 0, st, a);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }
   return a.keep == kAngKeepSmall ? launch_stage<kAngKeepSmall>(a, st) : a.keep == kAngKeepMid ? launch_stage<kAngKeepMid>(a, st) : launch_stage<kAngKeepLarge>(a, st);

@@ -1,10 +1,10 @@
-// fdoct_angio_kernels.h -- the device side of include/fdoct_angio.h (fdoct_angio.hip): the argument block of the two kernels, the
-// tile geometry as plain functions (fdoct_angio.cpp refuses with them before anything is enqueued), and the launcher.  Internal:
-// fdoct_angio.cpp is the only caller.
+// fdoct_angio_kernels.h -- the device side of include/fdoct_angio.h (fdoct_angio.hip): the argument block of the two kernels, its
+// launch fields through fdoct_boxtile.h's tile geometry (fdoct_angio.cpp decides them before anything is enqueued), and the
+// launcher.  Internal: fdoct_angio.cpp is the only caller.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "fdoct_grid.h"
+#include "fdoct_boxtile.h"
 
 namespace fdoct {
 
@@ -12,12 +12,7 @@ constexpr int kAngMaxWin = 16;          // window sizes 1..16 on both axes: what
 constexpr int kAngMinRepeats = 2, kAngMaxRepeats = 64;
 constexpr int kAngMaxFrames = 65536;
 constexpr long long kAngMaxPixels = 1LL << 24;
-constexpr int kAngTileRows = 16;        // one workgroup's tile: 16 A-scans x 64 depth bins of output, 256 threads
-constexpr int kAngTileDepths = 64;      // (one wave's 64 lanes lie along depth in every pass)
-constexpr int kAngBlock = 256;
-constexpr int kAngOwn = kAngTileRows * kAngTileDepths / kAngBlock;   // output pixels a thread owns: 4
-constexpr int kAngWavesPerCu = 16;      // the grid's cap: four workgroups a CU (the 16 x 16 window's tile is 35 KiB of LDS)
-constexpr int kAngBulkBlock = 256;      // the bulk sums: one workgroup per (group, pair, A-scan)
+constexpr int kAngPlanes = 2;           // the tile's planes: what one window pass sums
 // Staged pixels a thread keeps in registers: ceil((16 + wa - 1) (64 + wd - 1) / 256), rounded up to one of the kernel's three
 // instantiations -- 4: the 1 x 1 window; 6: up to 22 x 69 staged, the 5 x 5 and 7 x 6 windows; 10: up to 31 x 79, the 16 x 16 window.
 constexpr int kAngKeepSmall = 4, kAngKeepMid = 6, kAngKeepLarge = 10;
@@ -37,30 +32,16 @@ struct AngioArgs {
   // decided by angio_plan_launch
   int tiles_r = 0, tiles_d = 0;
   long long tiles = 0;
-  int keep = 0;                  // kAngKeepSmall or kAngKeepLarge
+  int keep = 0;                  // kAngKeepSmall, kAngKeepMid or kAngKeepLarge
   int blocks = 0, bulk_blocks = 0;
   unsigned lds_bytes = 0;
 };
 
-// The staged halo tile and the depth-summed rows behind it, two planes of floats each.
-inline unsigned angio_lds_bytes(int wa, int wd) {
-  const unsigned sr = kAngTileRows + wa - 1, sw = kAngTileDepths + wd - 1;
-  return (sr * sw + sr * kAngTileDepths) * 2u * (unsigned)sizeof(float);
-}
-
 // Fills the launch fields from the others.  Nothing is enqueued.
 inline void angio_plan_launch(AngioArgs* a, int num_cu) {
-  a->tiles_r = (a->ascans + kAngTileRows - 1) / kAngTileRows;
-  a->tiles_d = (a->depths + kAngTileDepths - 1) / kAngTileDepths;
-  a->tiles = (long long)a->groups * a->tiles_r * a->tiles_d;
-  a->lds_bytes = angio_lds_bytes(a->wa, a->wd);
-  const int staged = (kAngTileRows + a->wa - 1) * (kAngTileDepths + a->wd - 1);
-  a->keep = staged <= kAngKeepSmall * kAngBlock ? kAngKeepSmall : staged <= kAngKeepMid * kAngBlock ? kAngKeepMid : kAngKeepLarge;
-  const long long cap = resident_blocks(num_cu, kAngWavesPerCu, kAngBlock);
-  a->blocks = (int)(a->tiles < cap ? a->tiles : cap);
-  const long long rows = (long long)a->groups * (a->repeats - 1) * a->ascans;
-  const long long bulk_cap = resident_blocks(num_cu, kAngWavesPerCu, kAngBulkBlock);
-  a->bulk_blocks = a->use_bulk ? (int)(rows < bulk_cap ? rows : bulk_cap) : 0;
+  box_plan_launch(a, kAngPlanes, a->groups, a->ascans, (long long)a->groups * (a->repeats - 1) * a->ascans, num_cu);
+  const int staged = box_staged_rows(a->wa) * box_staged_depths(a->wd);
+  a->keep = staged <= kAngKeepSmall * kBoxBlock ? kAngKeepSmall : staged <= kAngKeepMid * kBoxBlock ? kAngKeepMid : kAngKeepLarge;
 }
 
 // The bulk sums (a.use_bulk) and the stage, in that order on `st`.

@@ -23,10 +23,9 @@ int plan_doppler(fdoct_ctx* h, const char* fn, const fdoct_doppler_params* p, in
   if (p->lag < 1) return fail(h, FDOCT_ERR_INVALID, f + ": lag must be at least 1");
   if (!fdoct::doppler_pairs(p->axis, p->lag, nframes, ascans, &a->pair_images, &a->pair_rows))
     return fail(h, FDOCT_ERR_INVALID, f + ": the lag leaves no pair");
-  if (p->bulk) {
-    if (p->bulk_first < 0 || p->bulk_first >= depths || p->bulk_count < 0 || p->bulk_count > depths - p->bulk_first)
-      return fail(h, FDOCT_ERR_INVALID, f + ": the bulk range must lie in [0, depths)");
-  }
+  int bulk_count = 0;
+  if (p->bulk && !depth_range(p->bulk_first, p->bulk_count, depths, &bulk_count))
+    return fail(h, FDOCT_ERR_INVALID, f + ": the bulk range must lie in [0, depths)");
   if (!std::isfinite(p->scale) || !std::isfinite(p->min_power) || p->min_power < 0.0)
     return fail(h, FDOCT_ERR_INVALID, f + ": scale and min_power must be finite, min_power not negative");
   a->ascans = ascans, a->depths = depths;
@@ -34,7 +33,7 @@ int plan_doppler(fdoct_ctx* h, const char* fn, const fdoct_doppler_params* p, in
   a->wa = p->win_ascans, a->wd = p->win_depths;
   a->use_bulk = p->bulk ? 1 : 0;
   a->bulk_first = p->bulk ? p->bulk_first : 0;
-  a->bulk_count = !p->bulk ? 0 : p->bulk_count ? p->bulk_count : depths - p->bulk_first;
+  a->bulk_count = bulk_count;
   a->scale = (float)p->scale, a->min_power = (float)p->min_power;
   return FDOCT_OK;
 }

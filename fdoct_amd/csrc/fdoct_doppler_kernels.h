@@ -1,19 +1,15 @@
 // fdoct_doppler_kernels.h -- the device side of include/fdoct_doppler.h (fdoct_doppler.hip): the argument block of the two
-// kernels, the pair images' shape and the tile geometry as plain functions (fdoct_doppler.cpp refuses with them before anything
-// is enqueued), and the launchers.  Internal: fdoct_doppler.cpp is the only caller.
+// kernels, the pair images' shape as a plain function (fdoct_doppler.cpp refuses with it before anything is enqueued), the launch
+// fields through fdoct_boxtile.h's tile geometry, and the launchers.  Internal: fdoct_doppler.cpp is the only caller.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "fdoct_grid.h"
+#include "fdoct_boxtile.h"
 
 namespace fdoct {
 
 constexpr int kDopMaxWin = 32;        // window sizes 1..32 on both axes
-constexpr int kDopTileRows = 16;      // one workgroup's tile: 16 pair rows x 64 depth bins of output, 256 threads
-constexpr int kDopTileDepths = 64;    // (one wave's 64 lanes lie along depth in every pass)
-constexpr int kDopBlock = 256;
-constexpr int kDopWavesPerCu = 16;    // the grid's cap: four workgroups a CU (the 4 x 8 window's tile is 31 KiB of LDS; five fit)
-constexpr int kDopBulkBlock = 256;    // the bulk sums: one workgroup per pair row
+constexpr int kDopPlanes = 3;         // the tile's planes: T re, T im, |X1|^2 + |X2|^2
 
 // One call as the kernels see it.
 struct DopplerArgs {
@@ -44,23 +40,9 @@ inline bool doppler_pairs(int axis, int lag, int nframes, int ascans, int* pair_
   return true;
 }
 
-// The staged halo tile and the depth-summed rows behind it, three planes of floats each (re, im, power).
-inline unsigned doppler_lds_bytes(int wa, int wd) {
-  const unsigned sr = kDopTileRows + wa - 1, sw = kDopTileDepths + wd - 1;
-  return (sr * sw + sr * kDopTileDepths) * 3u * (unsigned)sizeof(float);
-}
-
 // Fills the launch fields from the others.  Nothing is enqueued.
 inline void doppler_plan_launch(DopplerArgs* a, int num_cu) {
-  a->tiles_r = (a->pair_rows + kDopTileRows - 1) / kDopTileRows;
-  a->tiles_d = (a->depths + kDopTileDepths - 1) / kDopTileDepths;
-  a->tiles = (long long)a->pair_images * a->tiles_r * a->tiles_d;
-  a->lds_bytes = doppler_lds_bytes(a->wa, a->wd);
-  const long long cap = resident_blocks(num_cu, kDopWavesPerCu, kDopBlock);
-  a->blocks = (int)(a->tiles < cap ? a->tiles : cap);
-  const long long rows = (long long)a->pair_images * a->pair_rows;
-  const long long bulk_cap = resident_blocks(num_cu, kDopWavesPerCu, kDopBulkBlock);
-  a->bulk_blocks = a->use_bulk ? (int)(rows < bulk_cap ? rows : bulk_cap) : 0;
+  box_plan_launch(a, kDopPlanes, a->pair_images, a->pair_rows, (long long)a->pair_images * a->pair_rows, num_cu);
 }
 
 // The bulk sums (a.use_bulk) and the stage, in that order on `st`.

@@ -16,6 +16,13 @@ inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
   return a && b && x < y + nb && y < x + na;
 }
+// A stage's depth range [first, first + count) of `depths` bins, count 0 meaning "to the last depth" (the Doppler and angiography
+// bulk ranges, vibrometry's reference range): false where it does not lie in [0, depths), else *resolved is the count, > 0.
+inline bool depth_range(int first, int count, int depths, int* resolved) {
+  if (first < 0 || first >= depths || count < 0 || count > depths - first) return false;
+  *resolved = count ? count : depths - first;
+  return true;
+}
 // What a call with n outputs of bytes[i] bytes at out[i] (null: absent) and an input range (in null: none, or one in another memory
 // space) refuses: the input lying on an output, or two outputs on each other.
 enum Overlap { OVERLAP_NONE = 0, OVERLAP_INPUT, OVERLAP_OUTPUTS };

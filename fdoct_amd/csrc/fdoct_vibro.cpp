@@ -36,10 +36,9 @@ int plan_vibro(fdoct_ctx* h, const char* fn, const fdoct_vibro_params* p, int nf
     if (!std::isfinite(p->freq[j]) || !(p->freq[j] > 0.0) || p->freq[j] > 0.5)
       return fail(h, FDOCT_ERR_INVALID, f + ": every frequency must lie in (0, 0.5] cycles per frame");
   if (p->ref != 0 && p->ref != 1) return fail(h, FDOCT_ERR_INVALID, f + ": ref must be 0 or 1");
-  if (p->ref) {
-    if (p->ref_first < 0 || p->ref_first >= depths || p->ref_count < 0 || p->ref_count > depths - p->ref_first)
-      return fail(h, FDOCT_ERR_INVALID, f + ": the reference range must lie in [0, depths)");
-  }
+  int ref_count = 0;
+  if (p->ref && !depth_range(p->ref_first, p->ref_count, depths, &ref_count))
+    return fail(h, FDOCT_ERR_INVALID, f + ": the reference range must lie in [0, depths)");
   if (p->detrend != 0 && p->detrend != 1) return fail(h, FDOCT_ERR_INVALID, f + ": detrend must be 0 or 1");
   if (p->window != FDOCT_VIBRO_RECT && p->window != FDOCT_VIBRO_HANN) return fail(h, FDOCT_ERR_INVALID, f + ": bad window");
   if (!std::isfinite(p->scale) || !std::isfinite(p->min_power) || p->min_power < 0.0)
@@ -48,7 +47,7 @@ int plan_vibro(fdoct_ctx* h, const char* fn, const fdoct_vibro_params* p, int nf
   a->T = nframes, a->ascans = ascans, a->depths = depths;
   a->use_ref = p->ref;
   a->ref_first = p->ref ? p->ref_first : 0;
-  a->ref_count = !p->ref ? 0 : p->ref_count ? p->ref_count : depths - p->ref_first;
+  a->ref_count = ref_count;
   a->detrend = p->detrend, a->window = p->window, a->nfreq = p->nfreq;
   for (int j = 0; j < fdoct::kVibMaxFreq; j++) a->freq[j] = j < p->nfreq ? p->freq[j] : 0.0;
   a->scale = p->scale, a->min_power = p->min_power;

@@ -57,7 +57,7 @@ import helpers
 U = 2.0 ** -24
 TINY = 2.0 ** -126
 NAMES = ("var", "decorr", "cdecorr", "power")
-TILE_ROWS, TILE_DEPTHS, BLOCKS_PER_CU = 16, 64, 4     # kAngTileRows, kAngTileDepths, kAngWavesPerCu / 4 (fdoct_angio_kernels.h)
+TILE_ROWS, TILE_DEPTHS, BLOCKS_PER_CU = 16, 64, 4     # kBoxRows, kBoxDepths, kBoxWavesPerCu / 4 (fdoct_boxtile.h)
 PLAN_CUS = 256                                        # what fdoct_angio_plan, which has no handle, takes for the card
 RATIOS = []   # (what, {output: (gpu ratio, f32 ratio)}), one per check()
 

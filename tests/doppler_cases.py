@@ -11,9 +11,9 @@ import numpy as np
 
 from doppler_model import ASCANS, FRAMES
 
-# Keep equal to fdoct_doppler_kernels.h:
-TILE_ROWS, TILE_DEPTHS = 16, 64     # kDopTileRows, kDopTileDepths
-BLOCKS_PER_CU = 4                   # kDopWavesPerCu / (kDopBlock / 64): the cap of both kernels' grids, per CU
+# Keep equal to fdoct_boxtile.h and fdoct_doppler_kernels.h:
+TILE_ROWS, TILE_DEPTHS = 16, 64     # kBoxRows, kBoxDepths
+BLOCKS_PER_CU = 4                   # kBoxWavesPerCu / (kBoxBlock / 64): the cap of both kernels' grids, per CU
 MAX_WIN = 32                        # kDopMaxWin
 
 
@@ -83,7 +83,7 @@ def tiles(pair_images, pair_rows, depths):
 
 
 def grid_cap(cus):
-    """resident_blocks(num_cu, kDopWavesPerCu, kDopBlock): the most workgroups either kernel is launched with."""
+    """resident_blocks(num_cu, kBoxWavesPerCu, kBoxBlock): the most workgroups either kernel is launched with."""
     return cus * BLOCKS_PER_CU
 
 

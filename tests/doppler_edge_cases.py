@@ -16,7 +16,7 @@ from doppler_model import ASCANS, FRAMES
 TILE_ROWS, TILE_DEPTHS = dc.TILE_ROWS, dc.TILE_DEPTHS
 
 
-# ---- the launch arithmetic restated (fdoct_doppler_kernels.h: doppler_lds_bytes) --------------------------------------------------
+# ---- the launch arithmetic restated (fdoct_boxtile.h: box_lds_bytes, three planes) --------------------------------------------------
 def lds_bytes(wa, wd):
     """Three planes of floats of the staged halo tile, (TILE_ROWS + wa - 1) x (TILE_DEPTHS + wd - 1), and three of its depth sums,
     (TILE_ROWS + wa - 1) x TILE_DEPTHS: 12 (15 + wa)(127 + wd)."""

@@ -1,7 +1,7 @@
 // stage_check.cpp -- the staging plan of the side entry points (fdoct_amd/csrc/fdoct_stage.h) over the plan type alone: where
 // host-memory items land in the two workspaces, what device-memory items keep, scratch, the in-place pair, the packed pitch, the
-// synchronise flag, the refusal of sizes that would wrap, the vibrometry and dispersion calls' layouts and the overlap check the
-// stages share.  tests/test_abi.py builds it with g++ and expects "ok".
+// synchronise flag, the refusal of sizes that would wrap, the vibrometry and dispersion calls' layouts, and the overlap check and the
+// depth range the stages share.  tests/test_abi.py builds it with g++ and expects "ok".
 #include <cstdio>
 #include <initializer_list>
 
@@ -187,6 +187,13 @@ int main() {
     const void* const gaps[3] = {nullptr, c, nullptr};
     CHECK(overlaps(a, 64, gaps, n17, 3) == OVERLAP_INPUT && overlaps(a, 32, gaps, n17, 3) == OVERLAP_NONE && overlaps(nullptr, 64, gaps, n17, 3) == OVERLAP_NONE);
     CHECK(overlaps(a, 64, gaps, n17, 0) == OVERLAP_NONE);
+    // ... and the depth range of the bulk and reference sums: inside [0, depths), a count of 0 reaching the last depth
+    int n = -1;
+    CHECK(!depth_range(-1, 1, 100, &n) && !depth_range(100, 0, 100, &n) && !depth_range(0, -1, 100, &n) && n == -1);
+    CHECK(depth_range(30, 0, 100, &n) && n == 70);
+    CHECK(depth_range(30, 70, 100, &n) && n == 70 && depth_range(99, 1, 100, &n) && n == 1 && depth_range(0, 0, 1, &n) && n == 1);
+    n = -1;
+    CHECK(!depth_range(30, 71, 100, &n) && !depth_range(99, 2, 100, &n) && !depth_range(0, 0, 0, &n) && n == -1);
   }
   if (failures) {
     std::printf("%d checks failed\n", failures);
