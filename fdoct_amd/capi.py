@@ -335,6 +335,9 @@ def load_library():
     # include/fdoct_angio.h: likewise (fdoct_amd/angiography.py)
     from . import angiography
     angiography.attach(lib)
+    # include/fdoct_cxavg.h: likewise (fdoct_amd/coherent.py)
+    from . import coherent
+    coherent.attach(lib)
     _lib = lib
     return lib
 

@@ -269,6 +269,9 @@ struct fdoct_ctx {
   // angiography (fdoct_angio.cpp): fdoct_process_angio's pairs go through ws_cx; the bulk-motion phasors, one per group, pair and
   // A-scan.  State like ws_dop_bulk: neither fdoct_clone_to_device nor the state blob carries it
   DevBuf<float2> ws_ang_bulk;
+  // coherent averaging (fdoct_cxavg.cpp): fdoct_process_cxavg's pairs go through ws_cx; with align 2 the phasors, one per group and
+  // repeat, and behind them the per-row sums they are made from.  State like ws_ang_bulk
+  DevBuf<float2> ws_cxa;
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
