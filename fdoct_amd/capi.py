@@ -338,6 +338,9 @@ def load_library():
     # include/fdoct_cxavg.h: likewise (fdoct_amd/coherent.py)
     from . import coherent
     coherent.attach(lib)
+    # include/fdoct_ssada.h: likewise (fdoct_amd/ssada.py)
+    from . import ssada
+    ssada.attach(lib)
     _lib = lib
     return lib
 

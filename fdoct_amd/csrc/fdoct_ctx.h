@@ -20,6 +20,7 @@
 //   fdoct_doppler.cpp those of include/fdoct_doppler.h (phase-resolved Doppler from complex A-scans: the stage alone, and behind enqueue_complex)
 //   fdoct_dispersion.cpp those of include/fdoct_dispersion.h (the dispersion search over (a2, a3): the stage alone, and behind enqueue_complex)
 //   fdoct_vibro.cpp   those of include/fdoct_vibro.h (vibrometry from the phase over time: the stage alone, and behind enqueue_complex)
+//   fdoct_ssada.cpp   those of include/fdoct_ssada.h (split-spectrum amplitude decorrelation: the stage alone, and behind enqueue_complex)
 //   fdoct_stage.h     the staging plan of host-memory arguments: the side entry points', fdoct_process's single shot (stage_reserve / stage_upload / stage_finish, below, commit it)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
@@ -272,6 +273,9 @@ struct fdoct_ctx {
   // coherent averaging (fdoct_cxavg.cpp): fdoct_process_cxavg's pairs go through ws_cx; with align 2 the phasors, one per group and
   // repeat, and behind them the per-row sums they are made from.  State like ws_ang_bulk
   DevBuf<float2> ws_cxa;
+  // split-spectrum decorrelation (fdoct_ssada.cpp): fdoct_process_ssada's pairs go through ws_cx; one pass's band pairs with the
+  // per-band decorrelation and power behind them, and the transform's twiddles with the bands' table.  State like ws_ang_bulk
+  DevBuf<unsigned char> ws_ssa, ws_ssa_tab;
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
