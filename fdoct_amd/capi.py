@@ -341,6 +341,9 @@ def load_library():
     # include/fdoct_ssada.h: likewise (fdoct_amd/ssada.py)
     from . import ssada
     ssada.attach(lib)
+    # include/fdoct_enface.h: likewise (fdoct_amd/enface.py)
+    from . import enface
+    enface.attach(lib)
     _lib = lib
     return lib
 

@@ -21,6 +21,7 @@
 //   fdoct_dispersion.cpp those of include/fdoct_dispersion.h (the dispersion search over (a2, a3): the stage alone, and behind enqueue_complex)
 //   fdoct_vibro.cpp   those of include/fdoct_vibro.h (vibrometry from the phase over time: the stage alone, and behind enqueue_complex)
 //   fdoct_ssada.cpp   those of include/fdoct_ssada.h (split-spectrum amplitude decorrelation: the stage alone, and behind enqueue_complex)
+//   fdoct_enface.cpp  those of include/fdoct_enface.h (en-face projection of a volume over depth slabs: the stage alone, and behind enqueue)
 //   fdoct_stage.h     the staging plan of host-memory arguments: the side entry points', fdoct_process's single shot (stage_reserve / stage_upload / stage_finish, below, commit it)
 // (round 5: one 2900-line file until then; the seams are DESIGN.md 3.5's).  Internal: nothing outside fdoct_amd/csrc includes it.
 #pragma once
@@ -276,6 +277,10 @@ struct fdoct_ctx {
   // split-spectrum decorrelation (fdoct_ssada.cpp): fdoct_process_ssada's pairs go through ws_cx; one pass's band pairs with the
   // per-band decorrelation and power behind them, and the transform's twiddles with the bands' table.  State like ws_ang_bulk
   DevBuf<unsigned char> ws_ssa, ws_ssa_tab;
+  // en-face projection (fdoct_enface.cpp): the raw surfaces, one per position and A-scan, between its two kernels; the row-major
+  // volume fdoct_process_enface's chain writes.  State like ws_ang_bulk
+  DevBuf<int32_t> ws_enf_surf;
+  DevBuf<float> ws_enf_vol;
 
   fdoct_timing timing{};
   bool timing_pending = false, timing_staged = false;
